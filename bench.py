@@ -14,7 +14,11 @@ rank runs its own job of the same size on its own GPU -> "weak" scaling; ranks
 only meet at the barriers around the timed region (a TCP store of rank 0; no
 torch in the rank processes) and value = all ranks' reads / the slowest rank's time.
 
-The JSON line also carries
+A plain run does only what the headline needs: make the sets resident, warm up,
+time --steps steps, write the last step's outputs (--dump-outputs DIR) and print
+the line.  Everything else below takes runs of its own and needs --full.
+
+With --full the JSON line also carries
   roofline     — the kernel with the largest measured share of the step's device
                  time (a hipEvent pair around every launch, commet_kernel_times,
                  taken in untimed extra steps), priced in the HBM bytes it really
@@ -35,6 +39,7 @@ The JSON line also carries
                  included, so the per-N values are one curve (detail.matrix has
                  the per-rank profile; detail.matrix_configs2 is configs[2],
                  10 x 10 M reads, on one GPU; --no-matrix skips both).
+  first_job_*, detail.ragged, detail.p_ref_probes — the extra legs below.
 """
 import argparse
 import hashlib
@@ -59,6 +64,12 @@ def parse_args():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline: first-job and per-kernel timing steps, the roofline, the CPU baseline, "
+                         "the ragged leg and the matrix legs (off by default: a plain run times the steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step returned as float .npy files into DIR: tags.npy (the search "
+                         "set's tag bytes) and stats.npy ([indexed, searched, shared]); with several ranks, rank<r>_ in front of the names")
     ap.add_argument("--reads", type=int, default=10_000_000, help="reads per set (configs[1]: 10 M)")
     ap.add_argument("--read-len", type=int, default=100)
     ap.add_argument("-k", type=int, default=32)
@@ -66,7 +77,7 @@ def parse_args():
     ap.add_argument("--cpu-sample", type=int, default=1_000_000, help="reads per set of the CPU-baseline sample (0 = skip)")
     ap.add_argument("--cpu-full", action="store_true",
                     help="also run the reference CPU tool ONCE on the whole job (both full sets, one core; 10-15 minutes at configs[1]) and "
-                         "compare its .bv bytes and log line with the GPU's: cpu_baseline.full_job (off by default: the driver's run stays short)")
+                         "compare its .bv bytes and log line with the GPU's: cpu_baseline.full_job (implies --full)")
     ap.add_argument("--no-probe-count", action="store_true", help="skip the extra (untimed) P_ref counting step")
     ap.add_argument("--no-kernel-times", action="store_true", help="skip the extra (untimed) per-kernel timing steps")
     ap.add_argument("--kt-steps", type=int, default=3, help="untimed steps of the per-kernel timing leg")
@@ -86,7 +97,9 @@ def parse_args():
     ap.add_argument("--ragged-only", action="store_true", help="the headline step itself on ragged sets (A/B runs, profiles): value is then the ragged rate")
     ap.add_argument("--rendezvous-only", action="store_true",
                     help="start the ranks, meet at the barriers, print the line's launch fields and leave (no GPU work: the CPU test of the launch path)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    args.full = args.full or args.cpu_full
+    return args
 
 
 def self_launch(args):
@@ -518,6 +531,25 @@ def matrix_leg(args, ranks, n, note=None, fatal_hook=None, ragged=None):
     return out
 
 
+DUMP_LIMIT = 64 << 20         # bytes of all ranks' --dump-outputs files together
+
+
+def dump_outputs(dirname, tags, stats, rank, world):
+    """--dump-outputs: what the last timed step handed its caller, as float .npy files — tags.npy, the search set's BooleanVector
+    bytes (one byte per 8 reads, as float32) and stats.npy, [indexed, searched, shared] of the reference's log line (float64).
+    Where all ranks' tags would pass DUMP_LIMIT, a fixed sample of the bytes (seeded, sorted positions) is written instead."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    prefix = f"rank{rank}_" if world > 1 else ""
+    t = np.asarray(tags, dtype=np.uint8)
+    cap = (DUMP_LIMIT // world - 4096) // 4
+    if t.size > cap:
+        t = t[np.sort(np.random.default_rng(20261016).choice(t.size, cap, replace=False))]
+    np.save(os.path.join(dirname, prefix + "tags.npy"), t.astype(np.float32))
+    np.save(os.path.join(dirname, prefix + "stats.npy"),
+            np.array([stats["indexed"], stats["searched"], stats["shared"]], dtype=np.float64))
+
+
 def main():
     args = parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -599,6 +631,8 @@ def main():
     elapsed = sharding.timed_region(ranks, ctx.synchronize, step, args.steps)
     progress(ranks, f"timed region: {elapsed * 1000.0 / args.steps:.3f} ms per step")
     stats, info = last["stats"], last["info"]
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last["tags"][0], stats[0], rank, world)
 
     # the first job on a SET also builds what is cached with the set (the tiled search's query list): not part of the
     # steady-state `value`, reported beside it (warm context) —
@@ -608,23 +642,24 @@ def main():
     # seen in round 6) the first two time that charge, the third the job
     query_list_bytes = qrs.cache_bytes
     first_job_s, first_job_all, fresh_sets = None, [], []
-    for i in range(3):
-        if i == 2:
-            fresh_sets.pop(0).close()
-        fresh_sets.append(commet_amd.ReadSet.from_files(ctx, [(b1, o1)]))
-        ctx.synchronize()
-        t_c = time.perf_counter()
-        ctx.index_and_search(irs, [fresh_sets[-1]])
-        ctx.synchronize()
-        dt = time.perf_counter() - t_c
-        first_job_all.append(round(dt * 1e3, 3))
-        first_job_s = dt if first_job_s is None else min(first_job_s, dt)
-    for fs in fresh_sets:
-        fs.close()
+    if args.full:
+        for i in range(3):
+            if i == 2:
+                fresh_sets.pop(0).close()
+            fresh_sets.append(commet_amd.ReadSet.from_files(ctx, [(b1, o1)]))
+            ctx.synchronize()
+            t_c = time.perf_counter()
+            ctx.index_and_search(irs, [fresh_sets[-1]])
+            ctx.synchronize()
+            dt = time.perf_counter() - t_c
+            first_job_all.append(round(dt * 1e3, 3))
+            first_job_s = dt if first_job_s is None else min(first_job_s, dt)
+        for fs in fresh_sets:
+            fs.close()
 
-    # ---- untimed extras (rank 0): P_ref, per-kernel times, the random-gather ceiling ---------------------------
+    # ---- untimed extras (rank 0, --full): P_ref, per-kernel times, the random-gather ceiling ---------------------------
     probes, ktimes, gather_ceiling = None, None, None
-    if rank == 0:
+    if rank == 0 and args.full:
         if not args.no_probe_count and info["n_chunks"] <= 256:   # (the counting builds replay every chunk one by one: minutes at configs[4]'s 10 421 chunks)
             ctx.set_option("count_probes", 1)     # P_ref of the reference's control flow, detail only
             _, _, inf = ctx.index_and_search(irs, [qrs])
@@ -645,9 +680,9 @@ def main():
     qrs.close()
     ctx.close()
 
-    # ---- the same step on ragged sets (one GPU; nothing of it is part of `value`) ----------------------------------
+    # ---- the same step on ragged sets (one GPU, --full; nothing of it is part of `value`) ----------------------------------
     ragged_detail = None
-    if world == 1 and parse_ragged(args.ragged) and not args.ragged_only:
+    if args.full and world == 1 and parse_ragged(args.ragged) and not args.ragged_only:
         progress(ranks, f"ragged leg: 2 sets x {n} reads of {args.ragged} bp")
         try:
             ragged_detail = ragged_leg(args, device, {"reads_per_s": round(n * args.steps / elapsed, 1), "bases_per_s": round(float(o1[-1]) * args.steps / elapsed, 1),
@@ -778,9 +813,10 @@ def main():
                 "ms_per_step": round(ms_per_step, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
                 # what `value` is, and the figure for ONE pair met for the first time, beside it
                 "value_note": "steady state of the N x N use (a set is searched N-1 times): the search set's query list — derived from the set and (k, t) alone — "
-                              "is cached with the resident set; the index set's filters are rebuilt in every step.  first_job_reads_per_s = one job on a search "
-                              "set never scanned before (list build included, warm context)",
-                "first_job_reads_per_s": round(world * n / first_job_s, 1),
+                              "is cached with the resident set; the index set's filters are rebuilt in every step.  first_job_reads_per_s (--full) = one job on a "
+                              "search set never scanned before (list build included, warm context)",
+                "first_job_reads_per_s": round(world * n / first_job_s, 1) if first_job_s else None,
+                "full": args.full,
                 "dtype": "u32" if k <= 32 else "u64", "data": "synthetic",
                 "config": {"workload": workload,
                            "reads_per_set": n, "read_len": L, "k": k, "t": t, "jobs": world,
@@ -794,7 +830,8 @@ def main():
                            "reference_model_bytes_per_step": {"index": round(idx_bytes_step), "search": round(srch_bytes_step) if srch_bytes_step else None,
                                                               "note": "SURVEY 8d's sector model of the REFERENCE's accesses; not what this implementation moves"},
                            # a job on a search set that was never scanned (warm context): builds the set's query list as well
-                           "first_job_ms": round(first_job_s * 1e3, 3), "first_job_reads_per_s": round(n / first_job_s, 1),
+                           "first_job_ms": round(first_job_s * 1e3, 3) if first_job_s else None,
+                           "first_job_reads_per_s": round(n / first_job_s, 1) if first_job_s else None,
                            "first_job_ms_all": first_job_all,
                            "query_list_bytes": query_list_bytes,
                            "cold_context_first_job_ms": round(cold_context_first_job_s * 1e3, 3) if cold_context_first_job_s else None,
@@ -813,7 +850,7 @@ def main():
                 # (the same workload at every N — BASELINE configs[3] when the host holds it — so the per-N values are one curve)
                 out["matrix"] = {f: matrix_detail[f] for f in ("workload", "world", "reads_per_s_incl_load_and_filter", "reads_per_s", "total_s",
                                                                "jobs_s", "set_wait_s", "alloc_wait_ms", "fresh_device_bytes", "handover", "imbalance", "predicted_vs_actual_share", "size_note")}
-            if world == 1:
+            if world == 1 and args.full:
                 out["cpu_baseline"] = cpu_baseline(args, b0, b1, info) if not ragged_hl else None
                 if out["cpu_baseline"] is not None and not args.cpu_full:
                     # the whole job was run once on one core (--cpu-full, minutes): quoted from the committed record of that run
@@ -838,7 +875,7 @@ def main():
             print(json.dumps(out), flush=True)
 
     matrix_detail, matrix_c2, failed_here = None, None, False
-    if not args.no_matrix and args.matrix_sets >= 2:
+    if args.full and not args.no_matrix and args.matrix_sets >= 2:
         # The extra legs must never cost the headline: if they are not done after BENCH_MATRIX_LIMIT_S (default 900 s; configs[3] takes
         # ~60 s on one GPU, most of it writing the FASTA files) every rank gives up — rank 0 prints the line without them — ends its
         # child processes, removes what it wrote and leaves NON-ZERO: a GPU process that had to be abandoned is not a success.

@@ -10,9 +10,10 @@ import sys
 
 import pytest
 
+import refrun
 import util
 from scenarios import GoldenScenario, Scenario, compare_runs, run_oracle, run_tool
-from conftest import ROOT, ref_tool
+from conftest import ROOT
 
 pytestmark = pytest.mark.gpu
 
@@ -38,6 +39,14 @@ def test_cli_reproduces_reference_golden(tmp_path, name):
     scn.check_against_golden(out, log)
 
 
+def _reference(scn, out, log, extra_args=()):
+    """the reference's index_and_search on the scenario: live where oracle/_ref is built, else its stored run (tests/refrun.py;
+    paths relative to the scenario directory, as the stored runs hold the arguments)"""
+    rel = lambda p: os.path.relpath(p, scn.dir)          # noqa: E731
+    return refrun.run("index_and_search", ["-i", scn.index_cfg, "-s", scn.search_cfg, "-o", rel(out), "-l", rel(log),
+                                           "-k", str(scn.k), "-t", str(scn.t)] + list(extra_args), scn.dir, watch=[out, log])
+
+
 def _strip_times(text):
     return re.sub(r"(Index  time|Search time|Total  time): .* s", r"\1: T s", text)
 
@@ -48,25 +57,24 @@ def test_cli_matches_oracle_and_reference(tmp_path, seed):
     scn = Scenario(str(tmp_path / "scn"), seed, **({"formats": ("fa", "fq", "fa.gz", "fq.gz"), "crlf": False} if mixed else {}))
     out_g, log_g = str(tmp_path / "out_gpu"), str(tmp_path / "log_gpu")
     out_o, log_o = str(tmp_path / "out_orc"), str(tmp_path / "log_orc")
+    # the compiled reference, or its stored run on this scenario (tests/refrun.py): stdout and whole logs must match too
+    out_r, log_r = str(tmp_path / "out_ref"), str(tmp_path / "log_ref")
+    q = _reference(scn, out_r, log_r)
+    assert q.returncode == 0
     p = run_tool(TOOL, scn, out_g, log_g)
     assert p.returncode == 0, p.stderr.decode()[-800:]
     rc, *_ = run_oracle(scn, out_o, log_o)
     assert rc == 0
     compare_runs(out_o, log_o, out_g, log_g, scn)
-    ref = ref_tool("index_and_search")
-    if ref:   # the compiled reference, when it travelled with the snapshot: stdout must match too
-        out_r, log_r = str(tmp_path / "out_ref"), str(tmp_path / "log_ref")
-        q = run_tool(ref, scn, out_r, log_r)
-        assert q.returncode == 0
-        compare_runs(out_r, log_r, out_g, log_g, scn)
-        assert _strip_times(q.stdout.decode()) == _strip_times(p.stdout.decode())
-        for f in os.listdir(log_r):
-            a = _strip_times(open(os.path.join(log_r, f)).read())
-            b = _strip_times(open(os.path.join(log_g, f)).read())
-            assert a == b
-        for f in os.listdir(out_r):
-            if f.endswith(".bv"):
-                assert oct(os.stat(os.path.join(out_g, f)).st_mode & 0o777) == "0o600"
+    compare_runs(out_r, log_r, out_g, log_g, scn)
+    assert _strip_times(q.stdout.decode()) == _strip_times(p.stdout.decode())
+    for f in os.listdir(log_r):
+        a = _strip_times(open(os.path.join(log_r, f)).read())
+        b = _strip_times(open(os.path.join(log_g, f)).read())
+        assert a == b
+    for f in os.listdir(out_r):
+        if f.endswith(".bv"):
+            assert oct(os.stat(os.path.join(out_g, f)).st_mode & 0o777) == "0o600"
 
 
 def _full_mode_outputs(out_dir, log_dir):
@@ -93,12 +101,9 @@ def test_cli_full_mode_reproduces_reference_golden(tmp_path, name):
 
 @pytest.mark.parametrize("seed", range(2100, 2115))
 def test_cli_full_mode_matches_reference_live(tmp_path, seed):
-    ref = ref_tool("index_and_search")
-    if not ref:
-        pytest.skip("oracle/_ref/index_and_search did not travel with the snapshot")
     scn = Scenario(str(tmp_path / "scn"), seed)
+    q = _reference(scn, str(tmp_path / "or"), str(tmp_path / "lr"), extra_args=["-f"])
     p = run_tool(TOOL, scn, str(tmp_path / "og"), str(tmp_path / "lg"), extra_args=["-f"])
-    q = run_tool(ref, scn, str(tmp_path / "or"), str(tmp_path / "lr"), extra_args=["-f"])
     assert p.returncode == q.returncode == 0, p.stderr.decode()[-500:]
     assert _full_mode_outputs(str(tmp_path / "og"), str(tmp_path / "lg")) == _full_mode_outputs(str(tmp_path / "or"), str(tmp_path / "lr"))
     assert _strip_times(q.stdout.decode()) == _strip_times(p.stdout.decode())

@@ -1,5 +1,6 @@
 """bvop, filter_reads (host-only C++ tools Commet.py needs) and extract_reads (8f-4) against
-the compiled reference tools, byte for byte: stdout, exit code and the files written."""
+the compiled reference tools, byte for byte: stdout, exit code and the files written (tests/refrun.py: live where
+oracle/_ref is built, else the stored runs of tests/golden/ref_runs)."""
 import os
 import re
 import subprocess
@@ -7,8 +8,9 @@ import subprocess
 import numpy as np
 import pytest
 
+import refrun
 import util
-from conftest import ROOT, ref_tool
+from conftest import ROOT
 
 # COMMET_BIN_DIR: prebuilt (e.g. sanitizer-instrumented, tests/test_sanitizers.py) tools to test instead
 BIN = os.environ.get("COMMET_BIN_DIR") or os.path.join(ROOT, "commet_amd", "bin")
@@ -30,11 +32,8 @@ def _run(tool, args, cwd):
 
 
 def _both(name, args, cwd_ours, cwd_ref):
-    ref = ref_tool(name)
-    if not ref:
-        pytest.skip(f"oracle/_ref/{name} not built")
     a = _run(os.path.join(BIN, name), args, cwd_ours)
-    b = _run(ref, args, cwd_ref)
+    b = refrun.run(name, args, cwd_ref)          # the reference's tool, or its stored run on the same inputs
     return a, b
 
 

@@ -8,7 +8,7 @@ SETS=(); while [ $# -gt 0 ] && [ "$1" != "--" ]; do SETS+=("$1"); shift; done
 [ "$1" = "--" ] && shift
 for f in "${SETS[@]}"; do
   hipcc --offload-arch=gfx950 -O3 -std=c++17 -shared -fPIC $f -o commet_amd/libcommet_hip.so commet_amd/csrc/capi.hip -lz
-  python3 bench.py --no-matrix --cpu-sample 0 --no-probe-count --steps 10 --kt-steps 3 "$@" > /tmp/ab.json 2> /tmp/ab.err || { tail -5 /tmp/ab.err; exit 1; }
+  python3 bench.py --full --no-matrix --cpu-sample 0 --no-probe-count --steps 10 --kt-steps 3 "$@" > /tmp/ab.json 2> /tmp/ab.err || { tail -5 /tmp/ab.err; exit 1; }
   python3 -c "
 import json, sys; b = json.load(open('/tmp/ab.json'))
 print('[' + sys.argv[1] + ']', 'ms/step', b['ms_per_step'], 'reads/s', b['value'], 'shared', b['detail']['shared'], 'idx', b['detail']['index_kernel_ms'], 'srch', b['detail']['search_kernel_ms'], {k: round(v['ms_per_step'], 2) for k, v in b['roofline']['kernels'].items() if v['ms_per_step'] > 0.05})" "$f"

@@ -11,7 +11,7 @@ VALS=(); while [ $# -gt 0 ] && [ "$1" != "--" ]; do VALS+=("$1"); shift; done
 [ "$1" = "--" ] && shift
 for v in "${VALS[@]}"; do
   hipcc --offload-arch=gfx950 -O3 -std=c++17 -shared -fPIC -D$M=$v -o commet_amd/libcommet_hip.so commet_amd/csrc/capi.hip -lz
-  python3 bench.py --no-matrix --cpu-sample 0 --no-probe-count --steps 3 --kt-steps 2 "$@" > /tmp/ab.json 2> /tmp/ab.err || { tail -5 /tmp/ab.err; exit 1; }
+  python3 bench.py --full --no-matrix --cpu-sample 0 --no-probe-count --steps 3 --kt-steps 2 "$@" > /tmp/ab.json 2> /tmp/ab.err || { tail -5 /tmp/ab.err; exit 1; }
   python3 -c "
 import json, sys; b = json.load(open('/tmp/ab.json'))
 print(sys.argv[1], '=', sys.argv[2], 'ms/step', b['ms_per_step'], 'shared', b['detail']['shared'], {k: round(v['ms_per_step'], 2) for k, v in b['roofline']['kernels'].items() if v['ms_per_step'] > 0.05})" $M $v

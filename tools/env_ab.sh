@@ -11,7 +11,7 @@ V=$1; shift
 VALS=(); while [ $# -gt 0 ] && [ "$1" != "--" ]; do VALS+=("$1"); shift; done
 [ "$1" = "--" ] && shift
 for v in "${VALS[@]}"; do
-  env $V=$v python3 bench.py --no-matrix --cpu-sample 0 --no-probe-count --steps 5 --kt-steps 2 "$@" > /tmp/ab.json 2> /tmp/ab.err || { tail -5 /tmp/ab.err; exit 1; }
+  env $V=$v python3 bench.py --full --no-matrix --cpu-sample 0 --no-probe-count --steps 5 --kt-steps 2 "$@" > /tmp/ab.json 2> /tmp/ab.err || { tail -5 /tmp/ab.err; exit 1; }
   python3 -c "
 import json, sys; b = json.load(open('/tmp/ab.json'))
 print(sys.argv[1], '=', sys.argv[2], 'ms/step', b['ms_per_step'], 'reads/s', b['value'], {k: round(v['ms_per_step'], 2) for k, v in b['roofline']['kernels'].items() if v['ms_per_step'] > 0.05})" $V $v

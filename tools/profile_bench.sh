@@ -8,10 +8,10 @@ shift || true
 O=$R/gpurun_out/$N
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-python3 $R/bench.py --no-matrix "$@" > $O/bench.json 2> $O/bench.err
+python3 $R/bench.py --full --no-matrix "$@" > $O/bench.json 2> $O/bench.err
 # one index lane here: with two, kernels of both lanes run at once and their durations are not additive
 # (the counter passes time ONE workload: no ragged leg beside it — pass --ragged-only to profile the ragged step itself)
-B="--cpu-sample 0 --no-probe-count --no-kernel-times --no-matrix --ragged none"
+B="--full --cpu-sample 0 --no-probe-count --no-kernel-times --no-matrix --ragged none"
 COMMET_INDEX_LANES=1 rocprofv3 --kernel-trace --stats -d $O/kt -o p --output-format csv -- python3 $R/bench.py --steps 5 --warmup 2 $B "$@" > $O/kt.log 2>&1
 COMMET_INDEX_LANES=1 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $O/pf -o p --output-format csv -- python3 $R/bench.py --steps 1 --warmup 0 $B "$@" > $O/pf.log 2>&1
 COMMET_INDEX_LANES=1 rocprofv3 --pmc WRITE_SIZE --kernel-trace -d $O/pw -o p --output-format csv -- python3 $R/bench.py --steps 1 --warmup 0 $B "$@" > $O/pw.log 2>&1
@@ -23,5 +23,5 @@ cp $(find $O/ps -name "*counter_collection.csv" | head -1) $O/pmc_sq.csv 2>/dev/
 rm -rf $O/kt $O/pf $O/pw $O/ps
 cd $R && python3 tools/pmc_summary.py $O
 # the bench line again, now priced with the counters just collected (the first one only named the workload)
-cd /tmp && python3 $R/bench.py --no-matrix --traffic $O/traffic.json "$@" > $O/bench.json 2> $O/bench.err
+cd /tmp && python3 $R/bench.py --full --no-matrix --traffic $O/traffic.json "$@" > $O/bench.json 2> $O/bench.err
 cat $O/bench.json
