@@ -38,11 +38,6 @@ commet_ctx *commet_create(int device, int kmer_size, int min_hits)
     if (const char *e = getenv("COMMET_TILED")) c->tiled_mode = std::max(0, std::min(2, atoi(e)));
     if (const char *e = getenv("COMMET_MULTI_JOB")) c->multi_job = atoi(e) == 1 ? 1 : 0;   // A/B runs: 1 = commet_index_many_and_search job by job
     if (const char *e = getenv("COMMET_SPARSE_SEARCH")) c->sparse_search = std::max(0, std::min(2, atoi(e)));   // A/B runs
-    if (const char *e = getenv("COMMET_TQ_SBITS")) c->tq_sbits = atoi(e);
-    if (const char *e = getenv("COMMET_TQ_WPX")) c->tq_wpx = (unsigned) std::max(1, atoi(e));
-    if (const char *e = getenv("COMMET_TQ_PARTS")) c->tq_parts = std::max(1, std::min(16, atoi(e)));
-    if (const char *e = getenv("COMMET_LANE_STAGGER")) c->lane_stagger = atoi(e) != 0;
-    c->stage_reads = getenv("COMMET_NO_STAGE_READS") == nullptr;
     c->job_verbose = getenv("COMMET_JOB_VERBOSE") != nullptr;
     c->ingest_verbose = getenv("COMMET_INGEST_VERBOSE") != nullptr;
     {   // query lists: half the device at most (64 GiB on small devices).  One list: 4 GiB (sets of up to ~15 M reads).  Larger lists

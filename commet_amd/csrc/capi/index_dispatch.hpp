@@ -33,12 +33,10 @@ int launch_index_atomic(commet_ctx *c, const commet_readset *rs, uint64_t first,
     const uint64_t blocks = (count + 255) / 256;
     if (blocks >= (1ull << 24)) return fail("index launch too large (>= 2^32 reads in one chunk)");
     KScope ks(c, "index_kernel", c->stream);
-    if (c->k <= 32)
-        COMMET_LAUNCH(index_kernel<uint32_t>, dim3((unsigned) blocks), dim3(256), 0, c->stream, rs->view(), c->view(),
-                           c->k, first, count, d_sel, d_fed);
-    else
-        COMMET_LAUNCH(index_kernel<uint64_t>, dim3((unsigned) blocks), dim3(256), 0, c->stream, rs->view(), c->view(),
-                           c->k, first, count, d_sel, d_fed);
+    with_key(c->k, [&](auto key) {
+        COMMET_LAUNCH(index_kernel<decltype(key)>, dim3((unsigned) blocks), dim3(256), 0, c->stream, rs->view(), c->view(), c->k, first,
+                      count, d_sel, d_fed);
+    });
     HIP_OK(hipGetLastError());
     return 0;
 }
@@ -69,13 +67,7 @@ int launch_index_partitioned(commet_ctx *c, const commet_readset *rs, uint64_t f
     }
     uint32_t *const slot = c->slot_ptr(c->cur_slot);
     PartGeom g = make_geom(c->k);
-    g.xcd_swizzle = c->s2_swizzle;
     g.packed = c->part_packed;
-    if (c->part_b1 > 0 && c->part_b1 < g.nb_bits && c->part_b1 <= 8 && g.nb_bits - c->part_b1 <= 9) {
-        g.b1 = c->part_b1;
-        g.b2 = g.nb_bits - g.b1;
-        g.nb1 = 1u << g.b1;
-    }
     if (g.b2 == 0) g.packed = 0;   // single level: scatter1 writes the final buckets itself, as plain keys
     const uint64_t total = 4 * kmers;
     if (ws.nb != g.nb) {
@@ -142,11 +134,10 @@ int launch_index_partitioned(commet_ctx *c, const commet_readset *rs, uint64_t f
         }
         // the list of an UNSELECTED read range is a function of the set alone: a workspace that still holds it (the same chunk of the same
         // set indexed again: the reference set of a rank's J1 calls, a benchmark's steady state) does not write it again
+        // (the key is set only once the launches are queued: a failed write leaves the buffer nobody's)
         const bool held = list && !d_sel && ws.items_set == rs->uid && ws.items_first == first && ws.items_count == count && ws.items_nblk == (uint32_t) nblk;
-        if (held) {
-            d_items = ws.items, d_nitems = ws.itemblk + nblk;
-        } else if (list) {
-            ws.items_set = d_sel ? 0 : rs->uid, ws.items_first = first, ws.items_count = count, ws.items_nblk = (uint32_t) nblk;
+        if (list && !held) {
+            ws.items_set = 0;
             KScope ks(c, "part_items_kernels", stream);
             COMMET_LAUNCH(part_items_kernel<false>, dim3((unsigned) nblk), dim3(ITEMS_BLOCK), 0, stream, rs->view(), rs->d_kcnt, d_sel, first, count, c->k,
                           ws.itemblk, ws.items);
@@ -154,16 +145,12 @@ int launch_index_partitioned(commet_ctx *c, const commet_readset *rs, uint64_t f
             COMMET_LAUNCH(part_items_kernel<true>, dim3((unsigned) nblk), dim3(ITEMS_BLOCK), 0, stream, rs->view(), rs->d_kcnt, d_sel, first, count, c->k,
                           ws.itemblk, ws.items);
             HIP_OK(hipGetLastError());
-            d_items = ws.items, d_nitems = ws.itemblk + nblk;
+            ws.items_set = d_sel ? 0 : rs->uid, ws.items_first = first, ws.items_count = count, ws.items_nblk = (uint32_t) nblk;
         }
+        if (list) d_items = ws.items, d_nitems = ws.itemblk + nblk;
     }
     const int mode = uni ? 1 : list ? 2 : 0;
-    // TIMING BOUND ONLY (COMMET_HIST_REUSE=1, never set by the product): a workspace that counted this very chunk last time keeps its
-    // histogram — what the index costs without the counting pass, measured on a benchmark's steady state
-    static const bool hist_reuse_on = getenv("COMMET_HIST_REUSE") && atoi(getenv("COMMET_HIST_REUSE")) != 0;
-    const bool hist_held = hist_reuse_on && !d_sel && !d_ids && ws.hist_set == rs->uid && ws.hist_first == first && ws.hist_count == count;
-    ws.hist_set = (d_sel || d_ids) ? 0 : rs->uid, ws.hist_first = first, ws.hist_count = count;
-    if (!hist_held) HIP_OK(hipMemsetAsync(ws.hist, 0, (g.nb + 1) * sizeof(uint32_t), stream));
+    HIP_OK(hipMemsetAsync(ws.hist, 0, (g.nb + 1) * sizeof(uint32_t), stream));
     // scatter1's grid fixes how the read range is cut; hist counts with the same cut, two ranges per workgroup
     const uint32_t grid1 = (uint32_t) std::min<uint64_t>(S1_GRID_MAX, (count + 63) / 64);
     {
@@ -172,11 +159,10 @@ int launch_index_partitioned(commet_ctx *c, const commet_readset *rs, uint64_t f
         // 32-bit keys (k <= 32): at most 2^15 buckets, the LDS histogram always covers them all (FULL); 64-bit keys: never.
         // Only those six instantiations exist (tests/test_gpu_zz_dispatch_coverage.py checks that each is reached).
         if (full == wide) return fail("internal error: histogram geometry (k = %d, %u buckets)", c->k, g.nb);
-        const void *fn = wide ? (mode == 1 ? (const void *) part_hist_kernel<uint64_t, 1, false> : mode == 2 ? (const void *) part_hist_kernel<uint64_t, 2, false>
-                                                                                                             : (const void *) part_hist_kernel<uint64_t, 0, false>)
-                              : (mode == 1 ? (const void *) part_hist_kernel<uint32_t, 1, true> : mode == 2 ? (const void *) part_hist_kernel<uint32_t, 2, true>
-                                                                                                            : (const void *) part_hist_kernel<uint32_t, 0, true>);
-        for (uint32_t b_lo = 0; b_lo < g.nb && !hist_held; b_lo += HIST_MAX_BUCKETS) {
+        const void *fn = with_key(c->k, [&](auto key) {
+            return with_value<0, 1, 2>(mode, [&](auto m) { return (const void *) part_hist_kernel<decltype(key), m, sizeof key == 4>; });
+        });
+        for (uint32_t b_lo = 0; b_lo < g.nb; b_lo += HIST_MAX_BUCKETS) {
             const uint32_t n_b = std::min<uint32_t>(HIST_MAX_BUCKETS, g.nb - b_lo);
             const size_t lds = ((size_t) n_b + 2 * HIST_NT + 24) * 4 + (size_t) HIST_NT * 8;
             HIP_OK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
@@ -208,10 +194,9 @@ int launch_index_partitioned(commet_ctx *c, const commet_readset *rs, uint64_t f
     // scatter 1 (straight into the final buckets when there is a single level)
     uint32_t *level1_out = g.b2 ? ws.bufA : ws.bufB;
     {
-        const void *fn = wide ? (mode == 1 ? (const void *) part_scatter1_kernel<uint64_t, 1> : mode == 2 ? (const void *) part_scatter1_kernel<uint64_t, 2>
-                                                                                                          : (const void *) part_scatter1_kernel<uint64_t, 0>)
-                              : (mode == 1 ? (const void *) part_scatter1_kernel<uint32_t, 1> : mode == 2 ? (const void *) part_scatter1_kernel<uint32_t, 2>
-                                                                                                          : (const void *) part_scatter1_kernel<uint32_t, 0>);
+        const void *fn = with_key(c->k, [&](auto key) {
+            return with_value<0, 1, 2>(mode, [&](auto m) { return (const void *) part_scatter1_kernel<decltype(key), m>; });
+        });
         ReadsView rv = rs->view();
         const uint32_t *kc = rs->d_kcnt;
         const unsigned long long *boff = ws.blockoff;
@@ -224,11 +209,10 @@ int launch_index_partitioned(commet_ctx *c, const commet_readset *rs, uint64_t f
     // scatter1 (VALU, LDS atomics, a write pattern) run beside this chunk's scatter2 and build (HBM streams) instead of beside
     // the same phases of this chunk.  Four boxes, configs[1], per step: -0.36, -0.25, 0.0 and +0.04 ms (the slower the box's
     // draw, the more); a 2 x 50 M-read pair 169.4 -> 168.1 ms.  Staggering behind hist instead: +0.5 ms.
-    if (c->lane_stagger && lane == 0 && c->ev_stagger) {
+    if (lane == 0) {
         HIP_OK(hipEventRecord(c->ev_stagger, stream));
         c->stagger_armed = true;
     }
-    if (COMMET_ABLATE & 31) return 0;   // ablation builds only: scatter1 left garbage in bufA, nothing downstream may consume it
     if (g.b2) {
         const uint64_t grid = (total + S2_KEYS - 1) / S2_KEYS;
         if (grid >= (1ull << 24)) return fail("scatter launch too large");
@@ -243,7 +227,6 @@ int launch_index_partitioned(commet_ctx *c, const commet_readset *rs, uint64_t f
         }
         HIP_OK(hipGetLastError());
     }
-    if (COMMET_ABLATE) return 0;   // ablation builds only: bufB holds garbage
     {
         const uint64_t grid = (uint64_t) g.nb + total / BUILD_CAP + 1;
         if (grid >= (1ull << 24)) return fail("build launch too large");

@@ -55,11 +55,6 @@ int commet_set_option(commet_ctx *c, const char *name, int64_t value)
         c->sparse_search = (int) value;
         return 0;
     }
-    if (!strcmp(name, "tq_parts")) {          // tiled search: parts of the set whose replay runs beside the next part's probe (1 = off)
-        if (value < 1 || value > 16) return fail("tq_parts must be 1..16");
-        c->tq_parts = (int) value;
-        return 0;
-    }
     if (!strcmp(name, "slice_mode")) {        // 0 auto (8 chunks or more, 12 <= k <= 24), 1 never, 2 whenever k allows it
         if (value < 0 || value > 2) return fail("slice_mode must be 0, 1 or 2");
         c->slice_mode = (int) value;
@@ -88,10 +83,6 @@ int commet_set_option(commet_ctx *c, const char *name, int64_t value)
     if (!strcmp(name, "index_lanes")) {       // 1 = the chunks of a group are built one after the other
         if (value < 1 || value > 2) return fail("index_lanes must be 1 or 2");
         c->index_lanes = (int) value;
-        return 0;
-    }
-    if (!strcmp(name, "lane_stagger")) {      // 1 = the second index lane's chunk starts behind the first lane's scatter1 (default), 0 = both at once
-        c->lane_stagger = value != 0;
         return 0;
     }
     if (!strcmp(name, "drop_workspaces")) {   // frees the scatter workspaces; the next bucketed index build allocates them again
@@ -126,14 +117,6 @@ int commet_set_option(commet_ctx *c, const char *name, int64_t value)
     }
     if (!strcmp(name, "part_list")) {
         c->part_list = value != 0;
-        return 0;
-    }
-    if (!strcmp(name, "part_b1")) {
-        c->part_b1 = (int) value;
-        return 0;
-    }
-    if (!strcmp(name, "s2_swizzle")) {
-        c->s2_swizzle = (int) std::max<int64_t>(0, std::min<int64_t>(value, 1 << 20));
         return 0;
     }
     if (!strcmp(name, "part_min_kmers")) {    // auto mode: chunks with fewer k-mers use the atomic kernel

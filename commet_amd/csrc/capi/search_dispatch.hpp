@@ -22,23 +22,13 @@ int launch_search(commet_ctx *c, const commet_readset *rs, const uint64_t *d_sel
     const uint64_t blocks = ((al.ids ? n_launch : rs->n_reads) + 255) / 256;
     if (blocks >= (1ull << 24)) return fail("search launch too large (>= 2^32 reads in one set)");
     const dim3 g((unsigned) blocks), b(256);
-    const bool cnt = d_probes != nullptr;
     KScope ks(c, "search_kernel", c->stream);
-    if (c->k <= 32) {
-        if (cnt)
-            COMMET_LAUNCH((search_kernel<uint32_t, true>), g, b, 0, c->stream, rs->view(), c->view(), c->k, t_eff(c, rs), d_sel,
-                               d_tags, d_found, d_counters, d_probes, al);
-        else
-            COMMET_LAUNCH((search_kernel<uint32_t, false>), g, b, 0, c->stream, rs->view(), c->view(), c->k, t_eff(c, rs), d_sel,
-                               d_tags, d_found, d_counters, d_probes, al);
-    } else {
-        if (cnt)
-            COMMET_LAUNCH((search_kernel<uint64_t, true>), g, b, 0, c->stream, rs->view(), c->view(), c->k, t_eff(c, rs), d_sel,
-                               d_tags, d_found, d_counters, d_probes, al);
-        else
-            COMMET_LAUNCH((search_kernel<uint64_t, false>), g, b, 0, c->stream, rs->view(), c->view(), c->k, t_eff(c, rs), d_sel,
-                               d_tags, d_found, d_counters, d_probes, al);
-    }
+    with_key(c->k, [&](auto key) {
+        with_value<false, true>(d_probes != nullptr, [&](auto count) {
+            COMMET_LAUNCH((search_kernel<decltype(key), count>), g, b, 0, c->stream, rs->view(), c->view(), c->k, t_eff(c, rs), d_sel, d_tags,
+                          d_found, d_counters, d_probes, al);
+        });
+    });
     HIP_OK(hipGetLastError());
     return 0;
 }
@@ -78,15 +68,10 @@ int launch_interleave(commet_ctx *c, int g, int gs)
 {
     const uint64_t blocks = std::min<uint64_t>((c->plane_words + 255) / 256, 1u << 16);
     KScope ks(c, "interleave_a_kernel", c->stream);
-    if (gs == 2)
-        COMMET_LAUNCH(interleave_a_kernel<2>, dim3((unsigned) blocks), dim3(256), 0, c->stream, c->filter, 4 * c->plane_words,
-                           c->plane_words, g, c->il_a);
-    else if (gs == 4)
-        COMMET_LAUNCH(interleave_a_kernel<4>, dim3((unsigned) blocks), dim3(256), 0, c->stream, c->filter, 4 * c->plane_words,
-                           c->plane_words, g, c->il_a);
-    else
-        COMMET_LAUNCH(interleave_a_kernel<8>, dim3((unsigned) blocks), dim3(256), 0, c->stream, c->filter, 4 * c->plane_words,
-                           c->plane_words, g, c->il_a);
+    with_value<2, 4, 8>(gs, [&](auto GS) {
+        COMMET_LAUNCH(interleave_a_kernel<GS>, dim3((unsigned) blocks), dim3(256), 0, c->stream, c->filter, 4 * c->plane_words, c->plane_words,
+                      g, c->il_a);
+    });
     HIP_OK(hipGetLastError());
     return 0;
 }
@@ -100,22 +85,18 @@ int launch_search_group_t(commet_ctx *c, const commet_readset *rs, const FilterG
     size_t lds = (size_t) fg.g * 2 * nw_max * 256 * sizeof(uint32_t);
     // the lanes' reads staged in LDS too (3 * nw_max words each) when that still fits 64 KiB
     uint32_t rw_nw = 0;
-    if (!d_probes && nw_max <= 8 && lds + (size_t) 3 * nw_max * 256 * sizeof(uint32_t) <= (64u << 10) && c->stage_reads) {
+    if (!d_probes && nw_max <= 8 && lds + (size_t) 3 * nw_max * 256 * sizeof(uint32_t) <= (64u << 10)) {
         rw_nw = nw_max;
         lds += (size_t) 3 * nw_max * 256 * sizeof(uint32_t);
     }
     KScope ks(c, "search_group_kernel", c->stream);
-    if (d_probes) {
-        HIP_OK(hipFuncSetAttribute((const void *) search_group_kernel<W, GS, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
-        COMMET_LAUNCH((search_group_kernel<W, GS, true>), g, b, lds, c->stream, rs->view(), fg, c->k, t_eff(c, rs), nw_max, d_sel, d_tags,
-                           d_counters, cstride, d_probes, rw_nw, al);
-    } else {
-        HIP_OK(hipFuncSetAttribute((const void *) search_group_kernel<W, GS, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
-        COMMET_LAUNCH((search_group_kernel<W, GS, false>), g, b, lds, c->stream, rs->view(), fg, c->k, t_eff(c, rs), nw_max, d_sel, d_tags,
-                           d_counters, cstride, d_probes, rw_nw, al);
-    }
-    HIP_OK(hipGetLastError());
-    return 0;
+    return with_value<false, true>(d_probes != nullptr, [&](auto count) {
+        HIP_OK(hipFuncSetAttribute((const void *) search_group_kernel<W, GS, count>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
+        COMMET_LAUNCH((search_group_kernel<W, GS, count>), g, b, lds, c->stream, rs->view(), fg, c->k, t_eff(c, rs), nw_max, d_sel, d_tags,
+                      d_counters, cstride, d_probes, rw_nw, al);
+        HIP_OK(hipGetLastError());
+        return 0;
+    });
 }
 
 // mask words (32 first-hit windows each) a read of the set needs per strand and filter in the register-mask kernels
@@ -125,6 +106,11 @@ inline int mask_words(const commet_ctx *c, const commet_readset *rs)
 {
     const int64_t fhw = (int64_t) rs->max_len - (int64_t) t_eff(c, rs) * c->k + 1;
     return fhw <= 64 ? 2 : fhw <= 96 ? 3 : fhw <= 128 ? 4 : fhw <= 192 ? 6 : 8;
+}
+template <typename F>
+decltype(auto) with_mask_words(int mw, F &&f)
+{
+    return with_value<2, 3, 4, 6, 8>(mw, f);
 }
 
 // one pass of rs over the `g` chunk filters in slots 0..g-1 (A planes already interleaved with stride gs)
@@ -147,21 +133,12 @@ int launch_search_group(commet_ctx *c, const commet_readset *rs, int g, int gs, 
         auto launch = [&](int mw, ActiveList l, uint64_t n_l) {
             KScope ks(c, "search_group8_kernel", c->stream);
             const dim3 grid((unsigned) (((l.ids ? n_l : rs->n_reads) + 255) / 256)), block(256);
-#define COMMET_G8(W, MW) COMMET_LAUNCH((search_group8_kernel<W, MW>), grid, block, 0, c->stream, rs->view(), fg, c->k, t_eff(c, rs), d_sel, d_tags, d_counters, cstride, l, job_mask, job_tag_words)
-            if (c->k <= 32) {
-                if (mw == 2) COMMET_G8(uint32_t, 2);
-                else if (mw == 3) COMMET_G8(uint32_t, 3);
-                else if (mw == 4) COMMET_G8(uint32_t, 4);
-                else if (mw == 6) COMMET_G8(uint32_t, 6);
-                else COMMET_G8(uint32_t, 8);
-            } else {
-                if (mw == 2) COMMET_G8(uint64_t, 2);
-                else if (mw == 3) COMMET_G8(uint64_t, 3);
-                else if (mw == 4) COMMET_G8(uint64_t, 4);
-                else if (mw == 6) COMMET_G8(uint64_t, 6);
-                else COMMET_G8(uint64_t, 8);
-            }
-#undef COMMET_G8
+            with_key(c->k, [&](auto key) {
+                with_mask_words(mw, [&](auto MW) {
+                    COMMET_LAUNCH((search_group8_kernel<decltype(key), MW>), grid, block, 0, c->stream, rs->view(), fg, c->k, t_eff(c, rs), d_sel,
+                                  d_tags, d_counters, cstride, l, job_mask, job_tag_words);
+                });
+            });
         };
         if (al.ids && al.ids == rs->d_len_order && rs->n_len_seg > 1 && !c->mask_split) {
             // the set's reads in order of their window counts: every segment of the list with the narrowest masks its reads fit
@@ -178,12 +155,11 @@ int launch_search_group(commet_ctx *c, const commet_readset *rs, int g, int gs, 
         return 0;
     }
     const uint32_t nw_max = (rs->max_len + 31) / 32;
-    if (c->k <= 32) {
-        if (gs == 2) return launch_search_group_t<uint32_t, 2>(c, rs, fg, nw_max, d_sel, d_tags, d_counters, cstride, d_probes, al, n_launch);
-        return launch_search_group_t<uint32_t, 4>(c, rs, fg, nw_max, d_sel, d_tags, d_counters, cstride, d_probes, al, n_launch);
-    }
-    if (gs == 2) return launch_search_group_t<uint64_t, 2>(c, rs, fg, nw_max, d_sel, d_tags, d_counters, cstride, d_probes, al, n_launch);
-    return launch_search_group_t<uint64_t, 4>(c, rs, fg, nw_max, d_sel, d_tags, d_counters, cstride, d_probes, al, n_launch);
+    return with_key(c->k, [&](auto key) {
+        return with_value<2, 4>(gs, [&](auto GS) {
+            return launch_search_group_t<decltype(key), GS>(c, rs, fg, nw_max, d_sel, d_tags, d_counters, cstride, d_probes, al, n_launch);
+        });
+    });
 }
 
 bool group_searchable(const commet_ctx *c, const commet_readset *rs, int g)
@@ -319,7 +295,7 @@ bool ordered_pass(commet_ctx *c, const commet_readset *rs, const uint64_t *d_sel
 }
 
 // ---- tiled search (tile_search.hpp) ----------------------------------------------------------------------------
-constexpr int TQ_SBITS = 24;          // slice = 2^24 bits of plane A's address space: 2 MiB per chunk filter, 4 MiB for a group of two
+constexpr int TQ_SLICE_BITS = 24;     // slice = 2^24 bits of plane A's address space: 2 MiB per chunk filter, 4 MiB for a group of two
                                       // (measured on configs[1]: 22 / 23 / 24 -> probe 2.43 / 2.56 / 2.35 ms, gpurun_out/r02_tq_ab2.log)
 
 constexpr int TQ_MAX_K = 34;          // 64-bit keys from k = 33 (the reference's default k, index_and_search.cpp:71): 2^(k - 24) <= 1024 slices
@@ -327,7 +303,7 @@ constexpr int TQ_MAX_K = 34;          // 64-bit keys from k = 33 (the reference'
 bool tiled_ok(const commet_ctx *c, const commet_readset *rs, int g)
 {
     if (c->tiled_mode == 1 || c->count_probes || rs->ql.failed) return false;
-    if (c->k <= TQ_SBITS || c->k > TQ_MAX_K || g < 1 || g > 2) return false;
+    if (c->k <= TQ_SLICE_BITS || c->k > TQ_MAX_K || g < 1 || g > 2) return false;
     const int64_t first_hit_windows = (int64_t) rs->max_len - (int64_t) t_eff(c, rs) * c->k + 1;
     if (first_hit_windows < 1 || first_hit_windows > TQ_MAX_WIN) return false;
     if (rs->max_len >= TQ_MAX_LEN) return false;        // (the replay keeps a piece's read extents in 16 + 16 bits; such reads pass the line above only with t in the hundreds)
@@ -357,8 +333,7 @@ int build_query_list(commet_ctx *c, const commet_readset *rs)
         ql.last_use = ++c->ql_clock;
         return 0;
     }
-    ql.sbits = TQ_SBITS;
-    if (c->tq_sbits) ql.sbits = std::max(c->k - 10, std::min(c->k - 1, c->tq_sbits));   // A/B runs
+    ql.sbits = TQ_SLICE_BITS;
     ql.n_slices = 1u << (c->k - ql.sbits);
     ql.n_pieces = (uint32_t) ((rs->n_reads + TQ_PIECE - 1) / TQ_PIECE);
     const uint64_t entries = (uint64_t) ql.n_slices * ql.n_pieces;
@@ -392,12 +367,10 @@ int build_query_list(commet_ctx *c, const commet_readset *rs)
         const size_t lds = (size_t) ql.n_slices * 4;
         {
             KScope ks(c, "tq_count_kernel", ls);
-            if (c->k <= 32)
-                COMMET_LAUNCH(tq_count_kernel<uint32_t>, dim3(ql.n_pieces), dim3(256), lds, ls, rs->view(), c->k, t, ql.sbits, ql.n_slices,
+            with_key(c->k, [&](auto key) {
+                COMMET_LAUNCH(tq_count_kernel<decltype(key)>, dim3(ql.n_pieces), dim3(256), lds, ls, rs->view(), c->k, t, ql.sbits, ql.n_slices,
                               ql.n_pieces, ql.d_tile_off);
-            else
-                COMMET_LAUNCH(tq_count_kernel<uint64_t>, dim3(ql.n_pieces), dim3(256), lds, ls, rs->view(), c->k, t, ql.sbits, ql.n_slices,
-                              ql.n_pieces, ql.d_tile_off);
+            });
         }
         {
             KScope ks(c, "tq_scan_kernels", ls);
@@ -429,18 +402,14 @@ int build_query_list(commet_ctx *c, const commet_readset *rs)
             uint32_t rpr = (TQ_PIECE + rounds - 1) / rounds;
             while (rpr > 1 && (uint64_t) rpr * (uint64_t) fhw > TQ_FILL_CAP) --rpr;
             const size_t lds_fill = ((size_t) 4 * ql.n_slices + 2 * TQ_FILL_CAP) * 4;
-            e = hipFuncSetAttribute(c->k <= 32 ? (const void *) tq_fill_kernel<uint32_t> : (const void *) tq_fill_kernel<uint64_t>,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds_fill);
-            if (e == hipSuccess) {
+            e = with_key(c->k, [&](auto key) {
+                hipError_t fe = hipFuncSetAttribute((const void *) tq_fill_kernel<decltype(key)>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds_fill);
+                if (fe != hipSuccess) return fe;
                 KScope ks(c, "tq_fill_kernel", ls);
-                if (c->k <= 32)
-                    COMMET_LAUNCH(tq_fill_kernel<uint32_t>, dim3(ql.n_pieces), dim3(256), lds_fill, ls, rs->view(), c->k, t, ql.sbits,
-                                  ql.n_slices, ql.n_pieces, rpr, ql.d_tstart, ql.d_qaddr, ql.d_qwho);
-                else
-                    COMMET_LAUNCH(tq_fill_kernel<uint64_t>, dim3(ql.n_pieces), dim3(256), lds_fill, ls, rs->view(), c->k, t, ql.sbits,
-                                  ql.n_slices, ql.n_pieces, rpr, ql.d_tstart, ql.d_qaddr, ql.d_qwho);
-                e = hipGetLastError();
-            }
+                COMMET_LAUNCH(tq_fill_kernel<decltype(key)>, dim3(ql.n_pieces), dim3(256), lds_fill, ls, rs->view(), c->k, t, ql.sbits, ql.n_slices,
+                              ql.n_pieces, rpr, ql.d_tstart, ql.d_qaddr, ql.d_qwho);
+                return hipGetLastError();
+            });
         }
     }
     if (e == hipSuccess) e = hipEventRecord(c->ev_list, ls);
@@ -487,16 +456,17 @@ bool query_list_blocks(const commet_ctx *c, const commet_readset *rs, uint64_t o
 {
     const int t = t_eff(c, rs);
     const int64_t fhw = (int64_t) rs->max_len - (int64_t) t * c->k + 1;
-    if (c->k <= TQ_SBITS || c->k > TQ_MAX_K || fhw < 1 || fhw > TQ_MAX_WIN || rs->max_len >= TQ_MAX_LEN || rs->n_reads < (1ull << 20) || rs->n_reads >= (1ull << 32)) return false;
+    if (c->k <= TQ_SLICE_BITS || c->k > TQ_MAX_K || fhw < 1 || fhw > TQ_MAX_WIN || rs->max_len >= TQ_MAX_LEN || rs->n_reads < (1ull << 20) || rs->n_reads >= (1ull << 32)) return false;
     const uint64_t records = rs->fhw_total;                   // (an upper bound: windows with a non-ACGT base make no record)
     if (records >= (1ull << 32)) return false;
-    int sbits = TQ_SBITS;
-    if (c->tq_sbits) sbits = std::max(c->k - 10, std::min(c->k - 1, c->tq_sbits));
-    const uint64_t entries = ((uint64_t) 1 << (c->k - sbits)) * ((rs->n_reads + TQ_PIECE - 1) / TQ_PIECE);
+    const uint64_t entries = ((uint64_t) 1 << (c->k - TQ_SLICE_BITS)) * ((rs->n_reads + TQ_PIECE - 1) / TQ_PIECE);
     out[0] = (entries + 1) * 8, out[1] = records * 4, out[2] = records * 2, out[3] = entries * 4, out[4] = entries * 2;
     out[5] = c->qres_cap >= records ? 0 : records;            // the context's result buffer, one byte per record
     return true;
 }
+
+constexpr unsigned TQ_PROBE_WGS_PER_XCD = 64;   // probe workgroups per XCD (a multiple of the 32 CUs of an XCD keeps the sweep even;
+                                                // measured: 32 or 64 (1 or 2 per CU) 2.3-2.6 ms, 128: 3.7, 256: 4.8)
 
 // one pass of rs over the g <= 2 chunk filters in slots slot0 .. slot0 + g - 1 (g == 2: slots 0, 1 with interleaved A planes)
 // job_tag_words != 0 (g == 2): the two filters belong to two jobs; job j's found flags go to d_tags + j * job_tag_words (zeroed by the caller)
@@ -515,53 +485,30 @@ int launch_search_tiled(commet_ctx *c, const commet_readset *rs, int g, int slot
     fg.slot_words = 4 * c->plane_words;
     fg.plane_words = c->plane_words;
     fg.g = g;
-    // The probe is bound by L2 gathers, the replay by L2-MISSING requests and bookkeeping: different walls.  The set is cut
-    // into `parts` runs of pieces; part i's probe and replay go to stream i % 2, every probe waiting for the probe before it
-    // (one slice sweep at a time keeps the slice's filter words in L2), so the replay of part i runs beside the probe of
-    // part i + 1.  With per-kernel timing on (durations must add up) or a small set: one part, one stream.
+    // The probe is bound by L2 gathers, the replay by L2-MISSING requests and bookkeeping: different walls, but run beside each
+    // other (the set cut into runs of pieces, the replay of one beside the probe of the next on a second stream) they contend for
+    // the same memory system: measured on configs[1] 19.76 ms per step in one part, 21.8 / 23.2 / 24.6 / 25.3 in 2 / 3 / 4 / 6
+    // (r03_parts_*.json).  So the whole set's probe, then its replay, on the job's stream.
     const int mw = mask_words(c, rs);
     const int t = t_eff(c, rs);
-    uint32_t parts = (c->kclock.on || q.n_pieces < 4096) ? 1u : (uint32_t) std::max(1, std::min(16, c->tq_parts));
-    const unsigned wpx = c->tq_wpx;
-    hipEvent_t ev_probe = c->ev_fork, ev_done = c->ev_join;
-    for (uint32_t pi = 0; pi < parts; ++pi) {
-        const uint32_t p0 = (uint32_t) ((uint64_t) q.n_pieces * pi / parts), p1 = (uint32_t) ((uint64_t) q.n_pieces * (pi + 1) / parts);
-        hipStream_t st = (pi & 1u) ? c->aux_stream : c->stream;
-        if (pi) HIP_OK(hipStreamWaitEvent(st, ev_probe, 0));      // behind the previous part's probe (and so behind the filter build)
-        {
-            KScope ks(c, "tq_probe_kernel", st);
-            if (g == 1) COMMET_LAUNCH(tq_probe_kernel<1>, dim3(8 * wpx), dim3(256), 0, st, v, fg.il_a, c->d_qres, p0, p1);
-            else COMMET_LAUNCH(tq_probe_kernel<2>, dim3(8 * wpx), dim3(256), 0, st, v, fg.il_a, c->d_qres, p0, p1);
-        }
-        HIP_OK(hipGetLastError());
-        if (pi + 1 < parts) HIP_OK(hipEventRecord(ev_probe, st));
-        {
-            KScope ks(c, "tq_replay_kernel", st);
-            const dim3 grid(p1 - p0), block(TQ_PIECE);
-#define COMMET_TQ_REPLAY(W, GS, MW) COMMET_LAUNCH((tq_replay_kernel<W, GS, MW>), grid, block, 0, st, rs->view(), v, c->d_qres, fg, c->k, t, d_sel, d_tags, d_counters, cstride, p0, (uint32_t) std::min<int>(c->tq_hit_cap, TQ_HIT_CAP), job_tag_words)
-#define COMMET_TQ_REPLAY_MW(W, GS)                 \
-    do {                                           \
-        if (mw == 2) COMMET_TQ_REPLAY(W, GS, 2);   \
-        else if (mw == 3) COMMET_TQ_REPLAY(W, GS, 3); \
-        else if (mw == 4) COMMET_TQ_REPLAY(W, GS, 4); \
-        else if (mw == 6) COMMET_TQ_REPLAY(W, GS, 6); \
-        else COMMET_TQ_REPLAY(W, GS, 8);           \
-    } while (0)
-            if (c->k <= 32) {
-                if (g == 1) COMMET_TQ_REPLAY_MW(uint32_t, 1);
-                else COMMET_TQ_REPLAY_MW(uint32_t, 2);
-            } else {
-                if (g == 1) COMMET_TQ_REPLAY_MW(uint64_t, 1);
-                else COMMET_TQ_REPLAY_MW(uint64_t, 2);
-            }
-#undef COMMET_TQ_REPLAY_MW
-#undef COMMET_TQ_REPLAY
-        }
-        HIP_OK(hipGetLastError());
+    {
+        KScope ks(c, "tq_probe_kernel", c->stream);
+        with_value<1, 2>(g, [&](auto GS) {
+            COMMET_LAUNCH(tq_probe_kernel<GS>, dim3(8 * TQ_PROBE_WGS_PER_XCD), dim3(256), 0, c->stream, v, fg.il_a, c->d_qres, 0u, q.n_pieces);
+        });
     }
-    if (parts > 1) {   // the second stream's replays join the main stream (the even parts are on it already)
-        HIP_OK(hipEventRecord(ev_done, c->aux_stream));
-        HIP_OK(hipStreamWaitEvent(c->stream, ev_done, 0));
+    HIP_OK(hipGetLastError());
+    {
+        KScope ks(c, "tq_replay_kernel", c->stream);
+        const uint32_t hit_cap = (uint32_t) std::min<int>(c->tq_hit_cap, TQ_HIT_CAP);
+        with_key(c->k, [&](auto key) {
+            with_value<1, 2>(g, [&](auto GS) {
+                with_mask_words(mw, [&](auto MW) {
+                    COMMET_LAUNCH((tq_replay_kernel<decltype(key), GS, MW>), dim3(q.n_pieces), dim3(TQ_PIECE), 0, c->stream, rs->view(), v, c->d_qres,
+                                  fg, c->k, t, d_sel, d_tags, d_counters, cstride, 0u, hit_cap, job_tag_words);
+                });
+            });
+        });
     }
     HIP_OK(hipGetLastError());
     return 0;
@@ -624,12 +571,9 @@ int launch_slice_build(commet_ctx *c, const commet_readset *rs, const uint64_t *
     const unsigned grid = (unsigned) ((((uint64_t) 4 << (c->k - 5)) + 255) / 256);
     {
         KScope ks(c, "slice_transpose_kernel", c->stream);
-        switch (gw) {
-        case 1: COMMET_LAUNCH(slice_transpose_kernel<1>, dim3(grid), dim3(256), 0, c->stream, c->slice_stage, c->k, g, tables, row_words, col0); break;
-        case 2: COMMET_LAUNCH(slice_transpose_kernel<2>, dim3(grid), dim3(256), 0, c->stream, c->slice_stage, c->k, g, tables, row_words, col0); break;
-        case 4: COMMET_LAUNCH(slice_transpose_kernel<4>, dim3(grid), dim3(256), 0, c->stream, c->slice_stage, c->k, g, tables, row_words, col0); break;
-        default: COMMET_LAUNCH(slice_transpose_kernel<8>, dim3(grid), dim3(256), 0, c->stream, c->slice_stage, c->k, g, tables, row_words, col0); break;
-        }
+        with_value<1, 2, 4, 8>(gw, [&](auto GW) {
+            COMMET_LAUNCH(slice_transpose_kernel<GW>, dim3(grid), dim3(256), 0, c->stream, c->slice_stage, c->k, g, tables, row_words, col0);
+        });
     }
     HIP_OK(hipGetLastError());
     return 0;
@@ -643,12 +587,10 @@ int launch_search_sliced(commet_ctx *c, const commet_readset *rs, int g, int gw,
     const uint64_t blocks = (rs->n_reads + 255) / 256;
     const dim3 grid((unsigned) ((blocks + block_stride - 1) / block_stride)), block(256);
     KScope ks(c, "search_sliced_kernel", c->stream);
-    switch (gw) {
-    case 1: COMMET_LAUNCH(search_sliced_kernel<1>, grid, block, 0, c->stream, rs->view(), c->slice_tables, c->k, t_eff(c, rs), g, d_sel, d_tags, d_counters, cstride, block_stride); break;
-    case 2: COMMET_LAUNCH(search_sliced_kernel<2>, grid, block, 0, c->stream, rs->view(), c->slice_tables, c->k, t_eff(c, rs), g, d_sel, d_tags, d_counters, cstride, block_stride); break;
-    case 4: COMMET_LAUNCH(search_sliced_kernel<4>, grid, block, 0, c->stream, rs->view(), c->slice_tables, c->k, t_eff(c, rs), g, d_sel, d_tags, d_counters, cstride, block_stride); break;
-    default: COMMET_LAUNCH(search_sliced_kernel<8>, grid, block, 0, c->stream, rs->view(), c->slice_tables, c->k, t_eff(c, rs), g, d_sel, d_tags, d_counters, cstride, block_stride); break;
-    }
+    with_value<1, 2, 4, 8>(gw, [&](auto GW) {
+        COMMET_LAUNCH(search_sliced_kernel<GW>, grid, block, 0, c->stream, rs->view(), c->slice_tables, c->k, t_eff(c, rs), g, d_sel, d_tags,
+                      d_counters, cstride, block_stride);
+    });
     HIP_OK(hipGetLastError());
     return 0;
 }
@@ -712,13 +654,12 @@ int launch_search_wide(commet_ctx *c, const commet_readset *rs, const WidePlan &
     const dim3 grid((unsigned) blocks), block(256);
     const int t = t_eff(c, rs);
     KScope ks(c, "search_wide_kernel", c->stream);
-#define COMMET_WIDE(LPR, NP) COMMET_LAUNCH((search_wide_kernel<LPR, NP>), grid, block, 0, c->stream, rs->view(), c->wide_tables, c->k, t, g, w.nw, w.rw, d_sel, d_tags, d_counters, cstride)
-    if (w.np == 2) COMMET_WIDE(64, 2);
-    else if (w.lpr == 64) COMMET_WIDE(64, 1);
-    else if (w.lpr == 32) COMMET_WIDE(32, 1);
-    else if (w.lpr == 16) COMMET_WIDE(16, 1);
-    else COMMET_WIDE(8, 1);
-#undef COMMET_WIDE
+    auto launch = [&](auto LPR, auto NP) {
+        COMMET_LAUNCH((search_wide_kernel<LPR, NP>), grid, block, 0, c->stream, rs->view(), c->wide_tables, c->k, t, g, w.nw, w.rw, d_sel, d_tags,
+                      d_counters, cstride);
+    };
+    if (w.np == 2) launch(std::integral_constant<int, 64>{}, std::integral_constant<int, 2>{});
+    else with_value<64, 32, 16, 8>(w.lpr, [&](auto LPR) { launch(LPR, std::integral_constant<int, 1>{}); });
     HIP_OK(hipGetLastError());
     return 0;
 }

@@ -37,6 +37,27 @@ inline void note_launch(const void *entry)
         hipLaunchKernelGGL(kernel, __VA_ARGS__);                      \
     } while (0)
 
+// Run-time choices -> template arguments: f is called with the case that applies, and a call site instantiates its kernels
+// for every case listed and no other.
+// f(W{}) with W the key type of k-mers of length k: uint32_t up to 32, uint64_t above
+template <typename F>
+decltype(auto) with_key(int k, F &&f)
+{
+    if (k <= 32) return f(uint32_t{});
+    return f(uint64_t{});
+}
+// f(std::integral_constant<V>) for the first of the listed values V that equals v; the last one when none does
+template <auto V, auto... Vs, typename T, typename F>
+decltype(auto) with_value(T v, F &&f)
+{
+    if constexpr (sizeof...(Vs) == 0) {
+        return f(std::integral_constant<decltype(V), V>{});
+    } else {
+        if (v == V) return f(std::integral_constant<decltype(V), V>{});
+        return with_value<Vs...>(v, f);
+    }
+}
+
 // ---- device memory kept for reuse ----------------------------------------------------------------------------------------
 // On this driver a hipMalloc of GBs costs 15-30 ms per GiB on some boxes (and ~0 on others: tools/exp/alloc_cost*.hip — where a
 // 16 GiB hipMalloc took 483 ms, and 965 ms again after its hipFree, sixteen of 1 GiB took 0.3 ms and a hipMallocAsync of 16 GiB
@@ -400,11 +421,9 @@ struct commet_ctx {
     bool have_index_ev = false, have_search_ev = false;
     bool count_probes = false;
     int index_mode = 0;               // 0 auto, 1 atomic kernel, 2 bucketed construction
-    int part_b1 = 0;                  // override of the level-1 radix bits (0 = default split)
     int part_packed = 1;              // option: final buckets as groups of three 19-bit keys in 8 bytes (index_part.hpp)
     int part_no_uni = 0;              // option: never take the uniform-length fast path of hist / scatter1 (tests, A/B timing)
     int part_list = 0;                // option: 0 = ragged sets take the item list in hist / scatter1 (index_part.hpp, LIST), 1 = never (the round planner)
-    int s2_swizzle = 128;             // scatter2 slab order: number of interleaved slab ranges (index_part.hpp), 0 = dispatch order
     uint64_t part_min_kmers = 8ull << 20;
     // workspaces of the bucketed construction (index_part.hpp): two, so that the chunks of a group can be built on two
     // streams at once (the compute-bound hist / scatter1 of one chunk overlap the HBM-bound scatter2 / build of another)
@@ -419,7 +438,6 @@ struct commet_ctx {
         uint64_t items_cap = 0, itemblk_cap = 0;
         uint64_t items_set = 0, items_first = 0, items_count = 0;  // whose list the buffer holds: (set uid, read range), no selection — 0 = nobody's
         uint32_t items_nblk = 0;
-        uint64_t hist_set = 0, hist_first = 0, hist_count = 0;     // (timing bound COMMET_HIST_REUSE only: whose histogram the workspace holds)
         uint32_t nb = 0;
         void release()
         {
@@ -447,8 +465,7 @@ struct commet_ctx {
                                               // host thread while another runs jobs on sets that are complete
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     int index_lanes = 2;                      // option: 1 = build the chunks of a group one after the other
-    int lane_stagger = 1;                     // option / COMMET_LANE_STAGGER: the second lane's chunk starts behind the first lane's scatter1 (index_dispatch.hpp)
-    bool stagger_armed = false;
+    bool stagger_armed = false;               // the second lane's chunk starts behind the first lane's scatter1 (index_dispatch.hpp)
     hipEvent_t ev_stagger = nullptr;
 
     int n_slots = 1;                  // filter slots allocated behind `filter` (chunk groups, kernels.hpp)
@@ -513,14 +530,7 @@ struct commet_ctx {
     unsigned long long *d_lo_cnt = nullptr;   // scratch of that list's counting sort (class-major block counts), kept
     uint64_t lo_cnt_cap = 0;
     int tiled_mode = 0;               // option "tiled_search": 0 auto (large sets, groups of 1 or 2 chunks), 1 never, 2 whenever possible
-    // environment knobs of A/B runs, read ONCE in commet_create (nothing on the launch path calls getenv)
-    int tq_sbits = 0;                 // COMMET_TQ_SBITS: log2 bits per address slice of the query list (0 = TQ_SBITS)
-    int tq_parts = 1;                 // COMMET_TQ_PARTS / option "tq_parts": runs of pieces whose replay overlaps the next run's probe.  Off:
-                                      // measured on configs[1] 19.76 ms per step in one part, 21.8 / 23.2 / 24.6 / 25.3 in 2 / 3 / 4 / 6 (the
-                                      // replay of one part and the probe of the next contend for the same memory system, r03_parts_*.json)
-    unsigned tq_wpx = 64;             // COMMET_TQ_WPX: probe workgroups per XCD (a multiple of the 32 CUs of an XCD keeps the sweep even;
-                                      // measured: 32 or 64 (1 or 2 per CU) 2.3-2.6 ms, 128: 3.7, 256: 4.8)
-    bool stage_reads = true;          // COMMET_NO_STAGE_READS: search_group_kernel without the LDS copy of the lanes' reads
+    // environment knobs, read ONCE in commet_create (nothing on the launch path calls getenv)
     bool job_verbose = false;         // COMMET_JOB_VERBOSE: host-side phase times of every commet_index_and_search call on stderr
     bool ingest_verbose = false;      // COMMET_INGEST_VERBOSE
     int slice_mode = 0;               // option: 0 auto, 1 never, 2 whenever k allows it

@@ -30,47 +30,27 @@
 
 namespace commet {
 
-// Timing ablations (results become wrong on purpose) exist only in builds made with -DCOMMET_ABLATE=<mask>; the shipped
-// library compiles them out.  scatter1: 1 no write-out, 2 no pass B, 4 no pass-A atomics; scatter2: 32 no placement,
-// 64 no write-out, 128 no cursor reservation, 256 no counting.
-#ifndef COMMET_ABLATE
-#define COMMET_ABLATE 0
-#endif
-
 constexpr int      TILE_BITS = 19;
 constexpr uint32_t TILE_MASK = (1u << TILE_BITS) - 1;
 constexpr uint32_t TILE_WORDS = 1u << (TILE_BITS - 5);      // 16384 words = 64 KiB
-#ifndef COMMET_S1_NT
-#define COMMET_S1_NT 512
-#endif
-constexpr int      S1_NT = COMMET_S1_NT;                    // scatter-1 workgroup size
-constexpr uint32_t S1_KEYS = 32u * COMMET_S1_NT;            // keys staged per scatter-1 round (64 KiB)
+constexpr int      S1_NT = 512;                             // scatter-1 workgroup size
+constexpr uint32_t S1_KEYS = 32u * S1_NT;                   // keys staged per scatter-1 round (64 KiB)
 constexpr uint32_t S1_ITEMS = S1_NT;                        // octet items per round: one per thread, keys cached
-#ifndef COMMET_S2_NT
-#define COMMET_S2_NT 512   // (448 threads x 72 VGPRs = four workgroups per CU instead of three: 4.52 against 4.54 ms per configs[1] step; 384: 5.06)
-#endif
-constexpr int      S2_NT = COMMET_S2_NT;                    // scatter-2 workgroup size
-constexpr uint32_t S2_KEYS = 16u * COMMET_S2_NT;            // keys per scatter-2 block (16 per thread)
+constexpr int      S2_NT = 512;                             // scatter-2 workgroup size (448 threads x 72 VGPRs = four workgroups per CU instead of
+                                                            // three: 4.52 against 4.54 ms per configs[1] step; 384: 5.06)
+constexpr uint32_t S2_KEYS = 16u * S2_NT;                   // keys per scatter-2 block (16 per thread)
 constexpr uint32_t S2_PER_THREAD = S2_KEYS / S2_NT;
-#ifndef S2P_WAVES
-#define S2P_WAVES 6   // 80 VGPRs, three workgroups per CU; 8 (64 VGPRs, four per CU with S2P_MAX_SUB = 128) spills and measured 4.6 instead of 4.1 ms
-#endif
+constexpr int      S2P_WAVES = 6;                           // 80 VGPRs, three workgroups per CU; 8 (64 VGPRs, four per CU with S2P_MAX_SUB = 128)
+                                                            // spills and measured 4.6 instead of 4.1 ms
 constexpr uint32_t S2P_MAX_SUB = 256;                       // packed scatter-2: final buckets per coarse bucket (k <= 33: the reference's default k takes the packed
                                                             // geometry too; 41.9 KiB of LDS, three workgroups of 80 VGPRs per CU either way)
 constexpr int      HIST_NT = 1024;                          // histogram workgroup size
-#ifndef BUILD_NT
-#define BUILD_NT 1024   // build workgroup: its loads in flight are what the kernel runs on (256 / 512 / 1024 threads: 2.75 / 2.52 / 2.36 ms per configs[1] step)
-#endif
+constexpr int      BUILD_NT = 1024;                         // build workgroup: its loads in flight are what the kernel runs on (256 / 512 / 1024
+                                                            // threads: 2.75 / 2.52 / 2.36 ms per configs[1] step)
 constexpr uint32_t BUILD_CAP = 1u << 17;                    // keys per build workgroup
 constexpr uint32_t HIST_MAX_BUCKETS = 32768;                // LDS histogram capacity (128 KiB)
 constexpr uint32_t MAX_SUB = 512;                           // 2^b2 upper bound
 constexpr uint32_t MAX_L1 = 256;                            // 2^b1 upper bound
-#ifndef HIST_ROLLING
-#define HIST_ROLLING 1
-#endif
-#ifndef S1_ALIGNED
-#define S1_ALIGNED 1
-#endif
 constexpr uint32_t S1_GRID_MAX = 1024;                       // pieces of the read range = scatter-1 workgroups (two run per CU at a time; 512 / 1024 / 2048 pieces: 4.46 / 4.37 / 4.33 ms per configs[1] step)
 
 struct PartGeom {
@@ -101,7 +81,7 @@ inline PartGeom make_geom(int k)
     g.nb = 1u << g.nb_bits;
     g.nb1 = 1u << g.b1;
     g.plane_shift = k - TILE_BITS;
-    g.xcd_swizzle = 0;
+    g.xcd_swizzle = 128;   // scatter2: 128 interleaved slab ranges (part_scatter2_kernel)
     g.packed = 0;
     return g;
 }
@@ -113,44 +93,18 @@ __device__ __forceinline__ uint32_t octets_of(uint32_t len, int k)
     return len >= (uint32_t) k ? ((len - 1) >> 3) - ((uint32_t) (k - 1) >> 3) + 1 : 0;
 }
 
-// calls f(plane, key) for the 4 forward keys of every complete k-mer ending in octet q of the read at p
-// TOP: the plane-A key is only good for its bucket (psi_a_top)
-// planes: bit p set = plane p's key is wanted (a histogram pass over part of the buckets needs only some planes)
-template <typename W, bool TOP = false, typename F>
-__device__ __forceinline__ void for_each_key(const uint32_t *p, uint32_t len, uint32_t q, int k, F &&f, uint32_t planes = 15u)
-{
-    using T = KeyTraits<W>;
-    const uint32_t w = q >> 2;
-    ItemWords<W> it;
-    it.load(p, w);
-    const W mask = (k == T::BITS) ? ~(W) 0 : (((W) 1 << k) - 1);
-    const int sh = T::BITS - k;
-    const uint32_t j0 = (q & 3u) * 8u;
-#pragma unroll
-    for (uint32_t jj = 0; jj < 8; ++jj) {
-        const uint32_t j = j0 + jj;
-        const uint32_t pos = 32u * w + j;
-        if (pos + 1u < (uint32_t) k || pos >= len) continue;
-        W wh, wl;
-        if (!it.window(j, k, mask, wh, wl)) continue;
-        const W ka = T::brev(wh) >> sh;
-        const W kb = T::brev(wl) >> sh;
-        if (planes & 1u) f(0u, TOP ? psi_a_top<W>(ka, k) : psi_a<W>(ka, k));   // plane A is stored strand-paired (kernels.hpp)
-        if (planes & 2u) f(1u, kb);
-        if (planes & 4u) f(2u, ka ^ kb);
-        if (planes & 8u) f(3u, ka | kb);
-    }
-}
-
-// The same for a bucket count (k <= 32): calls f(plane, bucket) with bucket = key >> TILE_BITS, the top nbits = k - TILE_BITS
-// bits of the plane's key, for the complete k-mers ending in octet q.  Those bits roll from one position to the next:
+// Bucket count (k <= 32): calls f(plane, bucket) for the 4 forward keys of every complete k-mer ending in octet q of the read
+// at p, with bucket = key >> TILE_BITS, the top nbits = k - TILE_BITS bits of the plane's key.  Those bits roll from one
+// position to the next:
 //   top(keya) = the hi bits of the nbits OLDEST bases, oldest first   -> shift left, the next base enters at the bottom
 //   top(keyb) = the same of the lo bits
-//   top(psi_a) = top(keya) ^ ~(hi bits of the nbits NEWEST bases, newest first)    (psi_a_top: s = u ^ g(L))
+//   top(psi_a) = top(keya) ^ ~(hi bits of the nbits NEWEST bases, newest first)
 //                                                                     -> shift right, the new base enters at the top
-// so a position costs ~27 instructions instead of the ~52 of three 64-bit window extractions, two bit reversals and
-// psi_a_top (the histogram kernel spends 82 % of the VALU's cycles).  The entering bases sit at fixed offsets from the
-// octet's first position (k - nbits = TILE_BITS), one 64-bit shift per plane and octet.
+// (psi_a's top bits are its s field, u ^ g(L) in kernels.hpp: s fills the address from bit h (+1 for odd k) upwards, and
+// h (+1) <= TILE_BITS for every k the bucketed construction takes.)  So a position costs ~27 instructions instead of the ~52
+// of three 64-bit window extractions, two bit reversals and the top bits of psi_a (the histogram kernel spends 82 % of the
+// VALU's cycles).  The entering bases sit at fixed offsets from the octet's first position (k - nbits = TILE_BITS), one
+// 64-bit shift per plane and octet.
 template <typename F>
 __device__ __forceinline__ void for_each_bucket32(const uint32_t *p, uint32_t len, uint32_t q, int k, F &&f)
 {
@@ -578,22 +532,12 @@ __global__ __launch_bounds__(HIST_NT) void part_hist_kernel(ReadsView rv, const 
     for (uint32_t pl = 0; pl < 4; ++pl)
         if (((pl + 1) << g.plane_shift) > b_lo && (pl << g.plane_shift) < b_lo + n_b) planes |= 1u << pl;
     if (FULL) planes = 15u;
-    // k <= 32 (always FULL): the buckets come from rolled top bits (for_each_bucket32)
-    constexpr bool ROLL = FULL && sizeof(W) == 4 && HIST_ROLLING;
-    constexpr bool ROLL64 = !FULL && sizeof(W) == 8 && HIST_ROLLING;       // k = 33, 34: the same rolling, pass by pass
+    // k <= 32 (always FULL): the buckets come from rolled top bits (for_each_bucket32); k = 33, 34: the same rolling, pass by pass
+    static_assert(FULL == (sizeof(W) == 4), "32-bit keys take the full histogram, 64-bit keys the passes");
     auto add_bucket = [&](uint32_t plane, uint32_t bucket) { atomicAdd(h + (plane << g.plane_shift) + bucket, 1u); };
     // (a pass of 64-bit keys covers whole planes: HIST_MAX_BUCKETS is a multiple of a plane's 2^(k - 19) buckets, so the
     // planes mask alone decides and the bucket's place in the pass is its number minus b_lo)
     auto add_bucket_rel = [&](uint32_t plane, uint32_t bucket) { atomicAdd(h + ((plane << g.plane_shift) + bucket - b_lo), 1u); };
-    auto add = [&](uint32_t plane, W key) {
-        if (FULL) {
-            atomicAdd(h + (plane << g.plane_shift) + (uint32_t) (key >> TILE_BITS), 1u);
-        } else {
-            const uint32_t b = (plane << g.plane_shift) | (uint32_t) (key >> TILE_BITS);
-            const uint32_t rel = b - b_lo;
-            if (rel < n_b) atomicAdd(&h[rel], 1u);
-        }
-    };
     for (uint32_t half = 0; half < 2; ++half) {
         const uint64_t j = 2ull * blockIdx.x + half;
         if (j >= n_blk1) break;   // uniform
@@ -606,9 +550,8 @@ __global__ __launch_bounds__(HIST_NT) void part_hist_kernel(ReadsView rv, const 
             for (; id < i1; id += NT) {
                 const uint32_t dn = id + NT < i1 ? items[id + NT] : 0u;      // (the next item's descriptor travels while this one's keys are counted)
                 const ListItem li = list_item(l_planes, d);
-                if constexpr (ROLL) for_each_bucket32(li.p, 0xFFFFFFFFu, li.q, g.k, add_bucket);
-                else if constexpr (ROLL64) for_each_bucket64(li.p, 0xFFFFFFFFu, li.q, g.k, planes, add_bucket_rel);
-                else for_each_key<W, true>(li.p, 0xFFFFFFFFu, li.q, g.k, add, planes);
+                if constexpr (FULL) for_each_bucket32(li.p, 0xFFFFFFFFu, li.q, g.k, add_bucket);
+                else for_each_bucket64(li.p, 0xFFFFFFFFu, li.q, g.k, planes, add_bucket_rel);
                 d = dn;
             }
         } else if (UNI) {
@@ -621,9 +564,8 @@ __global__ __launch_bounds__(HIST_NT) void part_hist_kernel(ReadsView rv, const 
             for (uint64_t id = threadIdx.x; id < total; id += NT) {
                 const uint64_t rn = ids ? (uint64_t) ids[rd] : rd;          // the read's number
                 const uint32_t *rp = rv.planes + 3 * (((rn * L) >> 5) + rn);
-                if constexpr (ROLL) for_each_bucket32(rp, L, q + q_first, g.k, add_bucket);
-                else if constexpr (ROLL64) for_each_bucket64(rp, L, q + q_first, g.k, planes, add_bucket_rel);
-                else for_each_key<W, true>(rp, L, q + q_first, g.k, add, planes);
+                if constexpr (FULL) for_each_bucket32(rp, L, q + q_first, g.k, add_bucket);
+                else for_each_bucket64(rp, L, q + q_first, g.k, planes, add_bucket_rel);
                 rd += dpos, q += dq;
                 if (q >= opr) q -= opr, ++rd;
             }
@@ -634,9 +576,8 @@ __global__ __launch_bounds__(HIST_NT) void part_hist_kernel(ReadsView rv, const 
                 for (uint32_t id = threadIdx.x; id < rp.n_items; id += NT) {
                     uint32_t slot, q;
                     item_lookup(istart, rp.n_reads, id, g.k, slot, q);
-                    if constexpr (ROLL) for_each_bucket32(rv.planes + 3 * rd_t0[slot], rd_len[slot], q, g.k, add_bucket);
-                    else if constexpr (ROLL64) for_each_bucket64(rv.planes + 3 * rd_t0[slot], rd_len[slot], q, g.k, planes, add_bucket_rel);
-                    else for_each_key<W, true>(rv.planes + 3 * rd_t0[slot], rd_len[slot], q, g.k, add, planes);
+                    if constexpr (FULL) for_each_bucket32(rv.planes + 3 * rd_t0[slot], rd_len[slot], q, g.k, add_bucket);
+                    else for_each_bucket64(rv.planes + 3 * rd_t0[slot], rd_len[slot], q, g.k, planes, add_bucket_rel);
                 }
                 __syncthreads();
                 r += rp.n_reads;
@@ -800,7 +741,7 @@ __global__ __launch_bounds__(S1_NT, 4) void part_scatter1_kernel(ReadsView rv, c
     // ALIGNED: a run's LDS copy starts at the same offset from a 16-byte boundary as its place in bufA (up to 3 + 3 idle
     // slots per run), so that the write-out reads whole vectors from LDS.  Only where the LDS allows it beside two
     // workgroups per CU: the round planner's tables of the other variant take that room.
-    constexpr bool ALIGNED = UNI && S1_ALIGNED;
+    constexpr bool ALIGNED = UNI;
     __shared__ __attribute__((aligned(16))) uint32_t sorted[S1_KEYS + (ALIGNED ? 6 * MAX_L1 : 0)];
     __shared__ uint32_t cnt[MAX_L1], base[MAX_L1];
     __shared__ unsigned long long gbase[MAX_L1], gcur[MAX_L1];   // this round's / the next round's output position per coarse bucket
@@ -939,7 +880,7 @@ __global__ __launch_bounds__(S1_NT, 4) void part_scatter1_kernel(ReadsView rv, c
                 if (WIDE)   // k <= 34: at most two bits above the low word
                     chi[jj >> 2] |= ((uint32_t) ((uint64_t) ka >> 32) | ((uint32_t) ((uint64_t) kb >> 32) << 2) | ((uint32_t) ((uint64_t) pa >> 32) << 4))
                                     << (6u * (jj & 3u));
-                if (ok && !(COMMET_ABLATE & 4)) {   // crk[] of other positions is never read
+                if (ok) {   // crk[] of other positions is never read
                     cvalid |= 1u << jj;
                     const uint32_t r0 = atomicAdd(cnt + (uint32_t) (pa >> sA), 1u);
                     const uint32_t r1 = atomicAdd(cnt_b + (uint32_t) (kb >> sA), 1u);
@@ -989,7 +930,7 @@ __global__ __launch_bounds__(S1_NT, 4) void part_scatter1_kernel(ReadsView rv, c
             __syncthreads();
         }
         // pass B: place every key at its bucket's base + its rank
-        if (ion && !(COMMET_ABLATE & 2)) {
+        if (ion) {
             const uint32_t *const base_b = base + nbp, *const base_c = base + 2 * nbp, *const base_d = base + 3 * nbp;
 #pragma unroll
             for (uint32_t jj = 0; jj < 8; ++jj) {
@@ -1015,9 +956,7 @@ __global__ __launch_bounds__(S1_NT, 4) void part_scatter1_kernel(ReadsView rv, c
         __syncthreads();
         if (UNI) pre_claim();
         // write-out: one wave per run, consecutive lanes -> consecutive addresses
-        if (!(COMMET_ABLATE & 1))
-        for (uint32_t c1 = wave * 4 + (lane >> 4); c1 < g.nb1; c1 += (NT / 64) * 4)
-        {
+        for (uint32_t c1 = wave * 4 + (lane >> 4); c1 < g.nb1; c1 += (NT / 64) * 4) {
             if (ALIGNED) write_run_aligned(out, gbase[c1], sorted, base[c1], cnt[c1], lane & 15u, 16u);
             else write_run(out, gbase[c1], sorted, base[c1], cnt[c1], lane & 15u, 16u);
         }
@@ -1040,7 +979,7 @@ __global__ __launch_bounds__(S2_NT, S2P_WAVES) void part_scatter2_kernel(const u
     __shared__ unsigned long long gbase[MAX_SUB];
     __shared__ uint32_t wsum[16];
     const uint32_t nsub = 1u << g.b2;
-    // Slab order (option "s2_swizzle" = G, 0 = dispatch order): workgroups b with equal b % G walk one of G contiguous
+    // Slab order (g.xcd_swizzle = G, 0 = dispatch order): workgroups b with equal b % G walk one of G contiguous
     // ranges of slabs, so the workgroups that run at the same time work on G different places of bufA, i.e. on
     // different coarse buckets, instead of all reserving space through the same 2^b2 cursors.  G = 8 is the
     // XCD-contiguous order (all writers of a final bucket behind one L2).  Placement never affects results.
@@ -1085,8 +1024,7 @@ __global__ __launch_bounds__(S2_NT, S2P_WAVES) void part_scatter2_kernel(const u
                 key[4 * q] = v.x, key[4 * q + 1] = v.y, key[4 * q + 2] = v.z, key[4 * q + 3] = v.w;
             }
 #pragma unroll
-            for (uint32_t q = 0; q < S2_PER_THREAD; ++q)
-                if (!(COMMET_ABLATE & 256)) atomicAdd(&cnt[key[q] >> TILE_BITS], 1u);
+            for (uint32_t q = 0; q < S2_PER_THREAD; ++q) atomicAdd(&cnt[key[q] >> TILE_BITS], 1u);
         } else {
 #pragma unroll
             for (uint32_t q = 0; q < S2_PER_THREAD; ++q) {
@@ -1096,7 +1034,7 @@ __global__ __launch_bounds__(S2_NT, S2P_WAVES) void part_scatter2_kernel(const u
 #pragma unroll
             for (uint32_t q = 0; q < S2_PER_THREAD; ++q) {
                 const uint32_t i = threadIdx.x + NT * q;
-                if (i < n && !(COMMET_ABLATE & 256)) atomicAdd(&cnt[key[q] >> TILE_BITS], 1u);
+                if (i < n) atomicAdd(&cnt[key[q] >> TILE_BITS], 1u);
             }
         }
         __syncthreads();
@@ -1104,28 +1042,26 @@ __global__ __launch_bounds__(S2_NT, S2P_WAVES) void part_scatter2_kernel(const u
         for (uint32_t i = threadIdx.x; i < nsub; i += NT) {
             const uint32_t c = cnt[i];
             const unsigned long long want = g.packed ? (c + 2) / 3 : c;   // packed: whole groups of three keys
-            gbase[i] = (c && !(COMMET_ABLATE & 128)) ? atomicAdd(&cursor2[((uint64_t) c1 << g.b2) + i], want) : 0ull;
+            gbase[i] = c ? atomicAdd(&cursor2[((uint64_t) c1 << g.b2) + i], want) : 0ull;
         }
         if (whole) {
 #pragma unroll
-            for (uint32_t q = 0; q < S2_PER_THREAD; ++q)
-                if (!(COMMET_ABLATE & 32)) {
-                    const uint32_t sb = key[q] >> TILE_BITS;
-                    sorted[base[sb] + atomicAdd(&fill[sb], 1u)] = key[q] & TILE_MASK;
-                }
+            for (uint32_t q = 0; q < S2_PER_THREAD; ++q) {
+                const uint32_t sb = key[q] >> TILE_BITS;
+                sorted[base[sb] + atomicAdd(&fill[sb], 1u)] = key[q] & TILE_MASK;
+            }
         } else {
 #pragma unroll
             for (uint32_t q = 0; q < S2_PER_THREAD; ++q) {
                 const uint32_t i = threadIdx.x + NT * q;
-                if (i < n && !(COMMET_ABLATE & 32)) {
+                if (i < n) {
                     const uint32_t sb = key[q] >> TILE_BITS;
                     sorted[base[sb] + atomicAdd(&fill[sb], 1u)] = key[q] & TILE_MASK;
                 }
             }
         }
         __syncthreads();
-        if (COMMET_ABLATE & 64) {
-        } else if (g.packed) {
+        if (g.packed) {
             for (uint32_t sb = wave * 2 + (lane >> 5); sb < nsub; sb += (NT / 64) * 2)
                 write_run_p3((uint2 *) out, gbase[sb], sorted, base[sb], cnt[sb], lane & 31u, 32u);
         } else {
@@ -1165,7 +1101,7 @@ __global__ __launch_bounds__(S2_NT, S2P_WAVES) void part_scatter2_packed_kernel(
     __shared__ uint32_t wsum[16];
     __shared__ uint8_t gid[S2_KEYS / 3 + S2P_MAX_SUB + 4];
     const uint32_t nsub = 1u << g.b2;   // <= S2P_MAX_SUB < NT
-    // Slab order (option "s2_swizzle" = G, 0 = dispatch order): see part_scatter2_kernel
+    // Slab order (g.xcd_swizzle = G, 0 = dispatch order): see part_scatter2_kernel
     const uint32_t G = (uint32_t) g.xcd_swizzle;
     uint64_t slab = blockIdx.x;
     if (G > 1) {
@@ -1222,8 +1158,7 @@ __global__ __launch_bounds__(S2_NT, S2P_WAVES) void part_scatter2_packed_kernel(
         }
         hot = __syncthreads_or(hot);
         const uint32_t lane = threadIdx.x & 63u;
-        if (COMMET_ABLATE & 256) {
-        } else if (hot) {
+        if (hot) {
 #pragma unroll
             for (uint32_t q = 0; q < S2_PER_THREAD; q += 4) {
                 const uint32_t b0 = key[q] >> TILE_BITS, b1 = key[q + 1] >> TILE_BITS, b2 = key[q + 2] >> TILE_BITS, b3 = key[q + 3] >> TILE_BITS;
@@ -1255,7 +1190,7 @@ __global__ __launch_bounds__(S2_NT, S2P_WAVES) void part_scatter2_packed_kernel(
         unsigned long long at = 0;
         if (threadIdx.x < nsub) {
             fill[threadIdx.x] = 3u * ex;
-            if (c && !(COMMET_ABLATE & 128)) at = atomicAdd(&cursor2[((uint64_t) c1 << g.b2) + threadIdx.x], (unsigned long long) ((c + 2) / 3));
+            if (c) at = atomicAdd(&cursor2[((uint64_t) c1 << g.b2) + threadIdx.x], (unsigned long long) ((c + 2) / 3));
         }
         __syncthreads();
         auto place = [&](uint32_t kq) {
@@ -1264,8 +1199,7 @@ __global__ __launch_bounds__(S2_NT, S2P_WAVES) void part_scatter2_packed_kernel(
             sorted[slot] = kq & TILE_MASK;
             if (slot == 3u * grp) gid[grp] = (uint8_t) sb;
         };
-        if (COMMET_ABLATE & 32) {
-        } else if (hot) {
+        if (hot) {
 #pragma unroll
             for (uint32_t q = 0; q < S2_PER_THREAD; q += 4) {
                 const uint32_t b0 = key[q] >> TILE_BITS, b1 = key[q + 1] >> TILE_BITS, b2 = key[q + 2] >> TILE_BITS, b3 = key[q + 3] >> TILE_BITS;
@@ -1309,7 +1243,7 @@ __global__ __launch_bounds__(S2_NT, S2P_WAVES) void part_scatter2_packed_kernel(
             }
         }
         __syncthreads();
-        for (uint32_t f = threadIdx.x; f < n_groups && !(COMMET_ABLATE & 64); f += NT) {
+        for (uint32_t f = threadIdx.x; f < n_groups; f += NT) {
             const uint32_t k0 = sorted[3u * f], k1 = sorted[3u * f + 1], k2 = sorted[3u * f + 2];
             out[gbase[gid[f]] + f] = make_uint2(k0 | (k1 << 19), (k1 >> 13) | (k2 << 6));
         }

@@ -32,14 +32,7 @@ namespace commet {
 // and loop-invariant addresses), i.e. 6-7 workgroups.  These kernels are chains of dependent memory round trips and run on
 // workgroups in flight: tq_replay_kernel 5.91 -> 5.20 ms per configs[1] step with the cap alone (tools/kernel_resources.py lists
 // every kernel's registers and what a CU admits).  What does not fit is kept in lanes of a vector register (v_writelane).
-#ifndef COMMET_SGPR_CAP
-#define COMMET_SGPR_CAP 80
-#endif
-#if COMMET_SGPR_CAP
-#define COMMET_SGPRS __attribute__((amdgpu_num_sgpr(COMMET_SGPR_CAP)))
-#else
-#define COMMET_SGPRS
-#endif
+#define COMMET_SGPRS __attribute__((amdgpu_num_sgpr(80)))
 
 struct ReadsView {
     const uint32_t *planes;      // word triples
@@ -211,20 +204,6 @@ __device__ __forceinline__ W psi_a(W key, int k, bool &self_paired)
         return s ? nz : z;
     }
     return ((W) s << h) | (W) y;
-}
-
-// psi_a(key) with the bits below its s field cleared: s fills the address from bit h (+1 for odd k) upwards and
-// h (+1) <= TILE_BITS for every k the bucketed construction takes, so  psi_a_top(key) >> TILE_BITS == psi_a(key) >> TILE_BITS
-// — all a bucket count needs, at a quarter of the arithmetic.
-template <typename W>
-__device__ __forceinline__ W psi_a_top(W key, int k)
-{
-    const int h = k >> 1, odd = k & 1;
-    const uint32_t hmask = (1u << h) - 1u;
-    const uint32_t L = (uint32_t) key & hmask;
-    const uint32_t u = (uint32_t) (key >> (h + odd)) & hmask;
-    const uint32_t v = (~(__brev(L) >> (32 - h))) & hmask;
-    return (W) (u ^ v) << (h + odd);
 }
 
 template <typename W>
@@ -584,21 +563,10 @@ __global__ __launch_bounds__(256) COMMET_SGPRS void search_kernel(ReadsView rv, 
 // windows per request of a cooperative tail fetch (powers of two <= 32).  More per request wastes L2 misses behind the hit
 // that ends the scan; fewer costs round trips.  search_group_kernel on configs[1]: 4 / 8 / 16 / 32 -> 9.29 / 9.25 / 9.25 / 9.37 ms
 // (9.39-9.65 with per-thread tails); search_group8_kernel on a 2 x 50 M-read pair: 8 / 16 / 32 -> 127 / 120.5 / 118.3 ms (136.6).
-#ifndef GROUP_TAIL_WIN
-#define GROUP_TAIL_WIN 16
-#endif
-#ifndef GROUP8_ABLATE
-#define GROUP8_ABLATE 0   // timing ablations (wrong results): 1 no replay, 2 no tails
-#endif
-#ifndef G8_HEAVY
-#define G8_HEAVY 20   // (8 / 12 / 16 / 20 / 24 / 28: 140 / 130 / 105 / 104 / 101 / 104 ms on a 2 x 50 M-read pair) search_group8_kernel: a scan with more lane-a candidates than this walks them itself
-#endif
-#ifndef G8_WAVES
-#define G8_WAVES 1   // search_group8_kernel: waves per SIMD the register allocation is held to (1 = whatever 88 VGPRs allow: five workgroups per CU; 3 / 4 / 5 / 7 / 8: 105.6 / 105.7 / 103.7-106.5 / 108.3 / 110.5 ms per 50 M-read target)
-#endif
-#ifndef GROUP8_TAIL_WIN
-#define GROUP8_TAIL_WIN 32
-#endif
+constexpr int GROUP_TAIL_WIN = 16;
+constexpr int G8_HEAVY = 20;   // (8 / 12 / 16 / 20 / 24 / 28: 140 / 130 / 105 / 104 / 101 / 104 ms on a 2 x 50 M-read pair) search_group8_kernel: a scan with more lane-a candidates than this walks them itself
+constexpr int G8_WAVES = 1;    // search_group8_kernel: waves per SIMD the register allocation is held to (1 = whatever 88 VGPRs allow: five workgroups per CU; 3 / 4 / 5 / 7 / 8: 105.6 / 105.7 / 103.7-106.5 / 108.3 / 110.5 ms per 50 M-read target)
+constexpr int GROUP8_TAIL_WIN = 32;
 // ---------------------------------------------------------------------------
 // search against a GROUP of chunk filters in one pass over the reads.
 // The reference re-scans the search set once per index chunk (index_and_search.cpp:
@@ -989,14 +957,6 @@ __global__ __launch_bounds__(256, G8_WAVES) COMMET_SGPRS void search_group8_kern
     }
     // (2) sparse replay, filter by filter (unrolled: the masks are registers); every thread walks the loop, the ones without
     // work only for its barriers
-    if (GROUP8_ABLATE & 1) {   // keep the gather alive
-        uint32_t n = 0;
-#pragma unroll
-        for (int h = 0; h < MW; ++h)
-#pragma unroll
-            for (int i = 0; i < GS; ++i) n += __popc(fm[h][i]) + 3 * __popc(rm[h][i]);
-        if (n == (uint32_t) t) found = true;   // (never with the t the bench uses... wrong results anyway)
-    }
     // (several jobs) what a job leaves behind: its found flags, one ballot word per 64 reads, and its chunks' counters
     auto end_job = [&](int first, int end) {
         if (al.ids) {                                     // list form (a ragged set's reads in order of their window counts): one atomic OR per found read
@@ -1021,7 +981,7 @@ __global__ __launch_bounds__(256, G8_WAVES) COMMET_SGPRS void search_group8_kern
 #pragma unroll
         for (int strand = 0; strand < 2; ++strand) {
             int seen = 0, next_ok = 0;
-            bool dead = !active || found || (GROUP8_ABLATE & 1);
+            bool dead = !active || found;
             auto probe_bcd = [&](W wh, W wl) -> bool {
                 W ka, kb;
                 if (strand == 0) ka = T::brev(wh) >> sh, kb = T::brev(wl) >> sh;
@@ -1108,7 +1068,7 @@ __global__ __launch_bounds__(256, G8_WAVES) COMMET_SGPRS void search_group8_kern
             }
             // windows behind the gathered ones, after a first full hit only, GROUP8_TAIL_WIN at a time
             for (int qb = max(pe + 1, next_ok);; qb += GROUP8_TAIL_WIN) {   // (uniform trip count: every thread takes part in the barriers)
-                const bool want = !(GROUP8_ABLATE & 2) && !found && !dead && seen >= 1 && qb <= last && qb + (t - seen - 1) * k <= last;
+                const bool want = !found && !dead && seen >= 1 && qb <= last && qb + (t - seen - 1) * k <= last;
                 if (threadIdx.x == 0) tail_n = 0;
                 if (!__syncthreads_or(want)) break;
                 if (want) {

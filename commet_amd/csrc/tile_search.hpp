@@ -26,28 +26,13 @@
 #include "kernels.hpp"
 #include "index_part.hpp"   // block_scan
 
-#ifndef COMMET_TQ_ABLATE
-#define COMMET_TQ_ABLATE 0   // timing ablations exist only in builds made with -DCOMMET_TQ_ABLATE=<mask> (512: no gather, 1024: no replay, 262144 / 524288: plane-B probes / tail gathers folded into an L2-resident window)
-#endif
-
 namespace commet {
 
-#ifndef TQ_SWEEP_U
-#define TQ_SWEEP_U 2     // replay, step (2): candidates per thread and round of the balanced sweep (1 / 2 / 4: 4.52 / 4.54 / 4.59 ms)
-#endif
-#ifndef TQ_COLLECT_U
-#define TQ_COLLECT_U 8   // replay, step (1): flat records per lane whose loads are in flight together (1 / 2 / 4 / 8: 5.20 / 4.82 / 4.68 / 4.63 ms)
-#endif
-#ifndef COMMET_TQ_PIECE
-#define COMMET_TQ_PIECE 256
-#endif
-#ifndef TQ_PASS_LIST
-#define TQ_PASS_LIST 1   // replay: full hits of the light scans posted as a list and ORed into the masks array behind the sweep (0: a second mask array)
-#endif
-#ifndef TQ_HIT_CAP
-#define TQ_HIT_CAP 1024  // ... of at most this many hits per piece; more: every scan of the piece walks its own candidates
-#endif
-constexpr uint32_t TQ_PIECE = COMMET_TQ_PIECE;   // reads per piece = threads of the replay workgroup (1024: 9.5 ms, 512: 7.1, 256: 6.8 on configs[1] in round 2; round 5: 256 / 128 / 64: 4.54 / 4.87 / 5.51)
+constexpr int TQ_SWEEP_U = 2;      // replay, step (2): candidates per thread and round of the balanced sweep (1 / 2 / 4: 4.52 / 4.54 / 4.59 ms)
+constexpr int TQ_COLLECT_U = 8;    // replay, step (1): flat records per lane whose loads are in flight together (1 / 2 / 4 / 8: 5.20 / 4.82 / 4.68 / 4.63 ms)
+constexpr int TQ_HIT_CAP = 1024;   // replay: full hits of the light scans posted as a list and ORed into the masks array behind the sweep, at most this
+                                   // many per piece; more: every scan of the piece walks its own candidates
+constexpr uint32_t TQ_PIECE = 256;        // reads per piece = threads of the replay workgroup (1024: 9.5 ms, 512: 7.1, 256: 6.8 on configs[1] in round 2; round 5: 256 / 128 / 64: 4.54 / 4.87 / 5.51)
 constexpr uint32_t TQ_MAX_LEN = 8000;     // reads of a set that takes the tiled search are shorter: 256 x (len / 32 + 2) triples of a piece < 2^16 (rd_ext)
 constexpr int      TQ_MAX_WIN = 255;      // first-hit windows per read (up to eight mask words; qwho has eight bits for the window, and a tile — one slice's share
                                           // of a piece of 256 reads, all of it when the reads are poly-A — must stay below 2^16 records: tlen is 16 bits)
@@ -256,10 +241,10 @@ __global__ __launch_bounds__(256) void tq_bounds_kernel(const unsigned long long
 // rounds wrote sit in LDS.  History: written record by record straight from the window loop, each 4-byte store reached HBM on its
 // own (18.7 GB written for 3 GB of records, 11 ms per 10 M-read set); sorted in LDS but written slice by slice — a wave per slice,
 // each with a dependent 8-byte load of its tile's start and ~24 of 64 lanes busy — 5.6 ms; flat, two rounds per piece 2.5 ms.
-#ifndef COMMET_TQ_FILL_CAP
-#define COMMET_TQ_FILL_CAP 9600   // a whole piece of 100-bp reads at k = 32, t = 2 (256 x 37 records) in ONE round: 1.94 ms per 10 M-read set against 2.59 with 6144 (two rounds of 128 reads) and 2.58 with 4800; 81 KB of LDS, two workgroups per CU
-#endif
-constexpr uint32_t TQ_FILL_CAP = COMMET_TQ_FILL_CAP;    // records sorted per round: rpr * (first-hit windows per read) <= TQ_FILL_CAP
+// records sorted per round: rpr * (first-hit windows per read) <= TQ_FILL_CAP.  9600 = a whole piece of 100-bp reads at k = 32, t = 2
+// (256 x 37 records) in ONE round: 1.94 ms per 10 M-read set against 2.59 with 6144 (two rounds of 128 reads) and 2.58 with 4800;
+// 81 KB of LDS, two workgroups per CU
+constexpr uint32_t TQ_FILL_CAP = 9600;
 template <typename W>
 __global__ __launch_bounds__(256) void tq_fill_kernel(ReadsView rv, int k, int t, int sbits, uint32_t n_slices, uint32_t n_pieces,
                                                       uint32_t rpr, const uint32_t *__restrict__ tstart,
@@ -418,7 +403,6 @@ __global__ __launch_bounds__(TQ_PIECE) COMMET_SGPRS void tq_replay_kernel(ReadsV
     auto mask_at = [&](int c, int strand, int h, uint32_t rd) -> uint32_t & { return masks[(((c * 2 + strand) * MW) + h) * TQ_PIECE + rd]; };
     for (uint32_t i = threadIdx.x; i < GS * 2 * MW * TQ_PIECE; i += TQ_PIECE) masks[i] = 0;
     __syncthreads();
-#if !(COMMET_TQ_ABLATE & 512)
     // (1) the piece's results.  Wave w takes slices w, w + 16, ... in batches of 64 tiles: every lane fetches the bounds of
     // one tile, the batch's records then form one flat list that the wave walks 64 at a time (tile of a record: by
     // counting the tile ends at or below it) — independent loads, no chain of small dependent ones.
@@ -485,7 +469,6 @@ __global__ __launch_bounds__(TQ_PIECE) COMMET_SGPRS void tq_replay_kernel(ReadsV
             }
         }
     }
-#endif
     __syncthreads();
     // (2) planes B, C, D for the lane-a candidates, balanced over the workgroup.  A read has ~11 candidates on average but
     // the count varies from lane to lane, and every probe is a dependent HBM round trip; walking them per read leaves
@@ -494,16 +477,13 @@ __global__ __launch_bounds__(TQ_PIECE) COMMET_SGPRS void tq_replay_kernel(ReadsV
     // round, all lanes busy.  Survivors (A & B) are collected in a second mask array and go through planes C and D the same
     // way; what is left are the full four-lane hits.
     // The full hits (A & B & C & D) of the light scans are found by whichever thread the sweep hands the candidate to, and are few (chance
-    // hits; reads that share sequence are heavy scans and walk their own candidates).  PASS_LIST: they are posted as a list of
+    // hits; reads that share sequence are heavy scans and walk their own candidates).  They are posted as a list of
     // TQ_HIT_CAP words and, behind the sweep, ORed into the masks array itself, which nobody reads any more by then — the second
     // mask array (12 KiB with three mask words: five workgroups per CU instead of eight, 6.4 against 4.5 ms per configs[1]-sized
     // step on 50-150-bp reads) is gone.  A piece with more hits than the list holds lets every scan walk its own candidates, as
     // heavy scans do: exact, only slower.
-    constexpr bool PASS_LIST = TQ_PASS_LIST != 0;
-    __shared__ uint32_t pass_arr[PASS_LIST ? 1 : GS * 2 * MW * TQ_PIECE];
-    __shared__ uint32_t hits[PASS_LIST ? TQ_HIT_CAP : 1];
+    __shared__ uint32_t hits[TQ_HIT_CAP];
     __shared__ uint32_t hit_n;
-    uint32_t *const pass = PASS_LIST ? masks : pass_arr;
     // where every read of the piece lies and how long it is: (first triple - the piece's first triple) | length << 16.  A candidate is
     // probed by whichever thread the sweep hands it to, a tail window by whichever thread its number falls on, and on a set of many read
     // lengths the owner's extent is two more loads (goff) in front of every such probe's chain; the piece's 256 extents fit 1 KiB
@@ -537,10 +517,8 @@ __global__ __launch_bounds__(TQ_PIECE) COMMET_SGPRS void tq_replay_kernel(ReadsV
 #pragma unroll
     for (int i = 0; i < NS; ++i)
 #pragma unroll
-        for (int h = 0; h < MW; ++h) {
+        for (int h = 0; h < MW; ++h)
             if (!active || (i >> 1) >= fg.g) word_at(masks, i, h, threadIdx.x) = 0;   // reads that are not searched have no candidates
-            if (!PASS_LIST) word_at(pass, i, h, threadIdx.x) = 0;
-        }
     __syncthreads();
     rd_ext[threadIdx.x] = (r < rv.n) ? ((uint32_t) (my_t0 - piece_t0) & 0xFFFFu) | (my_len << 16) : 0u;   // (first read before the sweep's first barrier)
     // A read that shares sequence with the index set has a lane-a bit on (nearly) every window of one strand; the
@@ -562,7 +540,6 @@ __global__ __launch_bounds__(TQ_PIECE) COMMET_SGPRS void tq_replay_kernel(ReadsV
             for (int h = 0; h < MW; ++h) word_at(masks, i, h, threadIdx.x) = 0;   // (the sweep's first barrier comes before anyone else reads them)
         }
     }
-    const bool heavy = hv != 0;
     // words of another read of the piece around window end q
     const uint32_t *const piece_planes = rv.planes + 3 * piece_t0;
     auto keys_of = [&](uint32_t owner, int strand, int q, W &ka, W &kb) {
@@ -639,44 +616,35 @@ __global__ __launch_bounds__(TQ_PIECE) COMMET_SGPRS void tq_replay_kernel(ReadsV
         }
         __syncthreads();
     };
-    if (!(COMMET_TQ_ABLATE & 1024)) {
-        // plane B of every candidate; the one in nine that passes goes through planes C and D at once (two independent
-        // loads).  A second balanced sweep for C / D (1.2 K survivors per piece) cost more in prefix sums and barriers
-        // than the divergence it avoided.
-        sweep(masks,
-              [&](int i, W, W kb, uint32_t &bit) -> const uint32_t * {
-                  bit = (uint32_t) kb & 31u;
-                  if (COMMET_TQ_ABLATE & 262144) return fg.slot0 + (uint64_t) (i >> 1) * fg.slot_words + fg.plane_words + ((kb >> 5) & 0x1FFFFu);   // timing bound: plane B served from L2
-                  return fg.slot0 + (uint64_t) (i >> 1) * fg.slot_words + fg.plane_words + (kb >> 5);
-              },
-              [&](uint32_t owner, int i, int h, uint32_t b, W ka, W kb) {
-                  const uint32_t *pc = fg.slot0 + (uint64_t) (i >> 1) * fg.slot_words + 2 * fg.plane_words, *pd = pc + fg.plane_words;
-                  const uint32_t vc = pc[(ka ^ kb) >> 5], vd = pd[(ka | kb) >> 5];
-                  if ((vc >> ((uint32_t) (ka ^ kb) & 31u)) & (vd >> ((uint32_t) (ka | kb) & 31u)) & 1u) {
-                      if (PASS_LIST) {
-                          const uint32_t at = atomicAdd(&hit_n, 1u);
-                          if (at < hit_cap) hits[at] = owner | ((uint32_t) i << 8) | ((uint32_t) h << 12) | (b << 16);
-                      } else {
-                          atomicOr(&word_at(pass, i, h, owner), 1u << b);
-                      }
-                  }
-              });
-    }
-    bool all_self = false;              // PASS_LIST: the list overflowed — every scan walks its own lane-a candidates (am[])
-    if (PASS_LIST) {                    // (behind the sweep's last barrier: nobody reads the masks any more)
+    // plane B of every candidate; the one in nine that passes goes through planes C and D at once (two independent
+    // loads).  A second balanced sweep for C / D (1.2 K survivors per piece) cost more in prefix sums and barriers
+    // than the divergence it avoided.
+    sweep(masks,
+          [&](int i, W, W kb, uint32_t &bit) -> const uint32_t * {
+              bit = (uint32_t) kb & 31u;
+              return fg.slot0 + (uint64_t) (i >> 1) * fg.slot_words + fg.plane_words + (kb >> 5);
+          },
+          [&](uint32_t owner, int i, int h, uint32_t b, W ka, W kb) {
+              const uint32_t *pc = fg.slot0 + (uint64_t) (i >> 1) * fg.slot_words + 2 * fg.plane_words, *pd = pc + fg.plane_words;
+              const uint32_t vc = pc[(ka ^ kb) >> 5], vd = pd[(ka | kb) >> 5];
+              if ((vc >> ((uint32_t) (ka ^ kb) & 31u)) & (vd >> ((uint32_t) (ka | kb) & 31u)) & 1u) {
+                  const uint32_t at = atomicAdd(&hit_n, 1u);
+                  if (at < hit_cap) hits[at] = owner | ((uint32_t) i << 8) | ((uint32_t) h << 12) | (b << 16);
+              }
+          });
+    // (behind the sweep's last barrier: nobody reads the masks any more) the full hits into the masks array
 #pragma unroll
-        for (int i = 0; i < NS; ++i)
+    for (int i = 0; i < NS; ++i)
 #pragma unroll
-            for (int h = 0; h < MW; ++h) word_at(masks, i, h, threadIdx.x) = 0;
-        __syncthreads();
-        const uint32_t nh = hit_n;
-        all_self = nh > hit_cap;
-        for (uint32_t e = threadIdx.x; e < min(nh, hit_cap); e += TQ_PIECE) {
-            const uint32_t x = hits[e];
-            atomicOr(&word_at(masks, (int) ((x >> 8) & 15u), (int) ((x >> 12) & 15u), x & 255u), 1u << (x >> 16));
-        }
-        __syncthreads();
+        for (int h = 0; h < MW; ++h) word_at(masks, i, h, threadIdx.x) = 0;
+    __syncthreads();
+    const uint32_t nh = hit_n;
+    const bool all_self = nh > hit_cap;   // the list overflowed: every scan walks its own lane-a candidates (am[])
+    for (uint32_t e = threadIdx.x; e < min(nh, hit_cap); e += TQ_PIECE) {
+        const uint32_t x = hits[e];
+        atomicOr(&word_at(masks, (int) ((x >> 8) & 15u), (int) ((x >> 12) & 15u), x & 255u), 1u << (x >> 16));
     }
+    __syncthreads();
     // (3) the reference's control flow (search_reads.h:45-83) on the full hits of this thread's read: per chunk, strand 0
     // then strand 1; greedy non-overlapping hits; the windows behind the first-hit ones are probed only for a scan that
     // already has a hit (exact pruning, see search_kernel).  Those tails are fetched by the whole workgroup: the threads
@@ -684,10 +652,9 @@ __global__ __launch_bounds__(TQ_PIECE) COMMET_SGPRS void tq_replay_kernel(ReadsV
     // round trip and ~50 instructions per window with every lane busy, where a thread fetching its own 32 windows
     // (a rolling window, four batches of eight loads) kept the other lanes of its wave waiting through
     // ~1500 instructions and four round trips (1.8 ms of this kernel's 6.1 on configs[1]).
-    // (PASS_LIST: the hit list is dead by now; the tails' request / answer arrays take its place)
-    static_assert(!PASS_LIST || TQ_HIT_CAP >= 2 * TQ_PIECE, "the tails' arrays alias the hit list");
-    __shared__ uint32_t tail_arr[PASS_LIST ? 1 : 2 * TQ_PIECE];
-    uint32_t *const tail_req = PASS_LIST ? hits : tail_arr, *const tail_bits = tail_req + TQ_PIECE;
+    // (the hit list is dead by now; the tails' request / answer arrays take its place)
+    static_assert(TQ_HIT_CAP >= 2 * TQ_PIECE, "the tails' arrays alias the hit list");
+    uint32_t *const tail_req = hits, *const tail_bits = tail_req + TQ_PIECE;
     __shared__ uint32_t tail_n;
     int found_chunk = -1;
     bool found_job0 = false, found_job1 = false;       // (two jobs in one scan)
@@ -696,18 +663,17 @@ __global__ __launch_bounds__(TQ_PIECE) COMMET_SGPRS void tq_replay_kernel(ReadsV
         const int last = (int) my_len - 1;
         const int pe = last - (t - 1) * k;
         const int q0 = k - 1;
-        const bool scanning = active && !(COMMET_TQ_ABLATE & (1024 | 8192));
-        bool found = false;
+                bool found = false;
         for (int i = 0; i < 2 * fg.g; ++i) {   // (uniform)
             if (multi && i == 2) found_job0 = found, found = false;    // chunk 1 opens the second job: nothing carries over
             const int strand = i & 1;
             const uint32_t *pb = fg.slot0 + (uint64_t) (i >> 1) * fg.slot_words + fg.plane_words;
             const uint32_t *pc = pb + fg.plane_words, *pd = pc + fg.plane_words;
             int seen = 0, next_ok = 0;
-            bool dead = !scanning || found;
+            bool dead = !active || found;
             for (int h = 0; h < MW && !found && !dead; ++h) {
                 const bool hscan = ((hv >> i) & 1u) || all_self;
-                uint32_t m = pass[((i * MW) + h) * TQ_PIECE + threadIdx.x];    // light scans: full hits (step 2)
+                uint32_t m = masks[((i * MW) + h) * TQ_PIECE + threadIdx.x];    // light scans: full hits (step 2)
                 if (hscan) {                                                     // heavy scans: lane-a candidates, probed here
                     m = 0;
 #pragma unroll
@@ -745,9 +711,8 @@ __global__ __launch_bounds__(TQ_PIECE) COMMET_SGPRS void tq_replay_kernel(ReadsV
                 }
             }
             // windows behind the first-hit ones, 32 at a time, for the scans that have a hit but not yet t of them
-            const bool tails_on = !(COMMET_TQ_ABLATE & 32768) && !((COMMET_TQ_ABLATE & 65536) && heavy) && !((COMMET_TQ_ABLATE & 131072) && !heavy);
             for (int qb = max(pe + 1, next_ok);; qb += 32) {   // (uniform trip count: every thread takes part in the barriers)
-                const bool want = tails_on && !found && !dead && seen >= 1 && qb <= last && qb + (t - seen - 1) * k <= last;
+                const bool want = !found && !dead && seen >= 1 && qb <= last && qb + (t - seen - 1) * k <= last;
                 if (threadIdx.x == 0) tail_n = 0;
                 if (!__syncthreads_or(want)) break;
                 if (want) {
@@ -767,8 +732,7 @@ __global__ __launch_bounds__(TQ_PIECE) COMMET_SGPRS void tq_replay_kernel(ReadsV
                     if (!it.window((uint32_t) q & 31u, k, kmask, wh, wl)) continue;   // a base that is not ACGT: no k-mer here
                     const W ka = strand ? (W) (~wh & kmask) : (W) (T::brev(wh) >> sh);
                     const W addr = psi_a<W>(ka, k);
-                    const uint32_t v = (COMMET_TQ_ABLATE & 524288) ? fg.il_a[(uint64_t) ((addr >> 5) & 0x1FFFFu) * GS + (uint32_t) (i >> 1)]   // timing bound: tails served from L2
-                                                                   : fg.il_a[(uint64_t) (addr >> 5) * GS + (uint32_t) (i >> 1)];
+                    const uint32_t v = fg.il_a[(uint64_t) (addr >> 5) * GS + (uint32_t) (i >> 1)];
                     if ((v >> ((uint32_t) addr & 31u)) & 1u) atomicOr(&tail_bits[owner], 1u << w);
                 }
                 __syncthreads();

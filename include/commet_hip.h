@@ -246,8 +246,6 @@ int commet_index_many_and_search(commet_ctx *ctx, int n_jobs, const commet_reads
  *   index_mode (0/1/2)   0 auto, 1 atomic-OR kernel, 2 bucketed (LDS-tile) construction
  *   part_min_kmers       auto mode: chunks with fewer k-mers take the atomic kernel
  *   index_lanes (1/2)    2 = the chunks of a group are built on two streams (default)
- *   lane_stagger (0/1)   two lanes: the second lane's chunk starts when the first lane's scatter1 is through (default 1), so that
- *                        its VALU-bound phases run beside the first chunk's HBM-bound ones; 0 = both chunks start together
  *   drop_workspaces      frees the scatter workspaces (the next bucketed index build allocates them again)
  *   chunk_group (1..8)   chunk filters searched per pass over a set (1 = the reference's order; 5..8 only
  *                        for read sets with at most 255 first-hit windows per read — reads of up to 318 bases at k = 32, t = 2 —, else 4)
@@ -278,11 +276,9 @@ int commet_index_many_and_search(commet_ctx *ctx, int n_jobs, const commet_reads
  *                        narrowest masks its reads fit (the list starts with the reads of most windows), 1 = one launch at the set's width
  *   tq_hit_cap           TEST HOOK of the tiled search's replay: full hits a piece of 256 reads may post for its owners (default and
  *                        at most 1024; beyond it every scan of the piece walks its own candidates — same bits, slower); 0 forces that path
- *   tq_parts (1..16)     tiled search in parts, the replay of one beside the probe of the next (default 1: measured slower)
  *   part_no_uni (0/1)    1 = never take the fixed-read-length fast path of hist / scatter1 (nor the item list of ragged sets)
  *   part_list (0/1)      ragged sets (reads of several lengths): 0 = hist / scatter1 walk the chunk's item list (written out once per
  *                        chunk; the words of the coming round's items prefetched as on fixed-length sets), 1 = the round planner
- *   part_b1, s2_swizzle  radix split / scatter2 slab order of the bucketed construction
  *   kernel_timing (0/1)  time every kernel launch of commet_index_and_search (commet_kernel_times)
  *   max_kmer             TEST HOOK: k-mers per index chunk instead of the reference's constant (0 = reference; the
  *                        results are then those of a reference built with that constant, index_and_search.cpp:73) */

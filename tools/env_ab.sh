@@ -1,8 +1,8 @@
 # Run-time A/Bs on the GPU box: bench.py under every value of one environment knob (read once in commet_create, capi/context.hpp),
 # one line per value with the step and the kernels' times.
 #   bash tools/env_ab.sh <VARIABLE> <value> [<value> ...] [-- <bench.py args>]
-#   e.g.  bash tools/env_ab.sh COMMET_TQ_WPX 16 32 64 128                                            (probe workgroups per XCD)
-#         bash tools/env_ab.sh COMMET_TQ_PARTS 1 2 3 4
+#   e.g.  bash tools/env_ab.sh COMMET_TILED 1 2                                                      (gather kernels / tiled search)
+#         bash tools/env_ab.sh COMMET_SPARSE_SEARCH 0 1 2
 #         bash tools/env_ab.sh COMMET_SLICE_WIDE 1 2 -- --reads 20000000 --read-len 150 -k 21 -t 5   (configs[4]: narrow tables / wide rows)
 #         bash tools/env_ab.sh COMMET_INDEX_LANES 1 2
 set -e
