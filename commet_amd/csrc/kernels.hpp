@@ -45,6 +45,15 @@ struct FilterView {
     uint32_t *a, *b, *c, *d;     // bit-planes, 2^k bits each
 };
 
+// the filters of a group of chunks (search_group_kernel and the kernels after it)
+struct FilterGroupView {
+    const uint32_t *il_a;        // interleaved A planes, stride GS words
+    const uint32_t *slot0;       // first filter slot (4 planes); slot i at slot0 + i * slot_words
+    uint64_t        slot_words;  // words per slot (4 * plane_words)
+    uint64_t        plane_words;
+    int             g;           // chunks in the group (<= GS)
+};
+
 template <typename W> struct KeyTraits;
 template <> struct KeyTraits<uint32_t> {
     static constexpr int BITS = 32;
@@ -123,11 +132,12 @@ struct SearchLane {
     bool     active, in_range;
 };
 
+// (block0: the launch's workgroup 0 stands for workgroup block0 of the set, tq_replay_kernel's launches by parts)
 __device__ __forceinline__ SearchLane search_lane(const ReadsView &rv, const ActiveList &al, const uint64_t *__restrict__ sel,
-                                                  const uint64_t *__restrict__ tags)
+                                                  const uint64_t *__restrict__ tags, uint32_t block0 = 0)
 {
     SearchLane me;
-    const uint64_t i = blockIdx.x * 256ull + threadIdx.x;
+    const uint64_t i = ((uint64_t) blockIdx.x + block0) * 256ull + threadIdx.x;
     if (al.ids) {
         me.active = i < (uint64_t) *al.n;
         me.r = me.active ? (uint64_t) al.ids[i] : rv.n;      // (rv.n: no read)
@@ -274,6 +284,12 @@ template <> struct ItemWords<uint64_t> {
         return ext(va, s, mask) == mask;
     }
 };
+
+}  // namespace commet
+
+#include "search_replay.hpp"   // the reference's control flow, shared by the gather-and-replay search kernels
+
+namespace commet {
 
 // ---------------------------------------------------------------------------
 // pack: ASCII -> {hi, lo, valid} planes, per-read complete-k-mer counts.
@@ -565,7 +581,7 @@ __global__ __launch_bounds__(256) COMMET_SGPRS void search_kernel(ReadsView rv, 
 // (9.39-9.65 with per-thread tails); search_group8_kernel on a 2 x 50 M-read pair: 8 / 16 / 32 -> 127 / 120.5 / 118.3 ms (136.6).
 constexpr int GROUP_TAIL_WIN = 16;
 constexpr int G8_HEAVY = 20;   // (8 / 12 / 16 / 20 / 24 / 28: 140 / 130 / 105 / 104 / 101 / 104 ms on a 2 x 50 M-read pair) search_group8_kernel: a scan with more lane-a candidates than this walks them itself
-constexpr int G8_WAVES = 1;    // search_group8_kernel: waves per SIMD the register allocation is held to (1 = whatever 88 VGPRs allow: five workgroups per CU; 3 / 4 / 5 / 7 / 8: 105.6 / 105.7 / 103.7-106.5 / 108.3 / 110.5 ms per 50 M-read target)
+constexpr int G8_WAVES = 1;    // search_group8_kernel: waves per SIMD the register allocation is held to (1 = not held: 101-105 VGPRs with two mask words — four workgroups per CU —, 135-141 with three or four — three —, 75-85 with six or eight, tools/kernel_resources.py; 3 / 4 / 5 / 7 / 8: 105.6 / 105.7 / 103.7-106.5 / 108.3 / 110.5 ms per 50 M-read target)
 constexpr int GROUP8_TAIL_WIN = 32;
 // ---------------------------------------------------------------------------
 // search against a GROUP of chunk filters in one pass over the reads.
@@ -579,14 +595,6 @@ constexpr int GROUP8_TAIL_WIN = 32;
 // strand, on the masks, probing planes B, C, D of that chunk only on lane-a hits.
 // counters: per chunk i of the group {scanned_i, found_i} at counters[i * cstride].
 // ---------------------------------------------------------------------------
-struct FilterGroupView {
-    const uint32_t *il_a;        // interleaved A planes, stride GS words
-    const uint32_t *slot0;       // first filter slot (4 planes); slot i at slot0 + i * slot_words
-    uint64_t        slot_words;  // words per slot (4 * plane_words)
-    uint64_t        plane_words;
-    int             g;           // chunks in the group (<= GS)
-};
-
 template <int GS> struct GroupWords;
 template <> struct GroupWords<2> {
     uint32_t x[2];
@@ -636,14 +644,13 @@ __global__ __launch_bounds__(256) COMMET_SGPRS void search_group_kernel(ReadsVie
     __shared__ uint32_t wg_len[256];
     wg_t0[threadIdx.x] = t0, wg_len[threadIdx.x] = len;      // (first read behind a barrier)
     const uint32_t *p = rv.planes + 3 * t0;
-    const int sh = T::BITS - k;
-    const W mask = (k == T::BITS) ? ~(W) 0 : (((W) 1 << k) - 1);
+    const KeyCtx<W> kc(k);
+    const int sh = kc.sh;
+    const W mask = kc.mask;
     const bool staged = rw_nw && !COUNT;
     auto getw = [&](uint32_t i) -> uint32_t { return staged ? rw[i * 256u + threadIdx.x] : p[i]; };
-    // Pruning (exact, see search_kernel): with `seen` hits a window ending at q matters only if
-    // q + (t-seen-1)*k <= len-1.  The gather therefore covers the windows that can be a FIRST hit,
-    // q <= pe = len-1-(t-1)*k (all of them in COUNT builds); later windows are needed only after a real
-    // 4-lane hit and are then fetched by the whole workgroup (below) or, in COUNT builds, one by one in the replay.
+    // The gather covers the windows that can be a FIRST hit, q <= pe (search_replay.hpp; all of them in COUNT builds); later windows
+    // are fetched by the whole workgroup after a real 4-lane hit (cooperative_tail) or, in COUNT builds, one by one in the replay.
     const int last = (int) len - 1;
     const int pe = COUNT ? last : last - (t - 1) * k;
     if (active) {
@@ -693,97 +700,41 @@ __global__ __launch_bounds__(256) COMMET_SGPRS void search_group_kernel(ReadsVie
         // (2) Sparse replay of the reference control flow per chunk (search_reads.h:45-83): the reference probes a window
         // iff its k bases are ACGT (that is what a gathered mask bit stands on) and it ends at least k bases after the
         // strand's last full hit.  A window whose lane-a bit is clear can never be a hit, so only the set mask bits are
-        // visited, in order, with that rule; their keys come straight from the read's words (no rolling over the bases
-        // in between).  Every thread walks the loops (the ones without work only for the barriers of the tails).
+        // visited, in order, with that rule (StrandScan::walk); their keys come straight from the read's words (no rolling over
+        // the bases in between).  Every thread walks the loops (the ones without work only for the barriers of the tails).
         __shared__ uint32_t tail_req[256], tail_bits[256];
         __shared__ uint32_t tail_n;
         for (int i = 0; i < fg.g; ++i) {   // (uniform)
-            const uint32_t *pb = fg.slot0 + (uint64_t) i * fg.slot_words + fg.plane_words;
-            const uint32_t *pc = pb + fg.plane_words;
-            const uint32_t *pd = pc + fg.plane_words;
+            const PlanesBCD f = planes_bcd(fg, i);
             for (int strand = 0; strand < 2; ++strand) {
-                int seen = 0, next_ok = 0;
-                bool dead = !active || found;
-                auto probe_bcd = [&](W wh, W wl) -> bool {
+                StrandScan sc(active && !found);
+                ItemWords<W> it;
+                auto probe_loaded = [&](int q) -> bool {   // (it: the read's words around q; complete: a lane-a bit stands for a complete window)
                     W ka, kb;
-                    if (strand == 0) ka = T::brev(wh) >> sh, kb = T::brev(wl) >> sh;
-                    else ka = ~wh & mask, kb = ~wl & mask;
-                    return test_bit<W>(pb, kb) && test_bit<W>(pc, ka ^ kb) && test_bit<W>(pd, ka | kb);
+                    (void) kc.window_keys(it, q, strand, ka, kb);
+                    return probe_bcd_chain<W>(f, ka, kb);
                 };
-                for (uint32_t w = 0; (int) (w * 32u) <= pe && !found && !dead; ++w) {
-                    uint32_t m = mask_at(i, strand, w);
+                for (uint32_t w = 0; (int) (w * 32u) <= pe && sc.open(); ++w) {
+                    const uint32_t m = mask_at(i, strand, w);
                     if (!m) continue;
-                    ItemWords<W> it;
                     it.load_with(getw, w);
-                    while (m && !found) {
-                        const uint32_t j = (uint32_t) __ffs((int) m) - 1u;
-                        m &= m - 1u;
-                        const int q = (int) (32u * w + j);
-                        if (q < next_ok) continue;
-                        if (q + (t - seen - 1) * k > last) {
-                            dead = true;
-                            break;
-                        }
-                        W wh, wl;
-                        (void) it.window(j, k, mask, wh, wl);   // valid: the gather saw a complete window here
-                        if (probe_bcd(wh, wl)) {
-                            ++seen;
-                            next_ok = q + k;
-                            if (seen >= t) found = true;
-                        }
-                    }
+                    sc.walk(m, (int) (32u * w), t, k, last, probe_loaded);
                 }
-                // Windows behind the gathered ones matter only after a first full hit (pruning, see above).  Their lane-a
-                // bits are fetched by the whole workgroup, GROUP_TAIL_WIN windows per request: the threads that need a tail
-                // post (read, first window end), thread p takes window p % GROUP_TAIL_WIN of request p / GROUP_TAIL_WIN —
-                // one round trip with every lane busy (see tq_replay_kernel); then only the set ones are probed.
-                for (int qb = max(pe + 1, next_ok);; qb += GROUP_TAIL_WIN) {   // (uniform trip count)
-                    const bool want = !found && !dead && seen >= 1 && qb <= last && qb + (t - seen - 1) * k <= last;
-                    if (threadIdx.x == 0) tail_n = 0;
-                    if (!__syncthreads_or(want)) break;
-                    if (want) {
-                        tail_req[atomicAdd(&tail_n, 1u)] = threadIdx.x | ((uint32_t) qb << 8);
-                        tail_bits[threadIdx.x] = 0;
-                    }
-                    __syncthreads();
-                    const uint32_t n_pairs = tail_n * (uint32_t) GROUP_TAIL_WIN;
-                    for (uint32_t pr = threadIdx.x; pr < n_pairs; pr += 256) {
-                        const uint32_t rq = tail_req[pr / GROUP_TAIL_WIN], owner = rq & 255u, wi = pr % GROUP_TAIL_WIN;
-                        const int q = (int) (rq >> 8) + (int) wi;
-                        if (q >= (int) wg_len[owner]) continue;
+                // the tail, GROUP_TAIL_WIN windows per request; an owner's words come from its staged copy where there is one
+                cooperative_tail<W, GROUP_TAIL_WIN, GS>(
+                    sc, tail_req, tail_bits, tail_n, kc, strand, t, pe, last, fg.il_a, i,
+                    [&](uint32_t owner, int q, W &wh, W &wl) -> bool {
+                        if (q >= (int) wg_len[owner]) return false;
                         const uint32_t *op = rv.planes + 3 * wg_t0[owner];
-                        ItemWords<W> it;
-                        it.load_with([&](uint32_t x) -> uint32_t { return staged ? rw[x * 256u + owner] : op[x]; }, (uint32_t) q >> 5);
-                        W wh, wl;
-                        if (!it.window((uint32_t) q & 31u, k, mask, wh, wl)) continue;   // a base that is not ACGT: no k-mer here
-                        const W ka = strand ? (W) (~wh & mask) : (W) (T::brev(wh) >> sh);
-                        const W addr = psi_a<W>(ka, k);
-                        const uint32_t v = fg.il_a[(uint64_t) (addr >> 5) * GS + i];
-                        if ((v >> ((uint32_t) addr & 31u)) & 1u) atomicOr(&tail_bits[owner], 1u << wi);
-                    }
-                    __syncthreads();
-                    if (want) {
-                        uint32_t m = tail_bits[threadIdx.x];
-                        while (m && !found) {
-                            const int q = qb + (__ffs((int) m) - 1);
-                            m &= m - 1u;
-                            if (q < next_ok) continue;
-                            if (q + (t - seen - 1) * k > last) {
-                                dead = true;
-                                break;
-                            }
-                            ItemWords<W> it;
-                            it.load_with(getw, (uint32_t) q >> 5);
-                            W wh, wl;
-                            (void) it.window((uint32_t) q & 31u, k, mask, wh, wl);
-                            if (probe_bcd(wh, wl)) {
-                                ++seen;
-                                next_ok = q + k;   // the next complete window ends k bases later
-                                if (seen >= t) found = true;
-                            }
-                        }
-                    }
-                }
+                        ItemWords<W> ot;
+                        ot.load_with([&](uint32_t x) -> uint32_t { return staged ? rw[x * 256u + owner] : op[x]; }, (uint32_t) q >> 5);
+                        return ot.window((uint32_t) q & 31u, k, mask, wh, wl);
+                    },
+                    [&](int q) -> bool {
+                        it.load_with(getw, (uint32_t) q >> 5);
+                        return probe_loaded(q);
+                    });
+                found = found || sc.found;
             }
             if (found && found_chunk < 0) found_chunk = i;
         }
@@ -881,7 +832,6 @@ __global__ __launch_bounds__(256, G8_WAVES) COMMET_SGPRS void search_group8_kern
     // set = filter i is the first of a job.  The lane-a gather — 37 of a J2 / J3 job's ~55 requests per read — then serves every job
     // of the pass; everything behind it runs job by job: `found` starts afresh at a job's first filter, job j's found flags go to
     // tags + j * job_tag_words (zeroed by the host: a job never spans passes), its counters to its own chunks' slots.
-    using T = KeyTraits<W>;
     constexpr int GS = 8;
     // tails (the windows behind the first-hit ones, for a scan that has a hit but not yet t of them) are fetched by the
     // whole workgroup: see tq_replay_kernel (tile_search.hpp), where doing so took 1.8 ms of tails to 1.1
@@ -908,8 +858,7 @@ __global__ __launch_bounds__(256, G8_WAVES) COMMET_SGPRS void search_group8_kern
     __shared__ uint32_t wg_len[256];
     wg_t0[threadIdx.x] = t0, wg_len[threadIdx.x] = len;      // (first read behind a barrier)
     const uint32_t *p = rv.planes + 3 * t0;
-    const int sh = T::BITS - k;
-    const W mask = (k == T::BITS) ? ~(W) 0 : (((W) 1 << k) - 1);
+    const KeyCtx<W> kc(k);
     const int last = (int) len - 1;
     const int pe = last - (t - 1) * k;     // last window that can be a first hit; the host guarantees pe - (k-1) < 32 * MW (MW = 2, 3, 4, 6 or 8: mask_words, capi/search_dispatch.hpp)
     const int q0 = k - 1;
@@ -939,7 +888,7 @@ __global__ __launch_bounds__(256, G8_WAVES) COMMET_SGPRS void search_group8_kern
                 roll(q);
                 if (run >= (uint32_t) k) {
                     bool selfp;
-                    const W addr = psi_a<W>(T::brev(wh) >> sh, k, selfp);
+                    const W addr = psi_a<W>(kc.key(wh, 0), k, selfp);
                     const uint32_t *src = fg.il_a + (uint64_t) (addr >> 5) * GS;
                     const uint4 v = *(const uint4 *) src, u = *(const uint4 *) (src + 4);
                     const uint32_t x[GS] = {v.x, v.y, v.z, v.w, u.x, u.y, u.z, u.w};
@@ -975,18 +924,14 @@ __global__ __launch_bounds__(256, G8_WAVES) COMMET_SGPRS void search_group8_kern
             ++job, job_first = i;
             found = false, found_chunk = -1;
         }
-        const uint32_t *pb = fg.slot0 + (uint64_t) i * fg.slot_words + fg.plane_words;
-        const uint32_t *pc = pb + fg.plane_words;
-        const uint32_t *pd = pc + fg.plane_words;
+        const PlanesBCD f = planes_bcd(fg, i);
 #pragma unroll
         for (int strand = 0; strand < 2; ++strand) {
-            int seen = 0, next_ok = 0;
-            bool dead = !active || found;
-            auto probe_bcd = [&](W wh, W wl) -> bool {
+            StrandScan sc(active && !found);
+            auto probe_own = [&](int q) -> bool {   // a lane-a candidate of this thread's read (complete: the gather saw it)
                 W ka, kb;
-                if (strand == 0) ka = T::brev(wh) >> sh, kb = T::brev(wl) >> sh;
-                else ka = ~wh & mask, kb = ~wl & mask;
-                return test_bit<W>(pb, kb) && test_bit<W>(pc, ka ^ kb) && test_bit<W>(pd, ka | kb);
+                (void) kc.window_keys(p, q, strand, ka, kb);
+                return probe_bcd_chain<W>(f, ka, kb);
             };
             // The scan's lane-a candidates (~3 of a read that shares nothing with the chunk, a different number in every
             // lane) are posted in LDS and dealt out evenly: thread p probes candidate p, p + 256, ... through planes B, C, D
@@ -995,7 +940,7 @@ __global__ __launch_bounds__(256, G8_WAVES) COMMET_SGPRS void search_group8_kern
             // with the chunk: it walks its own candidates and stops at t hits, as the reference does.
             uint32_t mm[MW], ncand = 0;
 #pragma unroll
-            for (int h = 0; h < MW; ++h) mm[h] = dead ? 0u : (strand ? rm[h][i] : fm[h][i]), ncand += __popc(mm[h]);
+            for (int h = 0; h < MW; ++h) mm[h] = sc.dead ? 0u : (strand ? rm[h][i] : fm[h][i]), ncand += __popc(mm[h]);
             const bool self = ncand > G8_HEAVY;
             if (threadIdx.x == 0) cand_n = 0;
 #pragma unroll
@@ -1023,96 +968,33 @@ __global__ __launch_bounds__(256, G8_WAVES) COMMET_SGPRS void search_group8_kern
                         if (!have[u]) continue;
                         const uint32_t e = cand[ci];
                         owner[u] = e & 255u, wq[u] = e >> 8;
-                        const int q = q0 + (int) wq[u];
-                        ItemWords<W> it;
-                        it.load(rv.planes + 3 * wg_t0[owner[u]], (uint32_t) q >> 5);
-                        W wh, wl;
-                        (void) it.window((uint32_t) q & 31u, k, mask, wh, wl);   // complete: the gather saw it
-                        if (strand == 0) ka[u] = T::brev(wh) >> sh, kb[u] = T::brev(wl) >> sh;
-                        else ka[u] = ~wh & mask, kb[u] = ~wl & mask;
-                        vb[u] = pb[kb[u] >> 5];
+                        (void) kc.window_keys(rv.planes + 3 * wg_t0[owner[u]], q0 + (int) wq[u], strand, ka[u], kb[u]);   // complete: the gather saw it
+                        vb[u] = f.b[kb[u] >> 5];
                     }
 #pragma unroll
                     for (int u = 0; u < U; ++u) {
                         if (!have[u] || !((vb[u] >> ((uint32_t) kb[u] & 31u)) & 1u)) continue;
-                        const W kc = ka[u] ^ kb[u], kd = ka[u] | kb[u];
-                        const uint32_t vc = pc[kc >> 5], vd = pd[kd >> 5];
-                        if ((vc >> ((uint32_t) kc & 31u)) & (vd >> ((uint32_t) kd & 31u)) & 1u) atomicOr(&full_hit[wq[u] >> 5][owner[u]], 1u << (wq[u] & 31u));
+                        const W key_c = ka[u] ^ kb[u], key_d = ka[u] | kb[u];
+                        const uint32_t vc = f.c[key_c >> 5], vd = f.d[key_d >> 5];
+                        if ((vc >> ((uint32_t) key_c & 31u)) & (vd >> ((uint32_t) key_d & 31u)) & 1u) atomicOr(&full_hit[wq[u] >> 5][owner[u]], 1u << (wq[u] & 31u));
                     }
                 }
             }
             __syncthreads();
 #pragma unroll
-            for (int h = 0; h < MW; ++h) {
-                uint32_t m = self ? mm[h] : full_hit[h][threadIdx.x];
-                while (m && !found && !dead) {
-                    const uint32_t jj = (uint32_t) __ffs((int) m) - 1u;
-                    m &= m - 1u;
-                    const int q = q0 + 32 * h + (int) jj;
-                    if (q < next_ok) continue;
-                    if (q + (t - seen - 1) * k > last) {
-                        dead = true;
-                        break;
-                    }
-                    if (self) {
-                        ItemWords<W> it;
-                        it.load(p, (uint32_t) q >> 5);
-                        W wh, wl;
-                        (void) it.window((uint32_t) q & 31u, k, mask, wh, wl);
-                        if (!probe_bcd(wh, wl)) continue;
-                    }
-                    ++seen;
-                    next_ok = q + k;
-                    if (seen >= t) found = true;
-                }
-            }
-            // windows behind the gathered ones, after a first full hit only, GROUP8_TAIL_WIN at a time
-            for (int qb = max(pe + 1, next_ok);; qb += GROUP8_TAIL_WIN) {   // (uniform trip count: every thread takes part in the barriers)
-                const bool want = !found && !dead && seen >= 1 && qb <= last && qb + (t - seen - 1) * k <= last;
-                if (threadIdx.x == 0) tail_n = 0;
-                if (!__syncthreads_or(want)) break;
-                if (want) {
-                    tail_req[atomicAdd(&tail_n, 1u)] = threadIdx.x | ((uint32_t) qb << 8);
-                    tail_bits[threadIdx.x] = 0;
-                }
-                __syncthreads();
-                const uint32_t n_pairs = tail_n * (uint32_t) GROUP8_TAIL_WIN;
-                for (uint32_t pr = threadIdx.x; pr < n_pairs; pr += 256) {
-                    const uint32_t rq = tail_req[pr / GROUP8_TAIL_WIN], owner = rq & 255u, w = pr % GROUP8_TAIL_WIN;
-                    const int q = (int) (rq >> 8) + (int) w;
-                    if (q >= (int) wg_len[owner]) continue;
-                    ItemWords<W> it;
-                    it.load(rv.planes + 3 * wg_t0[owner], (uint32_t) q >> 5);
-                    W wh, wl;
-                    if (!it.window((uint32_t) q & 31u, k, mask, wh, wl)) continue;   // a base that is not ACGT: no k-mer here
-                    const W ka = strand ? (W) (~wh & mask) : (W) (T::brev(wh) >> sh);
-                    const W addr = psi_a<W>(ka, k);
-                    const uint32_t v = fg.il_a[(uint64_t) (addr >> 5) * GS + i];
-                    if ((v >> ((uint32_t) addr & 31u)) & 1u) atomicOr(&tail_bits[owner], 1u << w);
-                }
-                __syncthreads();
-                if (want) {
-                    uint32_t m = tail_bits[threadIdx.x];
-                    while (m && !found) {
-                        const int q = qb + (__ffs((int) m) - 1);
-                        m &= m - 1u;
-                        if (q < next_ok) continue;
-                        if (q + (t - seen - 1) * k > last) {
-                            dead = true;
-                            break;
-                        }
-                        ItemWords<W> it;
-                        it.load(p, (uint32_t) q >> 5);
-                        W wh, wl;
-                        (void) it.window((uint32_t) q & 31u, k, mask, wh, wl);
-                        if (probe_bcd(wh, wl)) {
-                            ++seen;
-                            next_ok = q + k;
-                            if (seen >= t) found = true;
-                        }
-                    }
-                }
-            }
+            for (int h = 0; h < MW; ++h)
+                sc.walk(self ? mm[h] : full_hit[h][threadIdx.x], q0 + 32 * h, t, k, last, [&](int q) -> bool { return !self || probe_own(q); });
+            // the tail, GROUP8_TAIL_WIN windows per request
+            cooperative_tail<W, GROUP8_TAIL_WIN, GS>(
+                sc, tail_req, tail_bits, tail_n, kc, strand, t, pe, last, fg.il_a, i,
+                [&](uint32_t owner, int q, W &wh, W &wl) -> bool {
+                    if (q >= (int) wg_len[owner]) return false;
+                    ItemWords<W> ot;
+                    ot.load(rv.planes + 3 * wg_t0[owner], (uint32_t) q >> 5);
+                    return ot.window((uint32_t) q & 31u, k, kc.mask, wh, wl);
+                },
+                probe_own);
+            found = found || sc.found;
         }
         if (found && found_chunk < 0) found_chunk = i;
     }

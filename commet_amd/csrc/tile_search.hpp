@@ -384,8 +384,9 @@ __global__ __launch_bounds__(256) void tq_probe_kernel(QueryListView ql, const u
 }
 
 // replay: one workgroup per piece, one thread per read.
-// (scalar registers capped, COMMET_SGPRS in kernels.hpp: eight workgroups per CU instead of six — the LDS (19.3 KiB) and the 50
-// vector registers allow eight, and the kernel is a chain of dependent round trips that lives on workgroups in flight)
+// (scalar registers capped, COMMET_SGPRS in kernels.hpp: eight workgroups per CU instead of six — the LDS (10.3-18.3 KiB) and the 49-62
+// vector registers of the builds with up to three mask words for two filters, six for one, allow eight, and the kernel is a chain of
+// dependent round trips that lives on workgroups in flight; the larger builds take 106 scalar registers and 22-38 KiB: four to six)
 template <typename W, int GS, int MW>
 __global__ __launch_bounds__(TQ_PIECE) COMMET_SGPRS void tq_replay_kernel(ReadsView rv, QueryListView ql, const uint8_t *__restrict__ qres,
                                                              FilterGroupView fg, int k, int t, const uint64_t *__restrict__ sel,
@@ -497,23 +498,16 @@ __global__ __launch_bounds__(TQ_PIECE) COMMET_SGPRS void tq_replay_kernel(ReadsV
     auto word_at = [&](uint32_t *arr, int i, int h, uint32_t rd) -> uint32_t & { return arr[((i * MW) + h) * TQ_PIECE + rd]; };
     if (threadIdx.x < 2 * GS) wg_cnt[threadIdx.x] = 0;
     if (threadIdx.x == 0) hit_n = 0;
-    const uint64_t r = (uint64_t) piece * TQ_PIECE + threadIdx.x;
-    const uint64_t word = r >> 6;
-    const int lane = threadIdx.x & 63;
-    const bool in_range = (word << 6) < rv.n;
-    uint64_t selw = ~0ull, tagw = 0;
-    if (in_range) {
-        if (sel) selw = sel[word];
-        if (tags && !multi) tagw = tags[word];
-    }
-    const bool active = (r < rv.n) && ((selw >> lane) & 1ull) && !((tagw >> lane) & 1ull);
+    static_assert(TQ_PIECE == 256, "search_lane, add_chunk_counters and cooperative_tail are written for workgroups of 256 threads");
+    const ActiveList no_list{nullptr, nullptr};
+    const SearchLane me = search_lane(rv, no_list, sel, multi ? nullptr : tags, piece0);   // thread x of piece p has read 256 p + x
+    const uint64_t r = me.r;
+    const bool active = me.active;
     uint64_t my_t0 = 0;
     uint32_t my_len = 0;
     if (r < rv.n) read_extent(rv, r, my_t0, my_len);
     if (threadIdx.x == 0) piece_t0 = my_t0;                          // (the piece's first read exists: the grid covers pieces of the set only)
-    using T = KeyTraits<W>;
-    const int sh = T::BITS - k;
-    const W kmask = (k == T::BITS) ? ~(W) 0 : (((W) 1 << k) - 1);
+    const KeyCtx<W> kc(k);
 #pragma unroll
     for (int i = 0; i < NS; ++i)
 #pragma unroll
@@ -543,12 +537,7 @@ __global__ __launch_bounds__(TQ_PIECE) COMMET_SGPRS void tq_replay_kernel(ReadsV
     // words of another read of the piece around window end q
     const uint32_t *const piece_planes = rv.planes + 3 * piece_t0;
     auto keys_of = [&](uint32_t owner, int strand, int q, W &ka, W &kb) {
-        ItemWords<W> it;
-        it.load(piece_planes + 3u * (rd_ext[owner] & 0xFFFFu), (uint32_t) q >> 5);
-        W wh, wl;
-        (void) it.window((uint32_t) q & 31u, k, kmask, wh, wl);           // complete: only complete windows are in the list
-        if (strand) ka = ~wh & kmask, kb = ~wl & kmask;
-        else ka = T::brev(wh) >> sh, kb = T::brev(wl) >> sh;
+        (void) kc.window_keys(piece_planes + 3u * (rd_ext[owner] & 0xFFFFu), q, strand, ka, kb);   // complete: only complete windows are in the list
     };
     // one balanced sweep over the set bits of `src` (heavy scans are not in it), four candidates per thread and round so that
     // four probes are in flight per lane: word_of(owner, scan, window end) -> {filter word address, bit} of the first plane
@@ -646,12 +635,8 @@ __global__ __launch_bounds__(TQ_PIECE) COMMET_SGPRS void tq_replay_kernel(ReadsV
     }
     __syncthreads();
     // (3) the reference's control flow (search_reads.h:45-83) on the full hits of this thread's read: per chunk, strand 0
-    // then strand 1; greedy non-overlapping hits; the windows behind the first-hit ones are probed only for a scan that
-    // already has a hit (exact pruning, see search_kernel).  Those tails are fetched by the whole workgroup: the threads
-    // that need one post (read, first window end) in LDS, then thread p takes window p % 32 of request p / 32 — one
-    // round trip and ~50 instructions per window with every lane busy, where a thread fetching its own 32 windows
-    // (a rolling window, four batches of eight loads) kept the other lanes of its wave waiting through
-    // ~1500 instructions and four round trips (1.8 ms of this kernel's 6.1 on configs[1]).
+    // then strand 1; greedy non-overlapping hits (StrandScan::walk); the windows behind the first-hit ones are fetched by the whole
+    // workgroup, for the scans that have a hit but not yet t of them (cooperative_tail).
     // (the hit list is dead by now; the tails' request / answer arrays take its place)
     static_assert(TQ_HIT_CAP >= 2 * TQ_PIECE, "the tails' arrays alias the hit list");
     uint32_t *const tail_req = hits, *const tail_bits = tail_req + TQ_PIECE;
@@ -663,16 +648,20 @@ __global__ __launch_bounds__(TQ_PIECE) COMMET_SGPRS void tq_replay_kernel(ReadsV
         const int last = (int) my_len - 1;
         const int pe = last - (t - 1) * k;
         const int q0 = k - 1;
-                bool found = false;
+        bool found = false;
         for (int i = 0; i < 2 * fg.g; ++i) {   // (uniform)
             if (multi && i == 2) found_job0 = found, found = false;    // chunk 1 opens the second job: nothing carries over
             const int strand = i & 1;
-            const uint32_t *pb = fg.slot0 + (uint64_t) (i >> 1) * fg.slot_words + fg.plane_words;
-            const uint32_t *pc = pb + fg.plane_words, *pd = pc + fg.plane_words;
-            int seen = 0, next_ok = 0;
-            bool dead = !active || found;
-            for (int h = 0; h < MW && !found && !dead; ++h) {
-                const bool hscan = ((hv >> i) & 1u) || all_self;
+            const PlanesBCD f = planes_bcd(fg, i >> 1);
+            StrandScan sc(active && !found);
+            // a lane-a candidate of this thread's read: a heavy scan's in the first-hit windows, anybody's in a tail
+            auto probe_own = [&](int q) -> bool {
+                W ka, kb;
+                (void) kc.window_keys(p, q, strand, ka, kb);
+                return probe_bcd_together<W>(f, ka, kb);
+            };
+            const bool hscan = ((hv >> i) & 1u) || all_self;
+            for (int h = 0; h < MW && sc.open(); ++h) {
                 uint32_t m = masks[((i * MW) + h) * TQ_PIECE + threadIdx.x];    // light scans: full hits (step 2)
                 if (hscan) {                                                     // heavy scans: lane-a candidates, probed here
                     m = 0;
@@ -682,89 +671,27 @@ __global__ __launch_bounds__(TQ_PIECE) COMMET_SGPRS void tq_replay_kernel(ReadsV
                         for (int hh = 0; hh < MW; ++hh)
                             if (ii == i && hh == h) m = am[ii][hh];
                 }
-                while (m) {
-                    const int q = q0 + 32 * h + (__ffs((int) m) - 1);
-                    m &= m - 1u;
-                    if (q < next_ok) continue;
-                    if (q + (t - seen - 1) * k > last) {
-                        dead = true;
-                        break;
-                    }
-                    if (hscan) {
-                        ItemWords<W> it;
-                        it.load(p, (uint32_t) q >> 5);
-                        W wh, wl, ka, kb;
-                        (void) it.window((uint32_t) q & 31u, k, kmask, wh, wl);
-                        if (strand) ka = ~wh & kmask, kb = ~wl & kmask;
-                        else ka = T::brev(wh) >> sh, kb = T::brev(wl) >> sh;
-                        // three independent loads, one round trip: a heavy scan's candidates are almost all true k-mers of the
-                        // index set, the short circuit b -> c -> d would only serialise them
-                        const uint32_t vb = pb[kb >> 5], vc = pc[(ka ^ kb) >> 5], vd = pd[(ka | kb) >> 5];
-                        if (!((vb >> ((uint32_t) kb & 31u)) & (vc >> ((uint32_t) (ka ^ kb) & 31u)) & (vd >> ((uint32_t) (ka | kb) & 31u)) & 1u)) continue;
-                    }
-                    ++seen;
-                    next_ok = q + k;
-                    if (seen >= t) {
-                        found = true;
-                        break;
-                    }
-                }
+                sc.walk(m, q0 + 32 * h, t, k, last, [&](int q) -> bool { return !hscan || probe_own(q); });
             }
-            // windows behind the first-hit ones, 32 at a time, for the scans that have a hit but not yet t of them
-            for (int qb = max(pe + 1, next_ok);; qb += 32) {   // (uniform trip count: every thread takes part in the barriers)
-                const bool want = !found && !dead && seen >= 1 && qb <= last && qb + (t - seen - 1) * k <= last;
-                if (threadIdx.x == 0) tail_n = 0;
-                if (!__syncthreads_or(want)) break;
-                if (want) {
-                    tail_req[atomicAdd(&tail_n, 1u)] = threadIdx.x | ((uint32_t) qb << 8);
-                    tail_bits[threadIdx.x] = 0;
-                }
-                __syncthreads();
-                const uint32_t n_pairs = tail_n * 32u;
-                for (uint32_t pr = threadIdx.x; pr < n_pairs; pr += TQ_PIECE) {
-                    const uint32_t rq = tail_req[pr >> 5], owner = rq & 255u, w = pr & 31u;
-                    const int q = (int) (rq >> 8) + (int) w;
+            // the tail, 32 windows per request; an owner's extent and words through rd_ext (above)
+            cooperative_tail<W, 32, GS>(
+                sc, tail_req, tail_bits, tail_n, kc, strand, t, pe, last, fg.il_a, i >> 1,
+                [&](uint32_t owner, int q, W &wh, W &wl) -> bool {
                     const uint32_t oext = rd_ext[owner];
-                    if (q >= (int) (oext >> 16)) continue;
-                    ItemWords<W> it;
-                    it.load(piece_planes + 3u * (oext & 0xFFFFu), (uint32_t) q >> 5);
-                    W wh, wl;
-                    if (!it.window((uint32_t) q & 31u, k, kmask, wh, wl)) continue;   // a base that is not ACGT: no k-mer here
-                    const W ka = strand ? (W) (~wh & kmask) : (W) (T::brev(wh) >> sh);
-                    const W addr = psi_a<W>(ka, k);
-                    const uint32_t v = fg.il_a[(uint64_t) (addr >> 5) * GS + (uint32_t) (i >> 1)];
-                    if ((v >> ((uint32_t) addr & 31u)) & 1u) atomicOr(&tail_bits[owner], 1u << w);
-                }
-                __syncthreads();
-                if (want) {
-                    uint32_t m = tail_bits[threadIdx.x];
-                    while (m && !found) {
-                        const int q = qb + (__ffs((int) m) - 1);
-                        m &= m - 1u;
-                        if (q < next_ok) continue;
-                        if (q + (t - seen - 1) * k > last) {
-                            dead = true;
-                            break;
-                        }
-                        ItemWords<W> it;
-                        it.load(p, (uint32_t) q >> 5);
-                        W wh, wl, ka, kb;
-                        (void) it.window((uint32_t) q & 31u, k, kmask, wh, wl);
-                        if (strand) ka = ~wh & kmask, kb = ~wl & kmask;
-                        else ka = T::brev(wh) >> sh, kb = T::brev(wl) >> sh;
-                        const uint32_t vb = pb[kb >> 5], vc = pc[(ka ^ kb) >> 5], vd = pd[(ka | kb) >> 5];   // one round trip
-                        if ((vb >> ((uint32_t) kb & 31u)) & (vc >> ((uint32_t) (ka ^ kb) & 31u)) & (vd >> ((uint32_t) (ka | kb) & 31u)) & 1u) {
-                            ++seen;
-                            next_ok = q + k;
-                            if (seen >= t) found = true;
-                        }
-                    }
-                }
-            }
+                    if (q >= (int) (oext >> 16)) return false;
+                    ItemWords<W> ot;
+                    ot.load(piece_planes + 3u * (oext & 0xFFFFu), (uint32_t) q >> 5);
+                    return ot.window((uint32_t) q & 31u, k, kc.mask, wh, wl);
+                },
+                probe_own);
+            found = found || sc.found;
             if (found && found_chunk < 0) found_chunk = i >> 1;
         }
         found_job1 = found;
     }
+    const int lane = threadIdx.x & 63;
+    const uint64_t word = me.word;
+    const bool in_range = me.in_range;
     if constexpr (GS == 2) if (multi) {
         const uint64_t fb0 = __ballot(found_job0), fb1 = __ballot(found_job1), sc = __ballot(active);
         if (lane == 0 && in_range && tags) tags[word] = fb0, tags[job_tag_words + word] = fb1;
@@ -781,24 +708,8 @@ __global__ __launch_bounds__(TQ_PIECE) COMMET_SGPRS void tq_replay_kernel(ReadsV
         }
         return;
     }
-    const bool found = found_chunk >= 0;
-    const uint64_t fb = __ballot(found);
-    if (lane == 0 && in_range && tags) tags[word] = tagw | fb;
-    __syncthreads();
-    if (counters) {
-        // per workgroup in LDS first: every wave adding to the same two global words costs milliseconds of serialised atomics
-        for (int i = 0; i < fg.g; ++i) {
-            const uint64_t sc = __ballot(active && (found_chunk < 0 || found_chunk >= i));
-            const uint64_t fd = __ballot(found_chunk == i);
-            if (lane == 0) {
-                if (sc) atomicAdd(&wg_cnt[2 * i], (unsigned int) __popcll(sc));
-                if (fd) atomicAdd(&wg_cnt[2 * i + 1], (unsigned int) __popcll(fd));
-            }
-        }
-        __syncthreads();
-        if (threadIdx.x < 2 * (unsigned) fg.g && wg_cnt[threadIdx.x])
-            atomicAdd(&counters[(uint64_t) (threadIdx.x >> 1) * cstride + (threadIdx.x & 1)], (unsigned long long) wg_cnt[threadIdx.x]);
-    }
+    publish_found(no_list, me, found_chunk >= 0, tags);
+    if (counters) add_chunk_counters(counters, cstride, fg.g, active, found_chunk, wg_cnt);
 }
 
 }  // namespace commet
