@@ -274,6 +274,18 @@ class ReadSet:
         rs.finalize()
         return rs
 
+    def filter(self, min_len=0, max_n=None, min_shannon=0.0, max_reads=None):
+        """commet_readset_filter: the reads `filter_reads -l min_len -n max_n -e min_shannon -m max_reads` selects in each file of the
+        set, decided on the device from the resident planes.  max_n None: any number of non-ACGT bases; max_reads None: no cap (it
+        applies per file).  Returns (bits, stats): the set-wide selection (the form index_and_search takes as a select) and, per file,
+        dict(reads, selected, removed_length, removed_n, removed_shannon) — the numbers the tool prints."""
+        nf = self.num_files
+        bits = np.zeros(bits_nbytes(self.num_reads), dtype=np.uint8)
+        st = (_l.FilterStats * max(nf, 1))()
+        self._check(self._lib.commet_readset_filter(self._ctx._h, self._h, int(min_len), -1 if max_n is None else int(max_n),
+                                                    float(min_shannon), -1 if max_reads is None else int(max_reads), _ptr(bits), st))
+        return bits, [{f: int(getattr(st[i], f)) for f, _ in _l.FilterStats._fields_} for i in range(nf)]
+
     def file_reads(self):
         return [int(self._lib.commet_readset_file_reads(self._h, i)) for i in range(self.num_files)]
 

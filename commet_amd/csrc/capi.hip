@@ -9,9 +9,11 @@
 #include "index_part.hpp"
 #include "slice_search.hpp"
 #include "tile_search.hpp"
+#include "read_filter.hpp"
 #include "read_iter.hpp"
 #include "host/fasta_source.hpp"
 #include "host/ingest_pack.hpp"
+#include "host/filter_rule.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -22,6 +24,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <climits>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -44,6 +47,7 @@
 #include "capi/context.hpp"          // commet_create / _destroy
 #include "capi/readset.hpp"          // resident read sets, host ingest
 #include "capi/images.hpp"           // packed images, HIP IPC hand-over
+#include "capi/filter.hpp"           // commet_readset_filter: length / N / Shannon / -m on a resident set
 #include "capi/index_dispatch.hpp"   // index construction: which path, its launches
 #include "capi/search_dispatch.hpp"  // search regimes: which one, its launches
 #include "capi/job.hpp"              // commet_index_reads / _search_reads / _index_and_search

@@ -103,6 +103,7 @@ void commet_destroy(commet_ctx *c)
         if (b.done) (void) hipEventDestroy(b.done);
     }
     c->kclock.release();
+    (void) dm_free(c->d_shannon);
     (void) dm_free(c->d_qres);
     (void) dm_free(c->slice_stage);
     (void) dm_free(c->slice_tables);

@@ -183,6 +183,7 @@ int commet_kernel_times(commet_ctx *c, commet_kernel_time *out, int cap, int *n_
     HIP_OK(hipSetDevice(c->device));
     HIP_OK(hipStreamSynchronize(c->stream));
     c->kclock.collect();
+    std::lock_guard<std::mutex> lk(c->kclock.mu);
     const int n = (int) c->kclock.names.size();
     if (n_out) *n_out = n;
     for (int i = 0; i < n && i < cap; ++i) {

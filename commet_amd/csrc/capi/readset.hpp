@@ -71,6 +71,7 @@ void commet_readset_destroy(commet_readset *rs)
     (void) dm_free(rs->d_sel);
     (void) dm_free(rs->d_tags);
     (void) dm_free(rs->d_found);
+    (void) dm_free(rs->d_filter_ws);
     rs->ql.release();
     (void) dm_free(rs->d_len_order);
     for (int i = 0; i < 2; ++i) {

@@ -482,6 +482,16 @@ struct commet_ctx {
         std::vector<std::string> names;                // totals, in first-seen order
         std::vector<uint64_t> launches;
         std::vector<double> total_ms;
+        std::mutex mu;                                 // the totals: commet_readset_filter adds its kernel from the thread that makes the sets
+        void add(const char *name, double ms)
+        {
+            std::lock_guard<std::mutex> lk(mu);
+            size_t i = 0;
+            while (i < names.size() && names[i] != name) ++i;
+            if (i == names.size()) names.push_back(name), launches.push_back(0), total_ms.push_back(0);
+            launches[i] += 1;
+            total_ms[i] += ms;
+        }
         hipEvent_t get()
         {
             hipEvent_t e = nullptr;
@@ -493,19 +503,17 @@ struct commet_ctx {
         {
             for (Rec &r : open) {
                 float ms = 0;
-                if (r.a && r.b && hipEventElapsedTime(&ms, r.a, r.b) == hipSuccess) {
-                    size_t i = 0;
-                    while (i < names.size() && names[i] != r.name) ++i;
-                    if (i == names.size()) names.push_back(r.name), launches.push_back(0), total_ms.push_back(0);
-                    launches[i] += 1;
-                    total_ms[i] += ms;
-                }
+                if (r.a && r.b && hipEventElapsedTime(&ms, r.a, r.b) == hipSuccess) add(r.name, ms);
                 if (r.a) spare.push_back(r.a);
                 if (r.b) spare.push_back(r.b);
             }
             open.clear();
         }
-        void reset() { names.clear(), launches.clear(), total_ms.clear(); }
+        void reset()
+        {
+            std::lock_guard<std::mutex> lk(mu);
+            names.clear(), launches.clear(), total_ms.clear();
+        }
         void release()
         {
             collect();
@@ -540,6 +548,8 @@ struct commet_ctx {
     uint32_t *wide_tables = nullptr;
     uint64_t wide_table_words = 0;
     uint64_t max_kmer_test = 0;       // option "max_kmer": chunk size override for tests (0 = the reference's constant)
+    double *d_shannon = nullptr;      // Shannon terms of the read lengths shannon_lo .. shannon_hi (commet_readset_filter, host/filter_rule.hpp), kept between calls
+    uint32_t shannon_lo = 0, shannon_hi = 0;
     int chunk_group = 8;              // option: chunks searched per pass (1 = one pass per chunk; more than 4 only where group8_ok)
     // pinned / device staging buffers of the parallel host ingest, kept for the next read set (hipHostMalloc is slow)
     struct IngestBuf {
@@ -631,6 +641,8 @@ struct commet_readset {
     mutable std::atomic<uint64_t> ql_reserved_at{0};  // g_devmem.trims when the memory was set aside: a trim since then has given it back
     mutable std::atomic<bool> ql_reserved{false};   // the memory of the set's list waits in the library's device cache (commet_readset_reserve_cache): a list above the cap may be built
     mutable bool in_job = false;                    // part of the commet_index_and_search call that is running: its list stays
+    mutable uint64_t *d_filter_ws = nullptr;   // scratch of commet_readset_filter: three verdict bitmaps, the count and the list of its long reads; made on first use
+    mutable uint64_t filter_ws_bytes = 0;
     bool host_packed = false;                  // some reads were packed on the host (host/ingest_pack.hpp): counts come from kmer_counts_kernel
     uint32_t host_min_len = 0xFFFFFFFFu, host_max_len = 0;
     bool finalized = false;

@@ -16,6 +16,7 @@
 
 #include "bv_file.hpp"
 #include "fasta_source.hpp"
+#include "filter_rule.hpp"
 
 using namespace commet_host;
 
@@ -64,44 +65,15 @@ struct ReadStats {
     uint64_t non_acgt() const { return cnt[4]; }
 };
 
-// filter_reads.cpp:265-306, same float / double mix:  index (float) += f * log(f) / log(2)  with f = (float) count / (float) len.
-// The double term depends on (count, len) only and is remembered per worker for the read lengths that occur.
-struct Shannon {
-    std::vector<std::vector<double>> memo;   // memo[len][count], NaN = not computed yet
-    float operator()(const ReadStats &st)
-    {
-        float index = 0;
-        for (int i = 0; i < 5; ++i) {
-            const float f = (float) st.cnt[i] / (float) st.len;
-            if (f == 0) continue;
-            double term;
-            if (st.len <= 1024) {
-                if (memo.size() <= st.len) memo.resize(st.len + 1);
-                std::vector<double> &row = memo[st.len];
-                if (row.empty()) row.assign(st.len + 1, std::nan(""));
-                double &slot = row[st.cnt[i]];
-                if (slot != slot) slot = f * log(f) / log(2);
-                term = slot;
-            } else {
-                term = f * log(f) / log(2);
-            }
-            index += term;
-        }
-        return fabs(index);
-    }
-};
-
-// what the reference's loop does with a read (filter_reads.cpp:186-200), decided from its statistics alone
-enum Verdict : uint8_t { KEEP = 0, RM_LENGTH = 1, RM_N = 2, RM_SHANNON = 3, EMPTY = 4 };
-
 int main(int argc, char **argv)
 {
     const clock_t begin_time = clock();
     std::string in_name, out_name;
-    int min_size = 0, max_N = INT_MAX;
-    float min_shannon = 0.0;
+    FilterRule rule;   // -l, -n, -e
+    int &min_size = rule.min_size, &max_N = rule.max_N;
+    float &min_shannon = rule.min_shannon;
     std::stringstream comment;
-    long max_reads = -1, nb_selected = 0;
+    long max_reads = -1;
     for (int i = 1; i < argc; ++i) {
         const std::string flag = argv[i];
         auto arg = [&]() -> const char * { return i + 1 < argc ? argv[++i] : ""; };
@@ -158,16 +130,8 @@ int main(int argc, char **argv)
     BitVector bv;
     const bool fastq = mf.format() == ReadFormat::Fastq;
     if (fastq) bv.init_true(count_records(mf.format(), d, n));   // FASTA: the classification below counts the records
-    long rm_length = 0, rm_N = 0, rm_shannon = 0;
-    const bool need_bases = max_N != INT_MAX || min_shannon > 0;   // else the verdict depends on the length alone
-    auto classify = [&](const ReadStats &st, Shannon &sh) -> uint8_t {
-        if (st.len == 0) return EMPTY;
-        if ((int) st.len < min_size) return RM_LENGTH;
-        if ((long) st.non_acgt() > (long) max_N) return RM_N;
-        // the index is |...| >= 0: only a positive threshold can remove a read (the usual -e 0 never computes it)
-        if (min_shannon > 0 && sh(st) < min_shannon) return RM_SHANNON;
-        return KEEP;
-    };
+    const bool need_bases = rule.needs_bases();   // else the verdict depends on the length alone
+    auto classify = [&](const ReadStats &st, Shannon &sh) -> uint8_t { return commet_host::classify(rule, st.len, st.cnt, sh); };
     // FASTA: pieces of whole records (cut at lines starting with '>', the reference's own record rule) are classified
     // by several threads; FASTQ stays one piece ('@' may also start a quality line).  The reference's sequential loop
     // (stop at an empty sequence or at the -m cap, counters, bits) then runs over the verdicts.
@@ -236,28 +200,30 @@ int main(int argc, char **argv)
         for (const std::vector<uint8_t> &piece : verdicts) total += piece.size();
         bv.init_true(total);
     }
-    if (max_reads == -1) max_reads = (long) bv.size;
-    uint64_t pos = 0;          // current_read_pos
-    bool stopped = false;      // the reference iterator stops at an empty sequence / at the -m cap
-    for (const std::vector<uint8_t> &piece : verdicts) {
-        for (const uint8_t v : piece) {
-            if (nb_selected >= max_reads || v == EMPTY) {   // loop condition of filter_reads.cpp:186
-                stopped = true;
-                break;
-            }
-            if (v == KEEP) ++nb_selected;
-            else {
-                bv.bytes[pos >> 3] &= (uint8_t) ~(1u << (pos & 7));
-                if (v == RM_LENGTH) ++rm_length;
-                else if (v == RM_N) ++rm_N;
-                else ++rm_shannon;
-            }
-            ++pos;             // the look-ahead get_next_read (filter_reads.cpp:200)
+    // the reference's sequential loop over the verdicts, in file order (filter_rule.hpp)
+    std::vector<const uint8_t *> piece_at;     // verdicts of read pos: pieces are whole runs of records
+    std::vector<uint64_t> piece_first;
+    {
+        uint64_t r = 0;
+        for (const std::vector<uint8_t> &piece : verdicts) {
+            if (piece.empty()) continue;
+            piece_first.push_back(r);
+            piece_at.push_back(piece.data());
+            r += piece.size();
         }
-        if (stopped) break;
     }
-    if (nb_selected >= max_reads)   // untag_last_reads: everything from the look-ahead read on
-        for (uint64_t r = pos; r < bv.size; ++r) bv.bytes[r >> 3] &= (uint8_t) ~(1u << (r & 7));
+    uint64_t n_verdicts = 0;
+    for (const std::vector<uint8_t> &piece : verdicts) n_verdicts += piece.size();
+    size_t pc = 0;                             // the loop asks for the reads in order
+    const FilterCounts fc = filter_loop(
+        bv.size, max_reads,
+        [&](uint64_t pos) -> uint8_t {
+            if (pos >= n_verdicts) return EMPTY;   // (a FASTQ file that ends inside a record)
+            while (pc + 1 < piece_first.size() && piece_first[pc + 1] <= pos) ++pc;
+            return piece_at[pc][pos - piece_first[pc]];
+        },
+        [&](uint64_t r) { bv.bytes[r >> 3] &= (uint8_t) ~(1u << (r & 7)); });
+    const uint64_t rm_length = fc.removed_length, rm_N = fc.removed_n, rm_shannon = fc.removed_shannon, nb_selected = fc.selected;
     bv.comment = comment.str();
     if (!write_bv(out_name, bv)) return 1;
 

@@ -1,11 +1,13 @@
 // plan_capi.cpp — C entry points of the host-side chunk planner (read_iter.hpp)
-// for CPU-only tests (no HIP): libcommet_plan.so.  The HIP library uses the same
-// header directly.
+// and of the host half of the device read filter (host/filter_rule.hpp) for
+// CPU-only tests (no HIP): libcommet_plan.so.  The HIP library uses the same
+// headers directly.
 #include <cstdint>
 #include <cstring>
 #include <vector>
 
 #include "../read_iter.hpp"
+#include "filter_rule.hpp"
 
 using namespace commet;
 
@@ -64,6 +66,23 @@ uint64_t commet_plan_search(const uint64_t *files, int n_files, const uint8_t *s
     else bits = plan_search(fs, select, er, n_reads, &n);
     memcpy(visited_bits_out, bits.data(), bits.size());
     return n;
+}
+
+// the Shannon terms of the read lengths len_lo .. len_hi, as the device filter's table holds them (filter_rule.hpp); returns the
+// number of doubles (out == NULL: only that)
+uint64_t commet_filter_shannon_table(uint64_t len_lo, uint64_t len_hi, double *out)
+{
+    if (out) commet_host::fill_shannon_table(len_lo, len_hi, out);
+    return commet_host::shannon_table_size(len_lo, len_hi);
+}
+
+// the sequential part of the filter rule over verdict bitmaps of a set (64 reads per word), for the file of reads
+// [first, first + count): its final bits into `out` (a bitmap over the set), counts_out = {selected, removed by length, by N, by Shannon}
+void commet_filter_finish_file(const uint64_t *keep, const uint64_t *rm_length, const uint64_t *rm_n, uint64_t first, uint64_t count,
+                               const uint64_t *empty_reads, uint64_t n_empty, int64_t max_reads, uint64_t *out, uint64_t *counts_out)
+{
+    const commet_host::FilterCounts fc = commet_host::finish_file(keep, rm_length, rm_n, first, count, empty_reads, n_empty, max_reads, out);
+    counts_out[0] = fc.selected, counts_out[1] = fc.removed_length, counts_out[2] = fc.removed_n, counts_out[3] = fc.removed_shannon;
 }
 
 }  // extern "C"

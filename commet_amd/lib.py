@@ -26,6 +26,11 @@ class JobInfo(C.Structure):
                 ("index_kernel_ms", C.c_double), ("search_ms", C.c_double), ("total_ms", C.c_double)]
 
 
+class FilterStats(C.Structure):
+    _fields_ = [("reads", C.c_uint64), ("selected", C.c_uint64), ("removed_length", C.c_uint64), ("removed_n", C.c_uint64),
+                ("removed_shannon", C.c_uint64)]
+
+
 class KernelTime(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_uint64), ("total_ms", C.c_double)]
 
@@ -60,6 +65,8 @@ SIGNATURES = {
     "commet_readset_num_reads": (C.c_uint64, [C.c_void_p]),
     "commet_readset_num_files": (C.c_uint64, [C.c_void_p]),
     "commet_readset_kmer_counts": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "commet_readset_filter": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_int64, C.c_void_p,
+                                        C.POINTER(FilterStats)]),
     "commet_readset_cache_bytes": (C.c_uint64, [C.c_void_p]),
     "commet_readset_drop_cache": (None, [C.c_void_p]),
     "commet_cache_stats": (C.c_int, [C.c_void_p, u64p, u64p, u64p]),

@@ -88,18 +88,42 @@ def write_bv(path, comment, n, bits):
         fh.write(np.ascontiguousarray(bits[:n // 8 + 1], dtype=np.uint8).tobytes())
 
 
+def c_atoi(text):
+    """what C's atoi makes of a string: blanks, a sign, then digits up to the first other character (filter_reads reads -l, -n, -m so)"""
+    t = text.lstrip(" \t\n\v\f\r")
+    sign, i = 1, 0
+    if t[:1] in ("+", "-"):
+        sign, i = (-1 if t[0] == "-" else 1), 1
+    j = i
+    while j < len(t) and t[j] in "0123456789":
+        j += 1
+    return sign * int(t[i:j]) if j > i else 0
+
+
+def filter_comment(read_file, l=0, n=-1, e=0.0):
+    """the comment block `filter_reads <read_file> -l l [-n n] -e e` puts in front of its vector (filter_reads.cpp:160-176): the file's base
+    name, then the options as its stream prints them — `infinite` when -n is not given, -e as a C++ stream prints the float it was read into"""
+    i = read_file.rfind("/")
+    return ("----------------\nReference file\n  " + (read_file[i + 1:] if i > 0 else read_file) + "\nFilter Options\n"
+            "  min read size     : %d\n  max number of N   : %s\n  min shannon index : %s\n"
+            % (l, "infinite" if n < 0 else "%d" % n, "%g" % float(np.float32(e))))
+
+
+def write_filter_bv(path, read_file, count, bits, l=0, n=-1, e=0.0):
+    """The .bv `filter_reads <read_file> -l l [-n n] -e e [-m m] -o <path>` writes (boolean_vector.h:302-346), from the file's final bits
+    (count reads; -m shows in the bits only).  Appears complete or not at all (written under another name, renamed)."""
+    write_bv(path + ".part", filter_comment(read_file, l, n, e), count, bits)
+    os.rename(path + ".part", path)
+
+
 def default_filter_bv(path, read_file, n):
     """What `filter_reads <read_file> -l 0 -e 0 -o <path>` writes (filter_reads.cpp:160-176, boolean_vector.h:148-164, 302-346): with the
     default options no read can be removed, so the vector is all ones over the file's n reads (padding bits cleared) behind the tool's
     comment block — written from the parser's record count instead of a second pass over the file.  Returns the bits."""
     bits = np.full(n // 8 + 1, 0xFF, dtype=np.uint8)
     bits[-1] = (1 << (n & 7)) - 1                                   # bits n .. of the last byte (all of it when n % 8 == 0) are padding
-    i = read_file.rfind("/")
-    comment = ("----------------\nReference file\n  " + (read_file[i + 1:] if i > 0 else read_file) + "\nFilter Options\n"
-               "  min read size     : 0\n  max number of N   : infinite\n  min shannon index : 0\n")
     if path is not None:
-        write_bv(path + ".part", comment, n, bits)
-        os.rename(path + ".part", path)
+        write_filter_bv(path, read_file, n, bits)
     return bits
 
 
@@ -223,6 +247,11 @@ class HipEngine:
     def file_reads(self, rs):
         return rs.file_reads()
 
+    def filter_set(self, rs, l, n, e, m_per_file):
+        """The selection `filter_reads -l l [-n n] -e e [-m m_per_file]` makes in every file of the resident set (n < 0: no -n,
+        m_per_file < 0: no -m), on the device (commet_readset_filter) -> (set-wide bits, per-file counters)"""
+        return rs.filter(min_len=l, max_n=None if n < 0 else n, min_shannon=e, max_reads=None if m_per_file < 0 else m_per_file)
+
     def release(self, rs):
         rs.close()
 
@@ -311,7 +340,17 @@ def run(input_file, out_dir, k=33, t=2, l=0, n=-1, e=0.0, m=-1, bin_dir=None, ra
     # rank derives the same selection from the counts of the set it holds — no second pass over the files, nothing to wait for.
     # COMMET_MATRIX_FILTER_TOOL=1 runs filter_reads all the same.
     synth_filters = bvs is None and l == 0 and e == 0 and n < 0 and m < 0 and os.environ.get("COMMET_MATRIX_FILTER_TOOL", "0") != "1"
-    if synth_filters:
+    # Any other options: every read's length and base counts are in the resident set's planes, so the selection is made on the device
+    # from the copy each rank holds (filter_set: commet_readset_filter, the tool's bits) — no filter_reads process re-reads the text,
+    # nothing to wait for; the set's owner leaves the tool's .bv files.  Engines without filter_set and COMMET_MATRIX_FILTER_TOOL=1
+    # run filter_reads as before.
+    eng = None
+    device_filters = False
+    if bvs is None and not synth_filters and os.environ.get("COMMET_MATRIX_FILTER_TOOL", "0") != "1":
+        eng = (engine_factory or HipEngine)(k, t, ranks.local_rank)
+        device_filters = hasattr(eng, "filter_set")
+    device_filter_s = [0.0]
+    if synth_filters or device_filters:
         bvs = [[out_dir + os.path.basename(f) + ".bv" for f in fl] for fl in files]
         filter_pool, filter_jobs, filtered_here = None, [], False
     elif bvs is None:
@@ -373,6 +412,8 @@ def run(input_file, out_dir, k=33, t=2, l=0, n=-1, e=0.0, m=-1, bin_dir=None, ra
             finally:
                 filter_pool.shutdown(wait=True)
             filter_s = (filter_end[0] if filter_jobs else time.perf_counter()) - t_filter
+        elif device_filters:
+            filter_s = device_filter_s[0]
 
     scratch = None
     if world > 1:
@@ -380,7 +421,8 @@ def run(input_file, out_dir, k=33, t=2, l=0, n=-1, e=0.0, m=-1, bin_dir=None, ra
         scratch = ranks.broadcast_object(tempfile.mkdtemp(prefix="commet_pk_", dir=_scratch_root()) if rank == 0 else None)
     # sets are made resident by a second thread while the jobs run (COMMET_MATRIX_PIPELINE=0: everything first)
     pipelined = N >= 2 and os.environ.get("COMMET_MATRIX_PIPELINE", "1") != "0"
-    eng = (engine_factory or HipEngine)(k, t, ranks.local_rank)
+    if eng is None:
+        eng = (engine_factory or HipEngine)(k, t, ranks.local_rank)
     # How a set parsed by one rank reaches the others: device to device over HIP IPC (the owner exports its buffers, the
     # others copy them over xGMI: no file, tens of ms for a 50 M-read set) when every rank can import a probe set of its
     # neighbour and of rank 0; else as a packed image in the scratch directory (0.5 s to write, 0.2 s to read).
@@ -479,11 +521,30 @@ def run(input_file, out_dir, k=33, t=2, l=0, n=-1, e=0.0, m=-1, bin_dir=None, ra
         sets = {}
         solo = pipelined and world == 1                           # (then the loading thread parses, too)
 
+        device_sel = {}                                           # set -> its per-file (count, bits), made on the device (device_filters)
+
+        def device_filter(s, rs):
+            """the selection of set s from the resident copy this rank holds; the per-file cap is what the tool's atoi makes of the
+            `-m` the driver passes it (str(m / files of the set))"""
+            if s not in device_sel:
+                w0 = time.perf_counter()
+                bits, _ = eng.filter_set(rs, l, n, e, c_atoi(str(m / len(files[s]))) if m >= 0 else -1)
+                cs = eng.file_reads(rs)
+                device_sel[s] = list(zip(cs, split_bits(bits, cs)))
+                device_filter_s[0] += time.perf_counter() - w0
+            return device_sel[s]
+
         def leave_filters(s, rs):
-            """default options: the filter files of a set this rank has just parsed, from its record counts"""
+            """the filter files of a set this rank has just parsed: from its record counts (default options), or the device's selection"""
             if synth_filters:
                 for c_, f_, b_ in zip(eng.file_reads(rs), files[s], bvs[s]):
                     default_filter_bv(b_, f_, c_)
+            elif device_filters:
+                parts = device_filter(s, rs)
+                w0 = time.perf_counter()
+                for (c_, bits_), f_, b_ in zip(parts, files[s], bvs[s]):
+                    write_filter_bv(b_, f_, c_, bits_, l, n, e)
+                device_filter_s[0] += time.perf_counter() - w0
 
         def parse_own(s):
             """one of this rank's sets: parsed here and nowhere else; its packed image published for the ranks that need it
@@ -527,6 +588,8 @@ def run(input_file, out_dir, k=33, t=2, l=0, n=-1, e=0.0, m=-1, bin_dir=None, ra
                         return False
             if synth_filters:                                     # all ones (the set's owner has left the files: leave_filters)
                 parts = [(c, default_filter_bv(None, f, c)) for c, f in zip(counts[s], files[s])]
+            elif device_filters:                                  # from the copy this rank holds (its owner has left the files, too)
+                parts = device_filter(s, sets[s])
             else:
                 parts = [read_bv(b) for b in bvs[s]]
             considered[s] = sum(popcount(b, nb) for nb, b in parts)

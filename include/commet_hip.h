@@ -22,7 +22,7 @@
  *     caller; several ctxs may be used from several host threads.  One exception:
  *     read sets are made on a stream of their own, so ONE host thread may build read
  *     sets of a ctx (commet_readset_create ... commet_readset_finalize,
- *     commet_readset_from_*, commet_readset_load) while another runs
+ *     commet_readset_from_*, commet_readset_load, commet_readset_filter) while another runs
  *     commet_index_and_search on sets that are complete (commet_amd/matrix.py does).
  *   - there is NO CPU fallback: without a usable HIP device commet_create fails.
  */
@@ -119,6 +119,26 @@ uint64_t        commet_readset_num_reads(const commet_readset *rs);
 uint64_t        commet_readset_num_files(const commet_readset *rs);
 /* kmers_out[n_reads]: complete k-mers of each read (valid after finalize) */
 int             commet_readset_kmer_counts(const commet_readset *rs, uint32_t *kmers_out);
+/* Replaces one `filter_reads <file> -l -n -e -m` run per file of the set (src/filter_reads.cpp:186-205, 265-306; Commet.py:103-121) for a
+ * FINALIZED resident set: one pass over the packed planes gives every read's length and A / C / G / T / other counts, the verdicts
+ * follow the tool's order (length, then N, then Shannon: index < min_shannon as floats, the terms f * log(f) / log(2) taken from a
+ * table the host fills with the tool's own expression, so no device transcendental decides), and the tool's sequential loop — stop
+ * at the first empty record or once max_reads_per_file reads are selected, counters over the reads before the stop,
+ * untag_last_reads — runs per file, as one tool run per file does.  min_len: -l; max_n: -n (< 0: any); min_shannon: -e (<= 0: not
+ * computed, as in the tool); max_reads_per_file: -m (< 0: all).  select_out (n/8+1 bytes over the set-wide read numbers, padding
+ * bits zero) is bit for bit the tool's vectors, file after file: the form commet_index_and_search takes as index_select /
+ * search_select.  per_file (num_files entries, may be NULL) carries what the tool prints for each file.  Runs on the stream that
+ * makes read sets (see Conventions). */
+typedef struct {
+    uint64_t reads;            /* records of the file                                  */
+    uint64_t selected;         /* "Number of selected reads"                           */
+    uint64_t removed_length;   /* "Length filter [l]: ... reads removed"               */
+    uint64_t removed_n;        /* "Number of N filter [n]: ... reads removed"          */
+    uint64_t removed_shannon;  /* "Shannon filter [e]: ... reads removed"              */
+} commet_filter_stats;
+int             commet_readset_filter(commet_ctx *ctx, const commet_readset *rs, int min_len, int64_t max_n /* <0: any */,
+                                      float min_shannon, int64_t max_reads_per_file /* <0: all */,
+                                      uint8_t *select_out /* set-wide, n/8+1 bytes */, commet_filter_stats *per_file /* num_files, may be NULL */);
 /* Derived data cached WITH a resident set: the query list of the tiled search (the set's lane-a addresses sorted by
  * address slice; depends on (k, t) and the set only, made on the set's first scan, ~6 bytes per first-hit window — 2.2 GB
  * for 10 M x 100 bp reads at k = 32, t = 2, against 0.5 GB for the packed set).  The lists of a context are held to a
