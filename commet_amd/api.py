@@ -65,6 +65,17 @@ def device_alloc_stats(device=-1):
     return {"wait_ms": float(ms.value), "fresh_bytes": int(by.value), "calls": int(n.value)}
 
 
+def files_packed_bytes(paths):
+    """commet_files_packed_bytes: (reads, bases, packed_bytes) of the set ReadSet.from_fasta would make of these files, counted on the
+    host — what a residency planner needs before any set is parsed"""
+    lib = _l.load()
+    arr = (C.c_char_p * len(paths))(*[os.fsencode(p) for p in paths])
+    r, b, p = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+    if lib.commet_files_packed_bytes(arr, len(paths), C.byref(r), C.byref(b), C.byref(p)) != 0:
+        raise CommetError(_err(lib))
+    return int(r.value), int(b.value), int(p.value)
+
+
 class Context:
     """commet_ctx: device, k, t, the 4-lane Bloom filter in HBM."""
 
@@ -316,6 +327,28 @@ class ReadSet:
         """commet_readset_reserve_cache: asks the driver NOW (from the calling thread) for the memory the set's query list will need, so
         that a list above the cap can be built later without an allocation on a job's path"""
         self._ctx._check(self._lib.commet_readset_reserve_cache(self._ctx._h, self._h))
+
+    def offload(self):
+        """commet_readset_offload: the set leaves the device for pageable host memory of its own; refused while a job uses it"""
+        self._check(self._lib.commet_readset_offload(self._h))
+
+    def restore(self):
+        """commet_readset_restore: the offloaded set comes back, indistinguishable from before"""
+        self._check(self._lib.commet_readset_restore(self._h))
+
+    @property
+    def resident(self):
+        return bool(self._lib.commet_readset_is_resident(self._h))
+
+    @property
+    def device_bytes(self):
+        """bytes the set's own buffers hold on the device now (0 when offloaded)"""
+        return int(self._lib.commet_readset_device_bytes(self._h))
+
+    @property
+    def packed_bytes(self):
+        """bytes the set's own buffers hold when resident, whether or not it is resident now"""
+        return int(self._lib.commet_readset_packed_bytes(self._h))
 
     def close(self):
         if getattr(self, "_h", None):

@@ -47,6 +47,7 @@
 #include "capi/context.hpp"          // commet_create / _destroy
 #include "capi/readset.hpp"          // resident read sets, host ingest
 #include "capi/images.hpp"           // packed images, HIP IPC hand-over
+#include "capi/residency.hpp"        // commet_readset_offload / _restore: a resident set leaves HBM and comes back
 #include "capi/filter.hpp"           // commet_readset_filter: length / N / Shannon / -m on a resident set
 #include "capi/index_dispatch.hpp"   // index construction: which path, its launches
 #include "capi/search_dispatch.hpp"  // search regimes: which one, its launches

@@ -102,6 +102,10 @@ void commet_destroy(commet_ctx *c)
         if (b.h_goff) (void) hipHostFree(b.h_goff);
         if (b.done) (void) hipEventDestroy(b.done);
     }
+    for (commet_ctx::AwayStage &a : c->away) {
+        if (a.h) (void) hipHostFree(a.h);
+        if (a.done) (void) hipEventDestroy(a.done);
+    }
     c->kclock.release();
     (void) dm_free(c->d_shannon);
     (void) dm_free(c->d_qres);

@@ -31,6 +31,8 @@ int commet_readset_filter(commet_ctx *c, const commet_readset *rs, int min_len, 
     if (!c || !rs || !select_out) return fail("commet_readset_filter: null argument");
     if (rs->ctx != c) return fail("the read set belongs to another context");
     if (!rs->finalized) return fail("read set not finalized");
+    SetUse use(c, rs);
+    if (use.enter()) return 1;
     const uint64_t n = rs->n_reads, bw = bitmap_words(n);
     commet_host::FilterRule rule;
     rule.min_size = min_len;

@@ -29,6 +29,8 @@ int commet_readset_save(const commet_readset *rs, const char *path)
 {
     if (!rs->finalized) return fail("read set not finalized");
     commet_ctx *c = rs->ctx;
+    SetUse use(c, rs);
+    if (use.enter()) return 1;
     HIP_OK(hipSetDevice(c->device));
     PackHeader h;
     memset(&h, 0, sizeof h);
@@ -143,6 +145,8 @@ int commet_readset_export(const commet_readset *rs, void *blob, uint64_t cap, ui
 {
     if (!rs->finalized) return fail("read set not finalized");
     commet_ctx *c = rs->ctx;
+    SetUse use(c, rs);                                   // (the set stays on the device for the length of the call)
+    if (use.enter()) return 1;
     HIP_OK(hipSetDevice(c->device));
     PackHeader h;
     memset(&h, 0, sizeof h);
@@ -168,7 +172,7 @@ int commet_readset_export(const commet_readset *rs, void *blob, uint64_t cap, ui
         bool busy;
         {
             std::lock_guard<std::mutex> lk(c->ql_mu);           // (in_job is written under this mutex)
-            busy = rs->in_job;
+            busy = rs->in_job > 1;                              // (one is this call's own)
         }
         if (busy) return fail("read set is part of a running job: export it before or after");
         HIP_OK(dm_make_shareable((void **) &w->d_planes));

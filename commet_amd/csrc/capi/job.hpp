@@ -10,6 +10,8 @@ int commet_index_reads(commet_ctx *c, const commet_readset *rs, uint64_t first, 
     if (!rs->finalized) return fail("read set not finalized");
     if (rs->ctx != c) return fail("read set belongs to another context");
     if (first > rs->n_reads || count > rs->n_reads - first) return fail("index range out of bounds");
+    SetUse use(c, rs);
+    if (use.enter()) return 1;
     HIP_OK(hipSetDevice(c->device));
     const uint64_t *d_sel = nullptr;
     if (select_bits) {
@@ -43,6 +45,8 @@ int commet_search_reads(commet_ctx *c, const commet_readset *rs, const uint8_t *
 {
     if (!rs->finalized) return fail("read set not finalized");
     if (rs->ctx != c) return fail("read set belongs to another context");
+    SetUse use(c, rs);
+    if (use.enter()) return 1;
     HIP_OK(hipSetDevice(c->device));
     const uint64_t *d_sel = nullptr;
     if (active_bits) {
@@ -90,21 +94,10 @@ int commet_index_and_search(commet_ctx *c, const commet_readset *index_rs, const
             if (search_rs[q] == search_rs[s]) return fail("search read set listed twice");
     }
     HIP_OK(hipSetDevice(c->device));
-    // the sets of this call keep their cached query lists whatever memory pressure another thread meets meanwhile
-    struct InJob {
-        commet_ctx *c;
-        const commet_readset *index_rs;
-        const commet_readset *const *srs;
-        int n;
-        void mark(bool v) const
-        {
-            std::lock_guard<std::mutex> lk(c->ql_mu);
-            index_rs->in_job = v;
-            for (int i = 0; i < n; ++i) srs[i]->in_job = v;
-        }
-        InJob(commet_ctx *c_, const commet_readset *i_, const commet_readset *const *s_, int n_) : c(c_), index_rs(i_), srs(s_), n(n_) { mark(true); }
-        ~InJob() { mark(false); }
-    } in_job(c, index_rs, search_rs, n_search);
+    // the sets of this call keep their cached query lists whatever memory pressure another thread meets meanwhile, and stay on the device
+    SetUse in_job(c, index_rs);
+    for (int s = 0; s < n_search; ++s) in_job.add(search_rs[s]);
+    if (in_job.enter()) return 1;
 
     // an input filter that selects every read is no filter (Commet.py passes all-ones bvs when nothing was filtered)
     if (index_select && all_ones(index_select, index_rs->n_reads)) index_select = nullptr;

@@ -56,22 +56,11 @@ int commet_index_many_and_search(commet_ctx *c, int n_jobs, const commet_readset
         if (index_rs[j] == search_rs) return fail("a set cannot be searched against itself in one call");
     }
     HIP_OK(hipSetDevice(c->device));
-    // the sets of this call keep their cached query lists, and are not exported, while it runs (as in commet_index_and_search; the jobs
-    // that run one by one mark their own sets again: the flag is a flag, the outer scope clears it last)
-    struct InJobs {
-        commet_ctx *c;
-        const commet_readset *const *irs;
-        const commet_readset *srs;
-        int n;
-        void mark(bool v) const
-        {
-            std::lock_guard<std::mutex> lk(c->ql_mu);
-            srs->in_job = v;
-            for (int i = 0; i < n; ++i) irs[i]->in_job = v;
-        }
-        InJobs(commet_ctx *c_, const commet_readset *const *i_, const commet_readset *s_, int n_) : c(c_), irs(i_), srs(s_), n(n_) { mark(true); }
-        ~InJobs() { mark(false); }
-    } in_jobs(c, index_rs, search_rs, n_jobs);
+    // the sets of this call keep their cached query lists, and are neither exported nor offloaded, while it runs (as in
+    // commet_index_and_search; the jobs that run one by one count their own sets again: in_job is a depth)
+    SetUse in_jobs(c, search_rs);
+    for (int j = 0; j < n_jobs; ++j) in_jobs.add(index_rs[j]);
+    if (in_jobs.enter()) return 1;
     // ---- does the fast path take the call? ---------------------------------------------------------------------------------------
     const uint8_t *ssel = search_select;
     if (ssel && all_ones(ssel, search_rs->n_reads)) ssel = nullptr;

@@ -74,6 +74,7 @@ void commet_readset_destroy(commet_readset *rs)
     (void) dm_free(rs->d_filter_ws);
     rs->ql.release();
     (void) dm_free(rs->d_len_order);
+    free(rs->h_away);
     for (int i = 0; i < 2; ++i) {
         if (rs->st[i].h_bases) (void) hipHostFree(rs->st[i].h_bases);
         if (rs->st[i].h_offs) (void) hipHostFree(rs->st[i].h_offs);
@@ -443,6 +444,8 @@ uint64_t commet_readset_num_files(const commet_readset *rs) { return rs->files.s
 int commet_readset_kmer_counts(const commet_readset *rs, uint32_t *out)
 {
     if (!rs->finalized) return fail("read set not finalized");
+    SetUse use(rs->ctx, rs);
+    if (use.enter()) return 1;
     if (host_counts(rs)) return 1;
     if (rs->n_reads) memcpy(out, rs->h_kcnt.data(), rs->n_reads * sizeof(uint32_t));
     return 0;

@@ -680,6 +680,8 @@ int commet_readset_reserve_cache(commet_ctx *c, const commet_readset *rs)
 {
     if (rs->ctx != c) return fail("read set belongs to another context");
     if (!rs->finalized) return fail("read set not finalized");
+    SetUse use(c, rs);
+    if (use.enter()) return 1;
     HIP_OK(hipSetDevice(c->device));
     uint64_t b[6];
     {

@@ -558,6 +558,13 @@ struct commet_ctx {
         hipEvent_t done = nullptr;
     };
     std::vector<IngestBuf> ingest_pool;
+    // pinned staging of commet_readset_offload / _restore (capi/residency.hpp): made on first use and kept — hipHostMalloc and
+    // hipHostFree are slow, synchronising calls; one host thread moves sets at a time (the thread that makes read sets)
+    struct AwayStage {
+        uint8_t *h = nullptr;
+        hipEvent_t done = nullptr;
+        bool inflight = false;
+    } away[2];
 
     // Derived data cached with the read sets (the tiled search's query lists, ~6 bytes per first-hit window: several times
     // the packed set itself) is accounted here and given back under pressure: least recently used lists first when the
@@ -640,12 +647,18 @@ struct commet_readset {
     mutable uint32_t ql_wanted = 0;                 // scans that would have taken the tiled search had the set's (large) list existed (tiled_ok)
     mutable std::atomic<uint64_t> ql_reserved_at{0};  // g_devmem.trims when the memory was set aside: a trim since then has given it back
     mutable std::atomic<bool> ql_reserved{false};   // the memory of the set's list waits in the library's device cache (commet_readset_reserve_cache): a list above the cap may be built
-    mutable bool in_job = false;                    // part of the commet_index_and_search call that is running: its list stays
+    mutable int in_job = 0;                         // calls that are using the set now (a depth: commet_index_many_and_search nests commet_index_and_search); written under
+                                                    // ql_mu (SetUse below).  While it is not 0 the set's list stays, and the set is neither exported nor offloaded
     mutable uint64_t *d_filter_ws = nullptr;   // scratch of commet_readset_filter: three verdict bitmaps, the count and the list of its long reads; made on first use
     mutable uint64_t filter_ws_bytes = 0;
     bool host_packed = false;                  // some reads were packed on the host (host/ingest_pack.hpp): counts come from kmer_counts_kernel
     uint32_t host_min_len = 0xFFFFFFFFu, host_max_len = 0;
     bool finalized = false;
+    // residency (capi/residency.hpp): an offloaded set keeps what defines it in pageable host memory of its own and holds no device block
+    bool resident = true;                      // written under ql_mu; false from the moment an offload is accepted until a restore is complete
+    bool moving = false;                       // an offload or a restore of the set is under way (ql_mu)
+    uint8_t *h_away = nullptr;                 // planes, then the read offsets (ragged sets), as they lay on the device
+    uint64_t away_bytes = 0;
 
     ReadsView view() const
     {
@@ -659,6 +672,35 @@ struct commet_readset {
 };
 
 namespace {
+// The sets a call works on, from its checks to its return: every entry point that reads a set's device buffers enters here.  enter()
+// refuses an offloaded set and counts the call in the sets' in_job, both under ql_mu — so commet_readset_offload, which looks at in_job
+// and clears `resident` under the same mutex, never takes the buffers from under a call that has passed its check (no check-then-act).
+struct SetUse {
+    commet_ctx *c;
+    std::vector<const commet_readset *> sets;
+    bool held = false;
+    explicit SetUse(commet_ctx *c_) : c(c_) {}
+    SetUse(commet_ctx *c_, const commet_readset *rs) : c(c_), sets(1, rs) {}
+    void add(const commet_readset *rs) { sets.push_back(rs); }
+    int enter()
+    {
+        std::lock_guard<std::mutex> lk(c->ql_mu);
+        for (const commet_readset *rs : sets)
+            if (!rs->resident) return fail("read set is offloaded");
+        for (const commet_readset *rs : sets) ++rs->in_job;
+        held = true;
+        return 0;
+    }
+    ~SetUse()
+    {
+        if (!held) return;
+        std::lock_guard<std::mutex> lk(c->ql_mu);
+        for (const commet_readset *rs : sets) --rs->in_job;
+    }
+    SetUse(const SetUse &) = delete;
+    SetUse &operator=(const SetUse &) = delete;
+};
+
 // times one kernel launch when option "kernel_timing" is on (no-op otherwise)
 struct KScope {
     commet_ctx::KernelClock &kc;

@@ -67,6 +67,12 @@ SIGNATURES = {
     "commet_readset_kmer_counts": (C.c_int, [C.c_void_p, C.c_void_p]),
     "commet_readset_filter": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_int64, C.c_void_p,
                                         C.POINTER(FilterStats)]),
+    "commet_readset_offload": (C.c_int, [C.c_void_p]),
+    "commet_readset_restore": (C.c_int, [C.c_void_p]),
+    "commet_readset_is_resident": (C.c_int, [C.c_void_p]),
+    "commet_readset_device_bytes": (C.c_uint64, [C.c_void_p]),
+    "commet_readset_packed_bytes": (C.c_uint64, [C.c_void_p]),
+    "commet_files_packed_bytes": (C.c_int, [C.POINTER(C.c_char_p), C.c_int, u64p, u64p, u64p]),
     "commet_readset_cache_bytes": (C.c_uint64, [C.c_void_p]),
     "commet_readset_drop_cache": (None, [C.c_void_p]),
     "commet_cache_stats": (C.c_int, [C.c_void_p, u64p, u64p, u64p]),

@@ -49,7 +49,7 @@ import traceback
 
 import numpy as np
 
-from . import sharding
+from . import residency, sharding
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -125,6 +125,16 @@ def default_filter_bv(path, read_file, n):
     if path is not None:
         write_filter_bv(path, read_file, n, bits)
     return bits
+
+
+def filter_command(bin_dir, read_file, bv_path, l, n, e, m, files_in_set):
+    """the filter_reads run Commet.py makes for one file of a set (Commet.py:103-121): -n and -m only when given, -m shared out over the set's files"""
+    cmd = [os.path.join(bin_dir, "filter_reads"), read_file, "-l", str(l), "-e", str(e)]
+    if n >= 0:
+        cmd += ["-n", str(n)]
+    if m >= 0:
+        cmd += ["-m", str(m / files_in_set)]
+    return cmd + ["-o", bv_path]
 
 
 def popcount(bits, n):
@@ -255,6 +265,20 @@ class HipEngine:
     def release(self, rs):
         rs.close()
 
+    # a set leaves the device and comes back (--set-budget-gb: commet_readset_offload / _restore)
+    def packed_bytes(self, files):
+        """bytes the set of these files holds on the device when resident, from a count of their records on the host"""
+        return self._api.files_packed_bytes(files)[2]
+
+    def set_bytes(self, rs):
+        return rs.packed_bytes
+
+    def offload(self, rs):
+        rs.offload()
+
+    def restore(self, rs):
+        rs.restore()
+
     def index_and_search(self, index, searches, isel, ssels):
         return self.ctx.index_and_search(index, searches, isel, ssels)
 
@@ -300,8 +324,10 @@ def _scratch_root():
 
 
 def run(input_file, out_dir, k=33, t=2, l=0, n=-1, e=0.0, m=-1, bin_dir=None, ranks=None, verbose=True,
-        engine_factory=None, progress=None, fatal_hook=None):
-    """progress: optional callable(str), called on every rank at the stages of the run (a caller that keeps stdout for itself —
+        engine_factory=None, progress=None, fatal_hook=None, set_budget_gb=None):
+    """set_budget_gb (also COMMET_MATRIX_SET_BUDGET_GB, --set-budget-gb; fractions allowed): the most device memory the packed sets may
+    hold together, in GiB — sets leave the device and come back as residency.plan says (one rank only); None: every set stays resident.
+    progress: optional callable(str), called on every rank at the stages of the run (a caller that keeps stdout for itself —
     bench.py — shows a long run is alive with it).
     fatal_hook: optional callable(str), called from a watchdog thread right before this process is ended with os._exit because a
     HIP call of it does not return (an import of another rank's set): the caller's last chance to say what it has to say"""
@@ -310,6 +336,18 @@ def run(input_file, out_dir, k=33, t=2, l=0, n=-1, e=0.0, m=-1, bin_dir=None, ra
     if ranks is None:
         ranks = sharding.Ranks()
     world, rank = ranks.world, ranks.rank
+    if set_budget_gb is None and os.environ.get("COMMET_MATRIX_SET_BUDGET_GB"):
+        set_budget_gb = float(os.environ["COMMET_MATRIX_SET_BUDGET_GB"])
+    if set_budget_gb is not None:
+        if world > 1:
+            raise ValueError(f"--set-budget-gb with {world} ranks: a set budget is kept by one rank only (run without --gpus / a launcher, "
+                             "or without the budget)")
+        try:
+            return _run_under_budget(input_file, out_dir, k, t, l, n, e, m, bin_dir, ranks, verbose, engine_factory, progress,
+                                     int(float(set_budget_gb) * (1 << 30)), t_start)
+        finally:
+            if own_ranks and sys.exc_info()[0] is None:
+                ranks.close()
     if out_dir[-1] != "/":
         out_dir += "/"
     bin_dir = bin_dir or os.path.join(HERE, "bin")
@@ -360,12 +398,7 @@ def run(input_file, out_dir, k=33, t=2, l=0, n=-1, e=0.0, m=-1, bin_dir=None, ra
         for s, j in todo:
             if owner[s] != rank:                                   # (the set's parser filters its files, too: one producer per set)
                 continue
-            cmd = [os.path.join(bin_dir, "filter_reads"), files[s][j], "-l", str(l), "-e", str(e)]
-            if n >= 0:
-                cmd += ["-n", str(n)]
-            if m >= 0:
-                cmd += ["-m", str(m / len(files[s]))]
-            cmd += ["-o", bvs[s][j]]
+            cmd = filter_command(bin_dir, files[s][j], bvs[s][j], l, n, e, m, len(files[s]))
             say("Filtering command: " + " ".join(cmd))
             cmds.append(cmd)
         # independent processes (each one multi-threaded over its file), a few at a time — and beside the parsing of
@@ -1067,6 +1100,300 @@ def run(input_file, out_dir, k=33, t=2, l=0, n=-1, e=0.0, m=-1, bin_dir=None, ra
             ranks.close()
 
 
+def _run_under_budget(input_file, out_dir, k, t, l, n, e, m, bin_dir, ranks, verbose, engine_factory, progress, budget_bytes, t_start):
+    """The matrix of one rank when the packed sets may hold at most budget_bytes of device memory together (--set-budget-gb).
+
+    The reference runs one job at a time from disk and so finishes whatever N is (Commet.py:186-240); here residency.plan orders the
+    pair chains block by block, and two threads follow it: the loader parses a set at its first "load" (its filter runs then, while
+    the set is resident), offloads it at an "evict" it will come back from (releases it at its last one) and restores it at a later
+    "load" — as far ahead of the job thread as the budget allows, one load past a pending evict at most; the job thread runs the
+    plan's jobs in order.  J2 jobs that search one reference set and J3 jobs that search one target, their sets loaded together, still
+    share passes (jobs_on_one_search_set).  Every file written is what the unconstrained run writes: a job's result does not
+    depend on when it runs, nor on how J1 of its reference set was split (residency.py)."""
+    from concurrent.futures import ThreadPoolExecutor
+    if out_dir[-1] != "/":
+        out_dir += "/"
+    bin_dir = bin_dir or os.path.join(HERE, "bin")
+    os.makedirs(out_dir, exist_ok=True)
+    names, files, bvs = parse_set_file(input_file)
+    N = len(names)
+    say = print if verbose else (lambda *a, **kw: None)
+    note = progress if progress is not None else (lambda msg: None)
+    if l < k * t and l != 0:                                      # Commet.py:509-513
+        l = k * t
+    eng = (engine_factory or HipEngine)(k, t, ranks.local_rank)
+    writer = None
+    stop = threading.Event()
+    loader = None
+    try:
+        lacking = [a for a in ("packed_bytes", "offload", "restore") if not hasattr(eng, a)]
+        if lacking:
+            raise RuntimeError(f"a set budget needs an engine whose sets can leave the device and come back: {type(eng).__name__} has no "
+                               + " / ".join(lacking))
+        # what every set will hold, before any is parsed: the plan needs all of them (HipEngine: a count of the files' records on the
+        # host, i.e. every file is read once more than without a budget — its time is reported as set_sizing_s, inside total_s)
+        w0 = time.perf_counter()
+        sizes = [int(eng.packed_bytes(fl)) for fl in files]
+        sizing_s = time.perf_counter() - w0
+        try:
+            steps = residency.plan(sizes, budget_bytes)           # (raises before any job when two sets cannot meet)
+        except ValueError as ex:
+            big = sorted(range(N), key=lambda s: (-sizes[s], s))[:2]
+            raise ValueError(f"{ex} [{', '.join(names[s] for s in big)}]") from None
+        note(f"{N} sets of {sum(sizes) / 2**30:.2f} GiB under a set budget of {budget_bytes / 2**30:.2f} GiB: "
+             f"{sum(1 for st in steps if st[0] == 'load')} loads planned")
+        # ---- filters (Commet.py:103-121), as in run(): all ones from the record counts, the device's selection, or filter_reads -----
+        tool = os.environ.get("COMMET_MATRIX_FILTER_TOOL", "0") == "1"
+        synth_filters = bvs is None and l == 0 and e == 0 and n < 0 and m < 0 and not tool
+        device_filters = bvs is None and not synth_filters and not tool and hasattr(eng, "filter_set")
+        t_filter = time.perf_counter()
+        filter_s = [0.0]
+        if bvs is None:
+            bvs = [[out_dir + os.path.basename(f) + ".bv" for f in fl] for fl in files]
+            if not synth_filters and not device_filters:
+                cmds = []
+                for s in range(N):
+                    for j in range(len(files[s])):
+                        cmds.append(filter_command(bin_dir, files[s][j], bvs[s][j], l, n, e, m, len(files[s])))
+                        say("Filtering command: " + " ".join(cmds[-1]))
+                with ThreadPoolExecutor(max_workers=int(os.environ.get("COMMET_FILTER_JOBS", "3"))) as pool:
+                    list(pool.map(lambda c: subprocess.run(c, check=True, stdout=subprocess.DEVNULL), cmds))
+                filter_s[0] = time.perf_counter() - t_filter
+
+        sets, counts, sel, considered = {}, {}, {}, {}
+        prof = dict(rank=0, pairs=N * (N - 1) // 2, sets_parsed=0, sets_loaded=0, j1_builds=0, parse_s=0.0, save_s=0.0, load_s=0.0, jobs=0,
+                    call_ms=0.0, device_ms=0.0, handover="none", backend=getattr(ranks, "backend", None), torch_loaded="torch" in sys.modules,
+                    predicted_share=1.0, job_log=[])
+        res = dict(set_budget_bytes=int(budget_bytes), set_sizing_s=sizing_s, set_loads=0, set_reloads=0, set_offloads=0, peak_set_bytes=0, reload_s=0.0)
+        last_use = {}
+        for idx, st in enumerate(steps):
+            for s in ([st[1]] if st[0] in ("load", "evict") else [st[1]] + (list(st[2]) if st[0] == "j1" else [st[2]])):
+                last_use[s] = idx
+
+        def first_load(s):
+            w0 = time.perf_counter()
+            rs = eng.parse(files[s])
+            prof["parse_s"] += time.perf_counter() - w0
+            prof["sets_parsed"] += 1
+            if hasattr(eng, "set_bytes") and eng.set_bytes(rs) > sizes[s]:
+                raise RuntimeError(f"set {names[s]} holds {eng.set_bytes(rs)} bytes on the device, {sizes[s]} were planned")
+            sets[s] = rs
+            counts[s] = eng.file_reads(rs)
+            if synth_filters:
+                parts = [(c_, default_filter_bv(b_, f_, c_)) for c_, f_, b_ in zip(counts[s], files[s], bvs[s])]
+            elif device_filters:                                  # while the set is resident, before its first offload
+                w0 = time.perf_counter()
+                bits, _ = eng.filter_set(rs, l, n, e, c_atoi(str(m / len(files[s]))) if m >= 0 else -1)
+                parts = list(zip(counts[s], split_bits(bits, counts[s])))
+                for (c_, bits_), f_, b_ in zip(parts, files[s], bvs[s]):
+                    write_filter_bv(b_, f_, c_, bits_, l, n, e)
+                filter_s[0] += time.perf_counter() - w0
+            else:
+                parts = [read_bv(b) for b in bvs[s]]
+            considered[s] = sum(popcount(b, nb) for nb, b in parts)
+            for (nb, _), c, f in zip(parts, counts[s], files[s]):
+                if nb != c:
+                    raise eng.mismatch_error(f"Number of reads in {f} and boolean vector size are not equal -> quit")
+            _, sel[s] = concat_bits(parts)
+            if considered[s] == sum(counts[s]) and os.environ.get("COMMET_MATRIX_KEEP_SEL", "0") != "1":
+                sel[s] = None
+
+        # ---- the loader thread: the plan's "load" and "evict" steps ----------------------------------------------------------------
+        cv = threading.Condition()
+        done = [False] * len(steps)                               # "load" steps carried out
+        state = dict(progress=0, resident=0, err=None)            # progress: the job thread is through every step before it
+        t0 = time.perf_counter()
+        load_end = [t0]
+
+        def do_load(idx):
+            s = steps[idx][1]
+            assert state["resident"] + sizes[s] <= budget_bytes
+            state["resident"] += sizes[s]                         # (counted before the memory is asked for)
+            res["peak_set_bytes"] = max(res["peak_set_bytes"], state["resident"])
+            if s not in sets:
+                first_load(s)
+            else:
+                w0 = time.perf_counter()
+                eng.restore(sets[s])
+                res["reload_s"] += time.perf_counter() - w0
+                res["set_reloads"] += 1
+            res["set_loads"] += 1
+            load_end[0] = time.perf_counter()
+            with cv:
+                done[idx] = True
+                cv.notify_all()
+            note(f"set {s} resident")
+
+        def load_all():
+            try:
+                for idx, st in enumerate(steps):
+                    if stop.is_set():
+                        return
+                    if st[0] == "load" and not done[idx]:
+                        do_load(idx)
+                    elif st[0] == "evict":
+                        s = st[1]
+                        while True:
+                            with cv:
+                                if state["progress"] >= idx or stop.is_set():
+                                    break
+                                nxt = idx + 1                     # one load ahead of the evict, where the budget has the room
+                                ahead = (nxt < len(steps) and steps[nxt][0] == "load" and not done[nxt]
+                                         and state["resident"] + sizes[steps[nxt][1]] <= budget_bytes)
+                                if not ahead:
+                                    cv.wait(0.05)
+                                    continue
+                            do_load(nxt)
+                        if stop.is_set():
+                            return
+                        if last_use[s] > idx:
+                            eng.offload(sets[s])
+                            res["set_offloads"] += 1
+                        else:
+                            eng.release(sets.pop(s))
+                        state["resident"] -= sizes[s]
+            except BaseException as ex:
+                with cv:
+                    state["err"] = ex
+                    cv.notify_all()
+
+        loader = threading.Thread(target=load_all, name="commet-set-loader", daemon=True)
+        loader.start()
+
+        # ---- the job thread: the plan's jobs, in its order ----------------------------------------------------------------------------
+        writer, written = ThreadPoolExecutor(2), []
+        shared, reads_searched, set_wait = {}, 0, 0.0
+        T1 = {}                                                   # (ref, i) -> J1's tags of S_i, until the pair's J2 takes them
+
+        def _acc(inf, njobs, what):
+            prof["jobs"] += njobs
+            prof["call_ms"] += inf["total_ms"]
+            prof["device_ms"] += inf["index_ms"] + inf["search_ms"]
+            prof["job_log"].append([what[0], what[1], list(what[2]), round(inf["index_ms"], 3), round(inf["search_ms"], 3), round(inf["total_ms"], 3)])
+
+        def jobs_on_one_search_set(index_ids, search_id, selections, kind):
+            if hasattr(eng, "index_many_and_search") and len(index_ids) > 1:
+                tags, st, inf = eng.index_many_and_search([sets[x] for x in index_ids], sets[search_id], selections, sel[search_id])
+                _acc(inf, len(index_ids), (kind, search_id, index_ids))
+                return [(tags[j], st[j], inf["index_ms"] / len(index_ids)) for j in range(len(index_ids))]
+            out = []
+            for x, sl in zip(index_ids, selections):
+                tags, st, inf = eng.index_and_search(sets[x], [sets[search_id]], sl, [sel[search_id]])
+                _acc(inf, 1, (kind, search_id, [x]))
+                out.append((tags[0], st[0], inf["index_ms"]))
+            return out
+
+        def leave(search, index, tags, st, index_ms, w0):
+            """the files of one J2 / J3 job: <file of `search`>_in_<index>.bv, <search>_in_<index>.log"""
+            for f, c, b in zip(files[search], counts[search], split_bits(tags, counts[search])):
+                written.append(writer.submit(write_bv, out_dir + os.path.basename(f) + "_in_" + names[index] + ".bv", f + " in " + names[index], c, b))
+            written.append(writer.submit(_log, out_dir, names[search], names[index], st, index_ms, time.perf_counter() - w0))
+            shared[(search, index)] = st["shared"]
+
+        t_jobs = time.perf_counter()
+        p = 0
+        while p < len(steps):
+            st = steps[p]
+            if st[0] == "load":
+                w0 = time.perf_counter()
+                with cv:
+                    while not done[p] and state["err"] is None:
+                        cv.wait(0.05)
+                    if state["err"] is not None:
+                        raise state["err"]
+                set_wait += time.perf_counter() - w0
+                p += 1
+            elif st[0] == "evict":
+                p += 1
+            elif st[0] == "j1":
+                _, ref, targets = st
+                q = p + 1                                         # J1 of several reference sets against ONE streamed target: they all search it
+                while len(targets) == 1 and q < len(steps) and steps[q][0] == "j1" and steps[q][2] == targets:
+                    q += 1
+                if q - p > 1:
+                    i, of_i = targets[0], [r_ for _, r_, _t in steps[p:q]]
+                    for r_, (tg, _st1, _ms) in zip(of_i, jobs_on_one_search_set(of_i, i, [sel[r_] for r_ in of_i], "J1")):
+                        T1[(r_, i)] = tg
+                    prof["j1_builds"] += len(of_i)
+                    reads_searched += considered[i] * len(of_i)
+                else:
+                    tags1, _st1, inf1 = eng.index_and_search(sets[ref], [sets[i] for i in targets], sel[ref], [sel[i] for i in targets])
+                    prof["j1_builds"] += 1
+                    reads_searched += sum(considered[i] for i in targets)
+                    _acc(inf1, 1, ("J1", ref, targets))
+                    for i, tg in zip(targets, tags1):
+                        T1[(ref, i)] = tg
+                p = q
+            else:
+                q = p
+                while q < len(steps) and steps[q][0] == "pair":
+                    q += 1
+                run_ = [(r_, i_) for _, r_, i_ in steps[p:q]]
+                w0 = time.perf_counter()
+                T2 = {}
+                a = 0
+                while a < len(run_):                              # J2: consecutive pairs of one reference set search it together
+                    b = a
+                    while b < len(run_) and run_[b][0] == run_[a][0]:
+                        b += 1
+                    ref, targets = run_[a][0], [i_ for _, i_ in run_[a:b]]
+                    for i, (tg, st2, index_ms) in zip(targets, jobs_on_one_search_set(targets, ref, [T1.pop((ref, i)) for i in targets], "J2")):
+                        leave(ref, i, tg, st2, index_ms, w0)
+                        T2[(ref, i)] = tg
+                        reads_searched += considered[ref]
+                    a = b
+                for i in dict.fromkeys(i_ for _, i_ in run_):     # J3: the pairs of one target search it together
+                    of_i = [r_ for r_, i_ in run_ if i_ == i]
+                    for ref, (tg, st3, index_ms) in zip(of_i, jobs_on_one_search_set(of_i, i, [T2.pop((r_, i)) for r_ in of_i], "J3")):
+                        leave(i, ref, tg, st3, index_ms, w0)
+                        reads_searched += considered[i]
+                p = q
+            with cv:
+                state["progress"] = p
+                cv.notify_all()
+        eng.synchronize()
+        for f in written:
+            f.result()
+        writer.shutdown()
+        writer = None
+        jobs_s = time.perf_counter() - t_jobs - set_wait
+        loader.join()
+        if state["err"] is not None:
+            raise state["err"]
+        prof["jobs_s"], prof["set_wait_s"] = jobs_s, set_wait
+        if hasattr(eng, "alloc_stats"):
+            a_ = eng.alloc_stats()
+            prof["alloc_wait_ms"], prof["fresh_device_bytes"], prof["alloc_calls"] = round(a_["wait_ms"], 1), a_["fresh_bytes"], a_["calls"]
+        mat = [[0] * N for _ in range(N)]
+        for (a, b), v in shared.items():
+            mat[a][b] = v
+        considered_all = [considered[s] for s in range(N)]
+        for s in range(N):
+            mat[s][s] = considered_all[s]
+        write_matrices(out_dir, names, considered_all, mat)
+        say("All Commet work is done")
+        total_s = time.perf_counter() - t_start
+        res.update(names=names, considered=considered_all, matrix=mat, filter_s=filter_s[0], load_s=load_end[0] - t0, filter_overlaps_load=False,
+                   load_overlaps_jobs=True, set_wait_s=set_wait, jobs_s=jobs_s, total_s=total_s, reads_searched=reads_searched, world=1,
+                   rank0_profile=prof, per_rank=[prof], j1_builds=prof["j1_builds"], reload_s=round(res["reload_s"], 6),
+                   reads_per_s=reads_searched / jobs_s if jobs_s > 0 else 0.0,
+                   reads_per_s_incl_load_and_filter=reads_searched / total_s if total_s > 0 else 0.0)
+        say(f"{reads_searched} reads searched in {jobs_s:.3f} s of jobs; {res['set_loads']} set loads ({res['set_reloads']} reloads, "
+            f"{res['reload_s']:.3f} s), at most {res['peak_set_bytes'] / 2**30:.2f} of {budget_bytes / 2**30:.2f} GiB of sets resident")
+        for rs in sets.values():
+            eng.release(rs)
+        return res
+    finally:
+        stop.set()
+        if writer is not None:
+            writer.shutdown(wait=False, cancel_futures=True)
+        failed = sys.exc_info()[0] is not None
+        if loader is not None and loader.is_alive():
+            loader.join(timeout=5.0 if failed else None)
+        if not (loader is not None and loader.is_alive()):
+            eng.close()                                           # (never under a thread that is still inside the library)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description="Filtering and full N x N intersections of read sets on MI355X GPUs")
     ap.add_argument("input_file")
@@ -1078,6 +1405,9 @@ def main(argv=None):
     ap.add_argument("-n", type=int, default=-1)
     ap.add_argument("-e", type=float, default=0)
     ap.add_argument("-m", type=int, default=-1)
+    ap.add_argument("--set-budget-gb", dest="set_budget_gb", type=float, default=None,
+                    help="most device memory the packed read sets may hold together, in GiB (fractions allowed): sets leave the device and "
+                         "come back so that a matrix larger than the device finishes; one rank only")
     ap.add_argument("--gpus", type=int, default=1,
                     help="ranks to start on this node, one per GPU (ignored under a launcher that has set WORLD_SIZE)")
     a = ap.parse_args(argv)
@@ -1085,7 +1415,7 @@ def main(argv=None):
         # this process never touches the GPU: it starts the ranks as plain child processes and leaves with their exit code
         return sharding.spawn_ranks(a.gpus, [sys.executable, "-m", "commet_amd.matrix"] + list(sys.argv[1:] if argv is None else argv))
     try:
-        res = run(a.input_file, a.directory, k=a.k, t=a.t, l=a.l, n=a.n, e=a.e, m=a.m, bin_dir=a.bin_dir)
+        res = run(a.input_file, a.directory, k=a.k, t=a.t, l=a.l, n=a.n, e=a.e, m=a.m, bin_dir=a.bin_dir, set_budget_gb=a.set_budget_gb)
         if res is not None and os.environ.get("COMMET_MATRIX_REPORT"):   # rank 0: times and per-rank profile, as JSON
             import json
             with open(os.environ["COMMET_MATRIX_REPORT"], "w") as fh:

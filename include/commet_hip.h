@@ -22,8 +22,10 @@
  *     caller; several ctxs may be used from several host threads.  One exception:
  *     read sets are made on a stream of their own, so ONE host thread may build read
  *     sets of a ctx (commet_readset_create ... commet_readset_finalize,
- *     commet_readset_from_*, commet_readset_load, commet_readset_filter) while another runs
- *     commet_index_and_search on sets that are complete (commet_amd/matrix.py does).
+ *     commet_readset_from_*, commet_readset_load, commet_readset_filter, commet_readset_offload,
+ *     commet_readset_restore) while another runs commet_index_and_search on sets that are
+ *     complete (commet_amd/matrix.py does).  That thread may offload or restore set X while the
+ *     job thread works on other sets; a set some call is using is never offloaded (refused).
  *   - there is NO CPU fallback: without a usable HIP device commet_create fails.
  */
 #ifndef COMMET_HIP_H_
@@ -149,6 +151,35 @@ int             commet_readset_filter(commet_ctx *ctx, const commet_readset *rs,
 uint64_t        commet_readset_cache_bytes(const commet_readset *rs);
 void            commet_readset_drop_cache(commet_readset *rs);
 int             commet_cache_stats(commet_ctx *ctx, uint64_t *bytes, uint64_t *budget_bytes, uint64_t *evictions);
+/* A finalized set leaves HBM and comes back.  The reference runs one job at a time from disk, so the number of sets it compares is
+ * unbounded (Commet.py:186-240, file_manager.h:117-171); a driver whose sets together exceed the device sends the ones it does not need
+ * for a while to host memory.  offload copies what defines the set — the planes, the read offsets of a ragged set; file spans and
+ * lengths are host data already — into PAGEABLE host memory the set owns (chunk-wise through two pinned staging buffers), releases every device block of the set to the library's device cache
+ * (commet_device_cache_trim gives them to the driver) and drops the set's query list and length-order list, which the next scan that
+ * wants them rebuilds as after commet_readset_drop_cache.  restore allocates again, copies back and recomputes the per-read k-mer
+ * counts on the device as commet_readset_load does: from then on the set is what it was — commet_readset_save writes the same bytes,
+ * every job gives the same tags and stats, commet_readset_filter the same bits.  When the device is out of memory restore gives the
+ * device cache and the query lists of other sets back once, then fails and leaves the set offloaded and usable.
+ * Both run on the stream that makes read sets (see Conventions).  Both are refused, with a message and nothing changed: on a set that
+ * is not finalized; offload while any call is using the set (decided and marked under one lock with the jobs' own entry: there is no
+ * window between the check and the release) or when it is offloaded already; restore when it is resident.  While a set is offloaded
+ * commet_index_reads, commet_search_reads, commet_index_and_search, commet_index_many_and_search, commet_readset_filter, _export,
+ * _save, _kmer_counts and _reserve_cache fail with "read set is offloaded"; commet_readset_destroy works in either state.
+ * is_resident: 1 when the set is on the device.  device_bytes: what the set's own buffers (not its query list: cache_bytes) hold on
+ * the device now, 0 when offloaded.  packed_bytes: what they hold when resident, in either state — a planner's number.  Both count the
+ * blocks as the library asks for them (rounded to its size classes); a block handed out by the device cache may be up to a quarter
+ * larger than asked, and the blocks an offload releases stay in that cache (at most half the device, COMMET_DEVMEM_CACHE_GB) until an
+ * allocation needs them or commet_device_cache_trim is called: a budget kept with these numbers bounds the sets that are live, the
+ * device cache comes on top and is the first thing given back under pressure.  The pinned staging buffers (2 x 8 MiB) are the
+ * context's, made on first use and kept. */
+int             commet_readset_offload(commet_readset *rs);
+int             commet_readset_restore(commet_readset *rs);
+int             commet_readset_is_resident(const commet_readset *rs);
+uint64_t        commet_readset_device_bytes(const commet_readset *rs);
+uint64_t        commet_readset_packed_bytes(const commet_readset *rs);
+/* packed_bytes of the set commet_readset_from_fasta would make of these files, from a count of their records on the host (no device
+ * is touched): what a planner needs BEFORE any set is parsed.  reads / bases / packed_bytes may each be NULL. */
+int             commet_files_packed_bytes(const char *const *paths, int n_paths, uint64_t *reads, uint64_t *bases, uint64_t *packed_bytes);
 /* Device memory the library keeps for reuse.  On this driver a hipMalloc of GBs costs 15-30 ms per GiB and now and then blocks
  * for 50-150 ms behind the hipFree of tens of GB, so blocks of 8 MiB or more that a context, a read set or a cache gives up are
  * filed per device (at most half the device, COMMET_DEVMEM_CACHE_GB) and handed to the next allocation they fit; they go back to
