@@ -9,6 +9,7 @@
 #include "index_part.hpp"
 #include "slice_search.hpp"
 #include "tile_search.hpp"
+#include "long_search.hpp"
 #include "read_filter.hpp"
 #include "read_iter.hpp"
 #include "host/fasta_source.hpp"

@@ -38,6 +38,7 @@ commet_ctx *commet_create(int device, int kmer_size, int min_hits)
     if (const char *e = getenv("COMMET_TILED")) c->tiled_mode = std::max(0, std::min(2, atoi(e)));
     if (const char *e = getenv("COMMET_MULTI_JOB")) c->multi_job = atoi(e) == 1 ? 1 : 0;   // A/B runs: 1 = commet_index_many_and_search job by job
     if (const char *e = getenv("COMMET_SPARSE_SEARCH")) c->sparse_search = std::max(0, std::min(2, atoi(e)));   // A/B runs
+    if (const char *e = getenv("COMMET_LONG_SEARCH")) c->long_search = std::max(0, std::min(2, atoi(e)));       // A/B runs
     c->job_verbose = getenv("COMMET_JOB_VERBOSE") != nullptr;
     c->ingest_verbose = getenv("COMMET_INGEST_VERBOSE") != nullptr;
     {   // query lists: half the device at most (64 GiB on small devices).  One list: 4 GiB (sets of up to ~15 M reads).  Larger lists

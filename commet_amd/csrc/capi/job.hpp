@@ -254,7 +254,7 @@ int commet_index_and_search(commet_ctx *c, const commet_readset *index_rs, const
     if (n_chunks < 2) group_cap = 1;
     if (group_cap > 4) {   // more than four filters per pass: every search set must qualify for the register-mask kernel
         bool ok8 = n_chunks > 4;
-        for (int s = 0; s < n_search && ok8; ++s) ok8 = group8_ok(c, search_rs[s]);
+        for (int s = 0; s < n_search && ok8; ++s) ok8 = group8_ok(c, search_rs[s]) || long_ok(c, search_rs[s]);   // (search_long_kernel keeps no masks)
         if (!ok8) group_cap = 4;
     }
     if (slice_gw) {
@@ -472,9 +472,14 @@ int commet_index_and_search(commet_ctx *c, const commet_readset *index_rs, const
                 al = ActiveList{nullptr, nullptr};
                 return sparse && build_active_list(c, rs, sel_s, rs->d_tags, visited[s], &al) == 0;
             };
-            const int tiled2 = (g == 2 && !sparse) ? try_tiled(2, 0, cnt) : 1;   // large set, two chunk filters: lane-a gathers served from L2, slice by slice
+            const bool lng = long_ok(c, rs);                                      // long reads: a wave per read (long_search.hpp), whatever the group
+            const int tiled2 = (g == 2 && !sparse && !lng) ? try_tiled(2, 0, cnt) : 1;   // large set, two chunk filters: lane-a gathers served from L2, slice by slice
             if (tiled2 == 2) { rc = 1; break; }
-            if (tiled2 == 0) {
+            if (lng) {
+                (void) list_for_pass();
+                if (launch_search_long(c, rs, g, g > 1 ? gs : 1, sel_s, rs->d_tags, cnt, (uint32_t) (2 * n_search), d_probes, al, visited[s])) { rc = 1; break; }
+                ++n_search_launches;
+            } else if (tiled2 == 0) {
                 if (rs->n_reads) ++n_search_launches;
             } else if (g > 1 && (gs == 8 || group_searchable(c, rs, g))) {
                 (void) list_for_pass();

@@ -66,7 +66,7 @@ int commet_index_many_and_search(commet_ctx *c, int n_jobs, const commet_readset
     if (ssel && all_ones(ssel, search_rs->n_reads)) ssel = nullptr;
     const uint64_t max_kmer = commet_max_kmer(c);
     bool fast = n_jobs >= 2 && c->k >= 2 && !c->count_probes && c->chunk_group >= 8 && c->multi_job != 1 && search_rs->n_reads > 0 &&
-                slice_words(c, 8) == 0 && group8_ok(c, search_rs) && plan_fast_ok(search_rs->files, ssel, search_rs->empty_reads, 1) &&
+                slice_words(c, 8) == 0 && group8_ok(c, search_rs) && !long_ok(c, search_rs) && plan_fast_ok(search_rs->files, ssel, search_rs->empty_reads, 1) &&
                 (search_rs->n_reads + 255) / 256 < (1ull << 24);
     struct Job {
         IndexPlan plan;

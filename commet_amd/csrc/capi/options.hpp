@@ -55,6 +55,11 @@ int commet_set_option(commet_ctx *c, const char *name, int64_t value)
         c->sparse_search = (int) value;
         return 0;
     }
+    if (!strcmp(name, "long_search")) {       // 0 auto, 1 never, 2 whenever the set has a read (tests): a wave per read for sets of long reads (long_search.hpp)
+        if (value < 0 || value > 2) return fail("long_search must be 0, 1 or 2");
+        c->long_search = (int) value;
+        return 0;
+    }
     if (!strcmp(name, "slice_mode")) {        // 0 auto (8 chunks or more, 12 <= k <= 24), 1 never, 2 whenever k allows it
         if (value < 0 || value > 2) return fail("slice_mode must be 0, 1 or 2");
         c->slice_mode = (int) value;

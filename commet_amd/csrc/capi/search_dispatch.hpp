@@ -177,6 +177,67 @@ bool group8_ok(const commet_ctx *c, const commet_readset *rs)
     return c->k >= 2 && !c->count_probes && first_hit_windows <= MASK_MAX_WIN;
 }
 
+// ---- long reads: a wave per read (long_search.hpp) ---------------------------------------------------------------
+// Sets with a read of more than MASK_MAX_WIN first-hit windows have neither the register-mask kernels nor the tiled search; the
+// lane-per-read kernels that remain walk a read end to end in one lane, and a workgroup lives as long as its longest read.
+// search_long_kernel gives a read a wave.  Auto takes it only in that region (every set with a fast path keeps it), and there
+// by the set's LONGEST read: that is what the lane-per-read kernels' time follows.  Measured at k = 32, t = 2, three A/B pairs of
+// fresh processes each (tools/long_read_bench.py; MEASUREMENTS.md, "Long reads"): the wave kernel lost every pair on sets
+// whose longest read has 450..2500 bases (one length 450 / 600 / 800 / 1000 / 1500 / 2500, ragged 300-1500, 1 % of 600 / 1000 /
+// 2000 among 100-300) and won every pair from 3000 on (1 % of 3000: 9.55 -> 7.8 ms; ragged 500-5000: 14.0 -> 10.6; one length
+// 5500: 14.1 -> 5.7; ragged 1-10 kb: 22.2 -> 8.0).  Sets of ONE length between 2500 and 5500 were not measured, hence 5000.
+constexpr uint32_t LONG_MIN_MAX_LEN = 5000;
+bool long_ok(const commet_ctx *c, const commet_readset *rs)
+{
+    if (c->long_search == 1 || c->k < 2 || rs->n_reads == 0) return false;
+    if (c->long_search == 2) return true;
+    const int64_t first_hit_windows = (int64_t) rs->max_len - (int64_t) t_eff(c, rs) * c->k + 1;
+    if (first_hit_windows <= MASK_MAX_WIN) return false;
+    return rs->max_len >= LONG_MIN_MAX_LEN;
+}
+
+
+// one pass of rs over the g filters in slots 0..g-1: nf == 1 (g == 1): slot 0's own plane A; nf = 2, 4, 8: A planes interleaved with stride nf
+int launch_search_long(commet_ctx *c, const commet_readset *rs, int g, int nf, const uint64_t *d_sel, uint64_t *d_tags,
+                       unsigned long long *d_counters, uint32_t cstride, unsigned long long *d_probes, ActiveList al, uint64_t n_launch)
+{
+    if (rs->n_reads == 0) return 0;
+    if (al.ids && n_launch == 0) return 0;
+    if (g < 1 || g > nf) return fail("internal error: %d filters in a long-read pass of stride %d", g, nf);
+    FilterGroupView fg;
+    fg.il_a = nf == 1 ? c->slot_ptr(0) : c->il_a;
+    fg.slot0 = c->filter;
+    fg.slot_words = 4 * c->plane_words;
+    fg.plane_words = c->plane_words;
+    fg.g = g;
+    const uint64_t items = al.ids ? n_launch : rs->n_reads;
+    KScope ks(c, "search_long_kernel", c->stream);
+    with_key(c->k, [&](auto key) {
+        with_value<1, 2, 4, 8>(nf, [&](auto NF) {
+            with_value<false, true>(d_probes != nullptr, [&](auto count) {
+                // persistent grid: the workgroups the device holds at once (4-8 per CU by the instantiation's registers, tools/kernel_resources.py)
+                static std::atomic<int> resident{0};
+                int wgs = resident.load(std::memory_order_relaxed);
+                if (!wgs) {
+                    int per_cu = 0, cus = 0;
+                    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, search_long_kernel<decltype(key), NF, count>, LONG_WG, 0) != hipSuccess ||
+                        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess || per_cu < 1 || cus < 1) {
+                        (void) hipGetLastError();
+                        per_cu = 4, cus = 256;
+                    }
+                    wgs = per_cu * cus;
+                    resident.store(wgs, std::memory_order_relaxed);
+                }
+                const uint64_t blocks = std::min<uint64_t>((items + 3) / 4, (uint64_t) wgs);
+                COMMET_LAUNCH((search_long_kernel<decltype(key), NF, count>), dim3((unsigned) blocks), dim3(LONG_WG), 0, c->stream, rs->view(), fg,
+                              c->k, t_eff(c, rs), d_sel, d_tags, d_counters, cstride, d_probes, al);
+            });
+        });
+    });
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
 // ---- sparse passes: the reads of a pass as a list (kernels.hpp, ActiveList) --------------------------------------
 // A pass that searches less than half of a set's reads — Commet.py's third job of a pair searches a set restricted to the first
 // job's result (Commet.py:233), ~22 % of it — walks the list of those reads (sel & ~tags, in order) instead of the set: every lane

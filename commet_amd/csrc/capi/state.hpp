@@ -550,6 +550,7 @@ struct commet_ctx {
     uint64_t max_kmer_test = 0;       // option "max_kmer": chunk size override for tests (0 = the reference's constant)
     double *d_shannon = nullptr;      // Shannon terms of the read lengths shannon_lo .. shannon_hi (commet_readset_filter, host/filter_rule.hpp), kept between calls
     uint32_t shannon_lo = 0, shannon_hi = 0;
+    int long_search = 0;              // option "long_search": 0 auto (sets outside the register-mask kernels and the tiled search whose longest read has LONG_MIN_MAX_LEN bases), 1 never, 2 whenever the set has a read (tests)
     int chunk_group = 8;              // option: chunks searched per pass (1 = one pass per chunk; more than 4 only where group8_ok)
     // pinned / device staging buffers of the parallel host ingest, kept for the next read set (hipHostMalloc is slow)
     struct IngestBuf {

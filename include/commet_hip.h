@@ -299,7 +299,8 @@ int commet_index_many_and_search(commet_ctx *ctx, int n_jobs, const commet_reads
  *   index_lanes (1/2)    2 = the chunks of a group are built on two streams (default)
  *   drop_workspaces      frees the scatter workspaces (the next bucketed index build allocates them again)
  *   chunk_group (1..8)   chunk filters searched per pass over a set (1 = the reference's order; 5..8 only
- *                        for read sets with at most 255 first-hit windows per read — reads of up to 318 bases at k = 32, t = 2 —, else 4)
+ *                        for read sets with at most 255 first-hit windows per read — reads of up to 318 bases at k = 32, t = 2 — and for
+ *                        sets that take long_search, else 4)
  *   tiled_search (0/1/2) large search sets against 1 or 2 chunk filters (25 <= k <= 34): lane-a gathers served from L2 slice
  *                        by slice from the set's cached query list; 0 = sets of 2^20 reads or more whose list fits 4 GiB,
  *                        1 = never, 2 = whenever possible
@@ -320,6 +321,11 @@ int commet_index_many_and_search(commet_ctx *ctx, int n_jobs, const commet_reads
  *                        others) walks the list of the selected, not yet tagged reads instead of the set's bitmap, so that every
  *                        lane of a wave has a read: 0 = when the host plan visits less than half of the set's reads, 1 = never,
  *                        2 = whenever a selection applies (tests)
+ *   long_search (0/1/2)  sets with a read of more than 255 first-hit windows (no register masks, no tiled search): a WAVE per read, 64
+ *                        consecutive windows per step, the reference's greedy rule on the ballots (search_long_kernel), groups of up to
+ *                        eight chunk filters: 0 = such sets whose longest read has 5000 bases or more (measured: the lane-per-read
+ *                        kernels win below 2500, the wave from 3000 on), 1 = never, 2 = whenever the set has a read (tests);
+ *                        commet_index_many_and_search runs such sets job by job
  *   ordered_scan (0/1/2) ragged sets (reads of several lengths): the first pass of a gather kernel over a whole set walks its reads in
  *                        order of their first-hit window counts (a list made once per set: a workgroup lives as long as its longest
  *                        read, its other lanes idle meanwhile): 0 = sets of 2^16 reads and more, 1 = never, 2 = any ragged set (tests)
