@@ -52,6 +52,7 @@
 #include "capi/filter.hpp"           // commet_readset_filter: length / N / Shannon / -m on a resident set
 #include "capi/index_dispatch.hpp"   // index construction: which path, its launches
 #include "capi/search_dispatch.hpp"  // search regimes: which one, its launches
+#include "capi/job_parts.hpp"        // what the two job entry points share: phase clock, timing recorder, device planner, pass steps
 #include "capi/job.hpp"              // commet_index_reads / _search_reads / _index_and_search
 #include "capi/multi.hpp"            // commet_index_many_and_search: several jobs on one search set, their filters in one pass
 #include "capi/options.hpp"          // commet_set_option, measurement hooks

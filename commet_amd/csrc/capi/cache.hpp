@@ -46,6 +46,43 @@ hipError_t dev_alloc(commet_ctx *c, void **p, size_t bytes, bool job_thread)
     return e;
 }
 
+// the same for a caller that HOLDS ql_mu (build_query_list, ensure_query_results: dev_alloc would take the mutex again): the lists of
+// sets outside the running job are given back directly
+hipError_t dev_alloc_locked(commet_ctx *c, void **p, size_t bytes)
+{
+    hipError_t e = dm_malloc(p, bytes);
+    if (e != hipErrorOutOfMemory) return e;
+    (void) hipGetLastError();
+    if (!shrink_query_lists(c, 0, false)) return e;
+    e = dm_malloc(p, bytes);
+    if (e == hipErrorOutOfMemory) (void) hipGetLastError();
+    return e;
+}
+
+// A device buffer kept with the context between calls (hipMalloc / hipFree per job cost more than the kernels that use such a
+// buffer) and grown when a job needs more: ptr holds cap elements.  0 = it holds `need` now (nothing is done, and nothing
+// synchronised, when it did already); 1 = no room: the HIP error is cleared, ptr and cap are null / 0 — never a stale capacity — and
+// the caller decides what that means (an error, another regime).  A grow waits for the context's job streams, frees, and allocates
+// alloc_elems (>= need: some callers round up).  ql_locked: the caller holds ql_mu.
+template <typename T>
+int grow_kept(commet_ctx *c, T *&ptr, uint64_t &cap, uint64_t need, uint64_t alloc_elems, bool ql_locked = false)
+{
+    if (cap >= need) return 0;
+    if (hipStreamSynchronize(c->stream) != hipSuccess || hipStreamSynchronize(c->aux_stream) != hipSuccess)
+        return fail("stream synchronize failed: %s", hipGetErrorString(hipGetLastError()));
+    (void) dm_free(ptr);
+    ptr = nullptr, cap = 0;
+    void *p = nullptr;
+    const size_t bytes = (size_t) alloc_elems * sizeof(T);
+    const hipError_t e = ql_locked ? dev_alloc_locked(c, &p, bytes) : dev_alloc(c, &p, bytes, true);
+    if (e != hipSuccess) {
+        (void) hipGetLastError();
+        return fail("cannot allocate %zu bytes of device memory: %s", bytes, hipGetErrorString(e));
+    }
+    ptr = (T *) p, cap = alloc_elems;
+    return 0;
+}
+
 // A scatter workspace (several GB that kernels sweep as a whole): allocated and touched here, not inside the first scatter launch
 // (measured: 15.6 ms instead of 2.5 ms for that one launch).  Rounds 3 and 4 picked these buffers from several timed candidates —
 // how hipMalloc backs a multi-GB buffer decides how fast kernels sweep it, drawn once per allocation: one in three ~20 % faster on

@@ -117,14 +117,9 @@ void commet_destroy(commet_ctx *c)
     (void) dm_free(c->il_a);
     (void) dm_free(c->d_jobcnt);
     (void) dm_free(c->d_plansum);
-    (void) dm_free(c->d_ids);
-    (void) dm_free(c->d_idblk);
     (void) dm_free(c->d_lo_cnt);
-    (void) dm_free(c->d_ids2);
-    (void) dm_free(c->d_idblk2);
     (void) dm_free(c->d_mtags);
-    (void) dm_free(c->d_act);
-    (void) dm_free(c->d_actblk);
+    c->sel_ids.release(), c->sel_ids2.release(), c->act_ids.release();
     c->part[0].release();
     c->part[1].release();
     if (c->aux_stream) (void) hipStreamSynchronize(c->aux_stream), (void) hipStreamDestroy(c->aux_stream);

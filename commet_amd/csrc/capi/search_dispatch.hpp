@@ -12,6 +12,31 @@ inline int t_eff(const commet_ctx *c, const commet_readset *rs)
     return (int) std::min<uint64_t>((uint64_t) c->t, (uint64_t) rs->max_len / (uint64_t) c->k + 1);
 }
 
+// first-hit windows of the set's longest read: the positions at which the first of t non-overlapping k-mers can start (< 1: no read
+// of the set can be found)
+inline int64_t first_hit_windows(const commet_ctx *c, const commet_readset *rs)
+{
+    return (int64_t) rs->max_len - (int64_t) t_eff(c, rs) * c->k + 1;
+}
+
+// a grid of one thread per read (or listed read), 256 per block, must stay below 2^24 blocks
+inline int launch_size_ok(uint64_t n_reads)
+{
+    return (n_reads + 255) / 256 < (1ull << 24) ? 0 : fail("search launch too large (>= 2^32 reads in one set)");
+}
+
+// the g filters of a pass, from slot slot0 on; their A planes interleaved (c->il_a), or one filter's own plane A (stride 1)
+inline FilterGroupView filter_group(const commet_ctx *c, int g, int slot0, bool interleaved)
+{
+    FilterGroupView fg;
+    fg.il_a = interleaved ? c->il_a : c->slot_ptr(slot0);
+    fg.slot0 = c->slot_ptr(slot0);
+    fg.slot_words = 4 * c->plane_words;
+    fg.plane_words = c->plane_words;
+    fg.g = g;
+    return fg;
+}
+
 // al.ids != nullptr: a pass over the n_launch (at most) listed reads (kernels.hpp, ActiveList) instead of the whole set
 int launch_search(commet_ctx *c, const commet_readset *rs, const uint64_t *d_sel, uint64_t *d_tags, uint64_t *d_found,
                   unsigned long long *d_counters, unsigned long long *d_probes = nullptr, ActiveList al = ActiveList{nullptr, nullptr},
@@ -19,9 +44,9 @@ int launch_search(commet_ctx *c, const commet_readset *rs, const uint64_t *d_sel
 {
     if (rs->n_reads == 0) return 0;
     if (al.ids && n_launch == 0) return 0;
-    const uint64_t blocks = ((al.ids ? n_launch : rs->n_reads) + 255) / 256;
-    if (blocks >= (1ull << 24)) return fail("search launch too large (>= 2^32 reads in one set)");
-    const dim3 g((unsigned) blocks), b(256);
+    const uint64_t items = al.ids ? n_launch : rs->n_reads;
+    if (launch_size_ok(items)) return 1;
+    const dim3 g((unsigned) ((items + 255) / 256)), b(256);
     KScope ks(c, "search_kernel", c->stream);
     with_key(c->k, [&](auto key) {
         with_value<false, true>(d_probes != nullptr, [&](auto count) {
@@ -33,7 +58,8 @@ int launch_search(commet_ctx *c, const commet_readset *rs, const uint64_t *d_sel
     return 0;
 }
 
-// makes `g` filter slots (+ the interleaved A planes with stride gs) available; slot contents are undefined after a grow
+// makes `g` filter slots (+ the interleaved A planes with stride gs) available; slot contents are undefined after a grow.  The slots
+// are not grown with grow_kept: the new block is taken BEFORE the old one goes, so that a context always has a filter
 int ensure_slots(commet_ctx *c, int g, int gs)
 {
     if (c->n_slots < g) {
@@ -53,15 +79,7 @@ int ensure_slots(commet_ctx *c, int g, int gs)
         c->filter = nf;
         c->n_slots = want;
     }
-    if (c->il_stride < gs) {
-        HIP_OK(hipStreamSynchronize(c->stream));
-        (void) dm_free(c->il_a);
-        c->il_a = nullptr;
-        c->il_stride = 0;
-        HIP_OK(dev_alloc(c, (void **) &c->il_a, (size_t) gs * c->plane_words * sizeof(uint32_t), true));
-        c->il_stride = gs;
-    }
-    return 0;
+    return grow_kept(c, c->il_a, c->il_words, (uint64_t) gs * c->plane_words, (uint64_t) gs * c->plane_words);
 }
 
 int launch_interleave(commet_ctx *c, int g, int gs)
@@ -104,7 +122,7 @@ int launch_search_group_t(commet_ctx *c, const commet_readset *rs, const FilterG
 constexpr int MASK_MAX_WIN = 255;      // (= TQ_MAX_WIN)
 inline int mask_words(const commet_ctx *c, const commet_readset *rs)
 {
-    const int64_t fhw = (int64_t) rs->max_len - (int64_t) t_eff(c, rs) * c->k + 1;
+    const int64_t fhw = first_hit_windows(c, rs);
     return fhw <= 64 ? 2 : fhw <= 96 ? 3 : fhw <= 128 ? 4 : fhw <= 192 ? 6 : 8;
 }
 template <typename F>
@@ -121,13 +139,8 @@ int launch_search_group(commet_ctx *c, const commet_readset *rs, int g, int gs, 
 {
     if (rs->n_reads == 0) return 0;
     if (al.ids && n_launch == 0) return 0;
-    if ((rs->n_reads + 255) / 256 >= (1ull << 24)) return fail("search launch too large (>= 2^32 reads in one set)");
-    FilterGroupView fg;
-    fg.il_a = c->il_a;
-    fg.slot0 = c->filter;
-    fg.slot_words = 4 * c->plane_words;
-    fg.plane_words = c->plane_words;
-    fg.g = g;
+    if (launch_size_ok(rs->n_reads)) return 1;
+    const FilterGroupView fg = filter_group(c, g, 0, true);
     if (gs == 8) {   // register masks, no LDS (group8_ok)
         const int mw_set = mask_words(c, rs);   // mask words per strand and filter: 2, 3, 4, 6 or 8
         auto launch = [&](int mw, ActiveList l, uint64_t n_l) {
@@ -173,8 +186,7 @@ bool group_searchable(const commet_ctx *c, const commet_readset *rs, int g)
 // registers (kernels.hpp: two to eight mask words per strand and filter); the probe-counting builds exist for groups of <= 4 only
 bool group8_ok(const commet_ctx *c, const commet_readset *rs)
 {
-    const int64_t first_hit_windows = (int64_t) rs->max_len - (int64_t) t_eff(c, rs) * c->k + 1;
-    return c->k >= 2 && !c->count_probes && first_hit_windows <= MASK_MAX_WIN;
+    return c->k >= 2 && !c->count_probes && first_hit_windows(c, rs) <= MASK_MAX_WIN;
 }
 
 // ---- long reads: a wave per read (long_search.hpp) ---------------------------------------------------------------
@@ -191,11 +203,8 @@ bool long_ok(const commet_ctx *c, const commet_readset *rs)
 {
     if (c->long_search == 1 || c->k < 2 || rs->n_reads == 0) return false;
     if (c->long_search == 2) return true;
-    const int64_t first_hit_windows = (int64_t) rs->max_len - (int64_t) t_eff(c, rs) * c->k + 1;
-    if (first_hit_windows <= MASK_MAX_WIN) return false;
-    return rs->max_len >= LONG_MIN_MAX_LEN;
+    return first_hit_windows(c, rs) > MASK_MAX_WIN && rs->max_len >= LONG_MIN_MAX_LEN;
 }
-
 
 // one pass of rs over the g filters in slots 0..g-1: nf == 1 (g == 1): slot 0's own plane A; nf = 2, 4, 8: A planes interleaved with stride nf
 int launch_search_long(commet_ctx *c, const commet_readset *rs, int g, int nf, const uint64_t *d_sel, uint64_t *d_tags,
@@ -204,12 +213,7 @@ int launch_search_long(commet_ctx *c, const commet_readset *rs, int g, int nf, c
     if (rs->n_reads == 0) return 0;
     if (al.ids && n_launch == 0) return 0;
     if (g < 1 || g > nf) return fail("internal error: %d filters in a long-read pass of stride %d", g, nf);
-    FilterGroupView fg;
-    fg.il_a = nf == 1 ? c->slot_ptr(0) : c->il_a;
-    fg.slot0 = c->filter;
-    fg.slot_words = 4 * c->plane_words;
-    fg.plane_words = c->plane_words;
-    fg.g = g;
+    const FilterGroupView fg = filter_group(c, g, 0, nf > 1);
     const uint64_t items = al.ids ? n_launch : rs->n_reads;
     KScope ks(c, "search_long_kernel", c->stream);
     with_key(c->k, [&](auto key) {
@@ -250,32 +254,29 @@ bool sparse_pass(const commet_ctx *c, const commet_readset *rs, const uint64_t *
     return rs->n_reads >= 4096 && selected * 2 < rs->n_reads;
 }
 
-// builds the list on the job's stream (three small launches, no synchronisation); 0 = done, 1 = no room (the caller takes the bitmap form)
-int build_active_list(commet_ctx *c, const commet_readset *rs, const uint64_t *d_sel, const uint64_t *d_tags, uint64_t selected, ActiveList *al)
+// The reads whose bit is set in d_sel (and, with d_tags, not set there) as a list in `l`, in order, built on the job's stream: three
+// small launches under one timing scope named `scope`, no synchronisation unless a buffer grows (n_ids: the reads the list may
+// hold; alloc_ids >= n_ids: what a grown buffer is sized for).  0 = built, out = the list and its length word on the device;
+// 1 = no room, or a launch failed (the caller takes the bitmap form, another path, or fails)
+int build_id_list(commet_ctx *c, commet_ctx::IdList &l, const char *scope, const commet_readset *rs, const uint64_t *d_sel, const uint64_t *d_tags,
+                  uint64_t n_ids, uint64_t alloc_ids, ActiveList *out)
 {
     const uint64_t n_words = bitmap_words(rs->n_reads), nb = (n_words + IDS_BLOCK_WORDS - 1) / IDS_BLOCK_WORDS;
-    if (c->act_cap < selected || c->actblk_cap < nb + 1) {
-        if (hipStreamSynchronize(c->stream) != hipSuccess) return 1;
-        (void) dm_free(c->d_act), (void) dm_free(c->d_actblk);
-        c->d_act = c->d_actblk = nullptr, c->act_cap = c->actblk_cap = 0;
-        const uint64_t cap = std::max<uint64_t>(selected, 1024);
-        if (dev_alloc(c, (void **) &c->d_act, cap * sizeof(uint32_t), true) != hipSuccess ||
-            dev_alloc(c, (void **) &c->d_actblk, (nb + 1) * sizeof(uint32_t), true) != hipSuccess) {
-            (void) hipGetLastError();
-            (void) dm_free(c->d_act), (void) dm_free(c->d_actblk);
-            c->d_act = c->d_actblk = nullptr;
-            return 1;
-        }
-        c->act_cap = cap, c->actblk_cap = nb + 1;
-    }
-    KScope ks(c, "active_list_kernels", c->stream);
-    COMMET_LAUNCH(sel_count_kernel, dim3((unsigned) nb), dim3(64), 0, c->stream, d_sel, n_words, c->d_actblk, d_tags);
-    COMMET_LAUNCH(sel_scan_kernel, dim3(1), dim3(1024), 0, c->stream, c->d_actblk, (uint32_t) nb);
-    COMMET_LAUNCH(sel_ids_kernel, dim3((unsigned) nb), dim3(64), 0, c->stream, d_sel, n_words, c->d_actblk, c->d_act, d_tags);
-    if (hipGetLastError() != hipSuccess) return 1;
-    al->ids = c->d_act;
-    al->n = c->d_actblk + nb;
+    if (grow_kept(c, l.ids, l.ids_cap, n_ids, alloc_ids) || grow_kept(c, l.blk, l.blk_cap, nb + 1, nb + 1)) return 1;
+    KScope ks(c, scope, c->stream);
+    COMMET_LAUNCH(sel_count_kernel, dim3((unsigned) nb), dim3(64), 0, c->stream, d_sel, n_words, l.blk, d_tags);
+    COMMET_LAUNCH(sel_scan_kernel, dim3(1), dim3(1024), 0, c->stream, l.blk, (uint32_t) nb);
+    COMMET_LAUNCH(sel_ids_kernel, dim3((unsigned) nb), dim3(64), 0, c->stream, d_sel, n_words, l.blk, l.ids, d_tags);
+    if (hipGetLastError() != hipSuccess) return fail("selection list launch failed");
+    out->ids = l.ids;
+    out->n = l.blk + nb;
     return 0;
+}
+
+// a sparse pass's list: sel & ~tags (re-made per pass: the tags of the pass before have shrunk it)
+inline int build_active_list(commet_ctx *c, const commet_readset *rs, const uint64_t *d_sel, const uint64_t *d_tags, uint64_t selected, ActiveList *al)
+{
+    return build_id_list(c, c->act_ids, "active_list_kernels", rs, d_sel, d_tags, selected, std::max<uint64_t>(selected, 1024), al);
 }
 
 // ---- ragged sets in order of their window counts (tile_search.hpp, lo_*_kernel) -------------------------------------------
@@ -291,12 +292,7 @@ bool ordered_pass(commet_ctx *c, const commet_readset *rs, const uint64_t *d_sel
         const uint32_t nb = (uint32_t) ((entries + 4095) / 4096);
         uint32_t *ids = nullptr;
         hipError_t e = dm_malloc((void **) &ids, (rs->n_reads + 8) * sizeof(uint32_t));   // (+ 1: the list's length; + 5: its segments')
-        if (e == hipSuccess && c->lo_cnt_cap < entries + 1 + nb + 2) {
-            (void) dm_free(c->d_lo_cnt);
-            c->d_lo_cnt = nullptr, c->lo_cnt_cap = 0;
-            e = dm_malloc((void **) &c->d_lo_cnt, (entries + 1 + nb + 2) * sizeof(unsigned long long));
-            if (e == hipSuccess) c->lo_cnt_cap = entries + 1 + nb + 2;
-        }
+        if (e == hipSuccess && grow_kept(c, c->d_lo_cnt, c->lo_cnt_cap, entries + 1 + nb + 2, entries + 1 + nb + 2)) e = hipErrorOutOfMemory;
         if (e != hipSuccess) {
             (void) hipGetLastError();
             (void) dm_free(ids);
@@ -361,17 +357,24 @@ constexpr int TQ_SLICE_BITS = 24;     // slice = 2^24 bits of plane A's address 
 
 constexpr int TQ_MAX_K = 34;          // 64-bit keys from k = 33 (the reference's default k, index_and_search.cpp:71): 2^(k - 24) <= 1024 slices
 
-bool tiled_ok(const commet_ctx *c, const commet_readset *rs, int g)
+// what the tiled search's kernels and the query list's layout can take, whatever the mode and the group: the one statement of it for
+// tiled_ok and query_list_blocks
+bool tiled_geometry_ok(const commet_ctx *c, const commet_readset *rs)
 {
-    if (c->tiled_mode == 1 || c->count_probes || rs->ql.failed) return false;
-    if (c->k <= TQ_SLICE_BITS || c->k > TQ_MAX_K || g < 1 || g > 2) return false;
-    const int64_t first_hit_windows = (int64_t) rs->max_len - (int64_t) t_eff(c, rs) * c->k + 1;
-    if (first_hit_windows < 1 || first_hit_windows > TQ_MAX_WIN) return false;
+    if (c->k <= TQ_SLICE_BITS || c->k > TQ_MAX_K) return false;
+    const int64_t fhw = first_hit_windows(c, rs);
+    if (fhw < 1 || fhw > TQ_MAX_WIN) return false;
     if (rs->max_len >= TQ_MAX_LEN) return false;        // (the replay keeps a piece's read extents in 16 + 16 bits; such reads pass the line above only with t in the hundreds)
     if (rs->n_reads >= (1ull << 32)) return false;
     // (rs->fhw_total: the set's first-hit windows summed over its reads — n x first_hit_windows for reads of one length, less for ragged sets)
-    if (rs->fhw_total >= (1ull << 32)) return false;   // record numbers are 32 bits (forced mode, too)
-    if (c->tiled_mode == 2) return true;
+    return rs->fhw_total < (1ull << 32);                // record numbers are 32 bits (forced mode, too)
+}
+
+bool tiled_ok(const commet_ctx *c, const commet_readset *rs, int g)
+{
+    if (c->tiled_mode == 1 || c->count_probes || rs->ql.failed) return false;
+    if (g < 1 || g > 2 || !tiled_geometry_ok(c, rs)) return false;
+    if (c->tiled_mode == 2) return true;                // (forced: sets below auto's 2^20 reads too — query_list_blocks keeps that bound in every mode)
     // auto: sets of a million reads or more whose query list (8 bytes per first-hit window) stays under 4 GiB.  Measured
     // against the fused kernels: configs[1] search 9.4 -> 8.6 ms, configs[2] jobs 1.92-1.96 -> 1.84 s.
     const uint64_t est = rs->fhw_total * 8;
@@ -404,25 +407,12 @@ int build_query_list(commet_ctx *c, const commet_readset *rs)
     // list before the probe (ev_list).  Nothing here may synchronise the device: the scan's block totals live in a scratch
     // buffer kept with the context (a hipFree would wait for the index build).
     hipStream_t ls = c->list_stream;
-    unsigned long long *d_totals = nullptr;
     // (the caller holds ql_mu: on an allocation failure here the other sets' lists are given back directly)
-    auto alloc = [&](void **ptr, size_t bytes) -> hipError_t {
-        hipError_t ae = dm_malloc(ptr, bytes);
-        if (ae != hipErrorOutOfMemory) return ae;
-        (void) hipGetLastError();
-        if (!shrink_query_lists(c, 0, false)) return ae;
-        ae = dm_malloc(ptr, bytes);
-        if (ae == hipErrorOutOfMemory) (void) hipGetLastError();
-        return ae;
-    };
+    auto alloc = [&](void **ptr, size_t bytes) { return dev_alloc_locked(c, ptr, bytes); };
     hipError_t e = alloc((void **) &ql.d_tile_off, (entries + 1) * sizeof(unsigned long long));
-    if (e == hipSuccess && c->ql_totals_cap < (uint64_t) nb + 1) {
-        (void) dm_free(c->d_ql_totals);                     // (grows a few times in a context's life)
-        c->d_ql_totals = nullptr, c->ql_totals_cap = 0;
-        e = alloc((void **) &c->d_ql_totals, ((size_t) nb + 1) * sizeof(unsigned long long));
-        if (e == hipSuccess) c->ql_totals_cap = (uint64_t) nb + 1;
-    }
-    d_totals = c->d_ql_totals;
+    // (grows a few times in a context's life)
+    if (e == hipSuccess && grow_kept(c, c->d_ql_totals, c->ql_totals_cap, (uint64_t) nb + 1, (uint64_t) nb + 1, true)) e = hipErrorOutOfMemory;
+    unsigned long long *const d_totals = c->d_ql_totals;
     if (e == hipSuccess) {
         const int t = t_eff(c, rs);
         const size_t lds = (size_t) ql.n_slices * 4;
@@ -457,7 +447,7 @@ int build_query_list(commet_ctx *c, const commet_readset *rs)
         }
         if (e == hipSuccess) {
             // reads sorted per round in LDS: as many as keep rpr * (first-hit windows per read) within TQ_FILL_CAP records
-            const int64_t fhw = std::max<int64_t>(1, (int64_t) rs->max_len - (int64_t) t * c->k + 1);
+            const int64_t fhw = std::max<int64_t>(1, first_hit_windows(c, rs));
             // (even rounds: e.g. 256 reads x 87 windows = 22 272 records are three rounds of 86 reads)
             const uint32_t rounds = (uint32_t) (((uint64_t) TQ_PIECE * (uint64_t) fhw + TQ_FILL_CAP - 1) / TQ_FILL_CAP);
             uint32_t rpr = (TQ_PIECE + rounds - 1) / rounds;
@@ -492,22 +482,12 @@ int build_query_list(commet_ctx *c, const commet_readset *rs)
 // the scan's result bytes (one per record of the set's query list); no room = this set keeps the gather kernels
 int ensure_query_results(commet_ctx *c, const commet_readset *rs)
 {
-    const uint64_t need = rs->ql.n_records;
-    if (c->qres_cap >= need && c->d_qres) return 0;
-    if (hipStreamSynchronize(c->stream) != hipSuccess) return 1;
-    (void) dm_free(c->d_qres);
-    c->d_qres = nullptr, c->qres_cap = 0;
-    hipError_t e = dm_malloc((void **) &c->d_qres, std::max<uint64_t>(need, 1));
-    if (e == hipErrorOutOfMemory) {   // (the caller holds ql_mu) give back the lists of sets outside this job and try once more
-        (void) hipGetLastError();
-        if (shrink_query_lists(c, 0, false)) e = dm_malloc((void **) &c->d_qres, std::max<uint64_t>(need, 1));
-    }
-    if (e != hipSuccess) {
-        (void) hipGetLastError();
+    const uint64_t need = std::max<uint64_t>(rs->ql.n_records, 1);
+    // (the caller holds ql_mu: the lists of sets outside this job are given back and the allocation tried once more)
+    if (grow_kept(c, c->d_qres, c->qres_cap, need, need, true)) {
         rs->ql.failed = true;
         return 1;
     }
-    c->qres_cap = need;
     return 0;
 }
 
@@ -515,11 +495,10 @@ int ensure_query_results(commet_ctx *c, const commet_readset *rs)
 // first-hit window of every read a record); false = the set does not qualify for the tiled search whatever the group
 bool query_list_blocks(const commet_ctx *c, const commet_readset *rs, uint64_t out[6])
 {
-    const int t = t_eff(c, rs);
-    const int64_t fhw = (int64_t) rs->max_len - (int64_t) t * c->k + 1;
-    if (c->k <= TQ_SLICE_BITS || c->k > TQ_MAX_K || fhw < 1 || fhw > TQ_MAX_WIN || rs->max_len >= TQ_MAX_LEN || rs->n_reads < (1ull << 20) || rs->n_reads >= (1ull << 32)) return false;
+    // (auto mode's bound of 2^20 reads holds here in EVERY mode, where tiled_ok's forced mode passes it by: memory is set aside for
+    // the sets that auto mode would scan tiled)
+    if (!tiled_geometry_ok(c, rs) || rs->n_reads < (1ull << 20)) return false;
     const uint64_t records = rs->fhw_total;                   // (an upper bound: windows with a non-ACGT base make no record)
-    if (records >= (1ull << 32)) return false;
     const uint64_t entries = ((uint64_t) 1 << (c->k - TQ_SLICE_BITS)) * ((rs->n_reads + TQ_PIECE - 1) / TQ_PIECE);
     out[0] = (entries + 1) * 8, out[1] = records * 4, out[2] = records * 2, out[3] = entries * 4, out[4] = entries * 2;
     out[5] = c->qres_cap >= records ? 0 : records;            // the context's result buffer, one byte per record
@@ -540,12 +519,7 @@ int launch_search_tiled(commet_ctx *c, const commet_readset *rs, int g, int slot
     QueryListView v;
     v.tile_off = q.d_tile_off, v.qaddr = q.d_qaddr, v.qwho = q.d_qwho, v.tstart = q.d_tstart, v.tlen = q.d_tlen;
     v.n_slices = q.n_slices, v.n_pieces = q.n_pieces, v.sbits = q.sbits;
-    FilterGroupView fg;
-    fg.slot0 = c->slot_ptr(slot0);
-    fg.il_a = g == 1 ? c->slot_ptr(slot0) : c->il_a;   // one filter: its own plane A (stride 1)
-    fg.slot_words = 4 * c->plane_words;
-    fg.plane_words = c->plane_words;
-    fg.g = g;
+    const FilterGroupView fg = filter_group(c, g, slot0, g > 1);   // one filter: its own plane A (stride 1)
     // The probe is bound by L2 gathers, the replay by L2-MISSING requests and bookkeeping: different walls, but run beside each
     // other (the set cut into runs of pieces, the replay of one beside the probe of the next on a second stream) they contend for
     // the same memory system: measured on configs[1] 19.76 ms per step in one part, 21.8 / 23.2 / 24.6 / 25.3 in 2 / 3 / 4 / 6
@@ -590,28 +564,9 @@ int ensure_slice_buffers(commet_ctx *c, int gw, uint64_t n_chunks)
 {
     const uint64_t G = 32ull * gw;
     const uint64_t stage_words = (G * 4) << (c->k - 5), table_words = ((uint64_t) 4 * gw) << c->k;
-    if (c->slice_stage_words < stage_words || c->slice_table_words < table_words || c->slice_chunks_cap < n_chunks) {
-        HIP_OK(hipStreamSynchronize(c->stream));
-        if (c->slice_stage_words < stage_words) {
-            (void) dm_free(c->slice_stage);
-            c->slice_stage = nullptr, c->slice_stage_words = 0;
-            HIP_OK(dev_alloc(c, (void **) &c->slice_stage, stage_words * 4, true));
-            c->slice_stage_words = stage_words;
-        }
-        if (c->slice_table_words < table_words) {
-            (void) dm_free(c->slice_tables);
-            c->slice_tables = nullptr, c->slice_table_words = 0;
-            HIP_OK(dev_alloc(c, (void **) &c->slice_tables, table_words * 4, true));
-            c->slice_table_words = table_words;
-        }
-        if (c->slice_chunks_cap < n_chunks) {
-            (void) dm_free(c->d_slice_chunks);
-            c->d_slice_chunks = nullptr, c->slice_chunks_cap = 0;
-            HIP_OK(dev_alloc(c, (void **) &c->d_slice_chunks, n_chunks * sizeof(SliceChunk), true));
-            c->slice_chunks_cap = n_chunks;
-        }
-    }
-    return 0;
+    return grow_kept(c, c->slice_stage, c->slice_stage_words, stage_words, stage_words) ||
+           grow_kept(c, c->slice_tables, c->slice_table_words, table_words, table_words) ||
+           grow_kept(c, c->d_slice_chunks, c->slice_chunks_cap, n_chunks, n_chunks);
 }
 
 // filters of chunks [ci, ci + g) of the plan -> bit-sliced tables (slice_search.hpp)
@@ -644,7 +599,7 @@ int launch_search_sliced(commet_ctx *c, const commet_readset *rs, int g, int gw,
                          unsigned long long *d_counters, uint32_t cstride, uint32_t block_stride = 1)
 {
     if (rs->n_reads == 0) return 0;
-    if ((rs->n_reads + 255) / 256 >= (1ull << 24)) return fail("search launch too large (>= 2^32 reads in one set)");
+    if (launch_size_ok(rs->n_reads)) return 1;
     const uint64_t blocks = (rs->n_reads + 255) / 256;
     const dim3 grid((unsigned) ((blocks + block_stride - 1) / block_stride)), block(256);
     KScope ks(c, "search_sliced_kernel", c->stream);
@@ -693,16 +648,7 @@ WidePlan wide_plan(const commet_ctx *c, uint64_t n_chunks, int slice_gw)
 int ensure_wide_tables(commet_ctx *c, const WidePlan &w)
 {
     const uint64_t words = ((uint64_t) 4 * w.rw) << c->k;
-    if (c->wide_table_words >= words) return 0;
-    HIP_OK(hipStreamSynchronize(c->stream));
-    (void) dm_free(c->wide_tables);
-    c->wide_tables = nullptr, c->wide_table_words = 0;
-    if (dev_alloc(c, (void **) &c->wide_tables, words * 4, true) != hipSuccess) {
-        (void) hipGetLastError();
-        return 1;                                                    // the caller falls back to the narrow tables
-    }
-    c->wide_table_words = words;
-    return 0;
+    return grow_kept(c, c->wide_tables, c->wide_table_words, words, words);   // 1: the caller falls back to the narrow tables
 }
 
 int launch_search_wide(commet_ctx *c, const commet_readset *rs, const WidePlan &w, int g, const uint64_t *d_sel, uint64_t *d_tags,

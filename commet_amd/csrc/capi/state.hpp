@@ -447,12 +447,20 @@ struct commet_ctx {
         }
     } part[2];
     unsigned long long *d_jobcnt = nullptr;   // per (chunk, set) counters of commet_index_and_search, kept between calls
-    uint32_t *d_ids = nullptr, *d_idblk = nullptr;   // read numbers of the index selection of the running job, in order (sel_ids_kernel)
-    uint64_t ids_cap = 0, idblk_cap = 0;
-    uint32_t *d_ids2 = nullptr, *d_idblk2 = nullptr; // the same for the second of two jobs whose chunks are built side by side (multi.hpp, two jobs per tiled scan)
-    uint64_t ids2_cap = 0, idblk2_cap = 0;
-    uint32_t *d_act = nullptr, *d_actblk = nullptr;  // read numbers of a sparse search pass (sel & ~tags, in order) and the scan's block sums
-    uint64_t act_cap = 0, actblk_cap = 0;
+    // the set bits of a bitmap over a set's reads as a list of read numbers, in order (sel_ids_kernel), and the block sums of the scan
+    // that places them (blk[blocks] = the list's length); made by build_id_list (search_dispatch.hpp), kept and grown between calls
+    struct IdList {
+        uint32_t *ids = nullptr, *blk = nullptr;
+        uint64_t ids_cap = 0, blk_cap = 0;
+        void release()
+        {
+            (void) dm_free(ids); (void) dm_free(blk);
+            *this = IdList();
+        }
+    };
+    IdList sel_ids;                                  // the index selection of the running job
+    IdList sel_ids2;                                 // the same for the second of two jobs whose chunks are built side by side (multi.hpp, two jobs per tiled scan)
+    IdList act_ids;                                  // a sparse search pass: sel & ~tags
     uint64_t *d_mtags = nullptr;                     // found flags of the jobs of a commet_index_many_and_search pass (up to eight bitmaps over the search set)
     uint64_t mtags_cap = 0;
     int multi_job = 0;                               // option: 0 = commet_index_many_and_search shares passes between jobs where it can, 1 = job by job
@@ -471,7 +479,7 @@ struct commet_ctx {
     int n_slots = 1;                  // filter slots allocated behind `filter` (chunk groups, kernels.hpp)
     int cur_slot = 0;                 // slot the index / search launch helpers work on
     uint32_t *il_a = nullptr;         // interleaved A planes of a chunk group
-    int il_stride = 0;
+    uint64_t il_words = 0;            // ... as allocated: stride x plane_words
     // option "kernel_timing": a hipEvent pair around every kernel launch of commet_index_and_search, on the stream the
     // kernel is launched on; per-kernel totals are read with commet_kernel_times (bench.py's roofline leg)
     struct KernelClock {

@@ -442,3 +442,52 @@ def test_selected_index_reads_as_a_list_match_the_round_planner(k, L, density, m
         assert np.array_equal(tags[0], found), name
         assert stats[0]["indexed"] == sum(e - a for a, e in chunks), name
     assert res["list"][1][0]["shared"] > 50
+
+
+def test_grown_buffers_serve_the_next_larger_job():
+    """the buffers a context keeps between jobs (selection list, sparse-pass list, block sums, job counters, filter slots and their
+    interleaved A planes) are grown by a larger job and serve the smaller one after it: a small job, one four times as large (more
+    chunks, so more counters and eight slots instead of four), the small one again — the small job's bits and numbers come out as
+    the first time, the large job's as in a context that ran nothing else.  A capacity left stale by a grow shows as wrong bits."""
+    import commet_amd as commet
+    from commet_amd import synth
+    k, t, L = 20, 2, 100
+    rng = np.random.default_rng(20251)
+
+    def pair(scale):      # (set 1's first quarter copies reads of set 0, synth.py)
+        idx = synth.synth_set(0, 20000 * scale, L, seed_base=1000 * scale)
+        qry = synth.synth_set(1, 30000 * scale, L, seed_base=1000 * scale)
+        isel = rng.random(20000 * scale) < 0.3
+        qsel = rng.random(30000 * scale) < 0.2
+        return idx, qry, util.bits_from_bools(isel), util.bits_from_bools(qsel)
+
+    small, large = pair(1), pair(4)
+
+    def run(ctx, sets, max_kmer):
+        (ib, io), (qb, qo), isel, qsel = sets
+        ctx.set_option("max_kmer", max_kmer)
+        irs = commet.ReadSet.from_files(ctx, [(ib, io)])
+        qrs = commet.ReadSet.from_files(ctx, [(qb, qo)])
+        tags, stats, info = ctx.index_and_search(irs, [qrs], index_select=isel, search_selects=[qsel])
+        irs.close()
+        qrs.close()
+        return tags[0].copy(), (stats[0]["indexed"], stats[0]["searched"], stats[0]["shared"]), info["n_chunks"]
+
+    def context():
+        ctx = commet.Context(k=k, t=t)
+        ctx.set_option("index_mode", 2)       # the bucketed build: it walks the selection list
+        ctx.set_option("sparse_search", 2)
+        ctx.set_option("slice_mode", 1)       # the slot loop: groups of chunks in filter slots
+        return ctx
+
+    # 0.3 x 20000 reads x 81 k-mers = 486 k k-mers: three chunks; the large job's 1.94 M in chunks of 50 k: 39, i.e. 79 counters
+    with context() as ctx:
+        first = run(ctx, small, 200000)
+        big = run(ctx, large, 50000)
+        third = run(ctx, small, 200000)
+    with context() as ctx:
+        big_alone = run(ctx, large, 50000)
+    assert first[2] == 3 and big[2] >= 9
+    assert first[1][2] > 20 and big[1][2] > 80
+    assert np.array_equal(third[0], first[0]) and third[1:] == first[1:]
+    assert np.array_equal(big[0], big_alone[0]) and big[1:] == big_alone[1:]
