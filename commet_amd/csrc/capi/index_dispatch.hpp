@@ -41,10 +41,67 @@ int launch_index_atomic(commet_ctx *c, const commet_readset *rs, uint64_t first,
     return 0;
 }
 
-bool partition_eligible(const commet_ctx *c, const commet_readset *rs)
+// ---- which construction a launch may take ----------------------------------------------------------------------------------------
+// what the geometry of the bucketed construction needs (tiles of 2^19 bits, at most 2^17 buckets)
+bool partition_geometry_ok(const commet_ctx *c) { return c->k >= 20 && c->k <= 34; }
+
+// what only the round planner needs (plan_round, MODE 0 of part_hist_kernel / part_scatter1_kernel): one whole read must fit a round of
+// S1_KEYS keys and S1_ITEMS items.  A set with a longer read ("oversize") takes the bucketed construction through the item list
+// only (LIST), whatever its shape: the list enumerates octets, not reads, and is cut into pieces of equal ITEM counts, so a set of a
+// few very long reads of one length is spread like any other (UNI cuts by reads: 20 reads would be 1 piece); the list of a job's
+// selected reads (d_ids) is not used for such a set, the list builder reads the selection bitmap itself
+bool oversize_reads(const commet_readset *rs)
 {
-    return c->k >= 20 && c->k <= 34 && (uint64_t) rs->max_kcnt * 4 <= S1_KEYS &&
-           ((uint64_t) rs->max_len + 7) / 8 <= S1_ITEMS;
+    return (uint64_t) rs->max_kcnt * 4 > S1_KEYS || ((uint64_t) rs->max_len + 7) / 8 > S1_ITEMS;
+}
+
+// word triples a chunk of `count` reads spans at most (an item holds its triple, counted from the chunk's first read, in 28 bits)
+uint64_t span_bound_of(const commet_readset *rs, uint64_t count)
+{
+    return std::min<uint64_t>((rs->n_bases >> 5) + rs->n_reads + 1, count * (((uint64_t) rs->max_len >> 5) + 2));
+}
+
+// items of a chunk at most: every selected read of it as long as the set's longest / the set's bases in octets plus one per read
+uint64_t items_bound_of(const commet_readset *rs, uint64_t sel_reads)
+{
+    return std::min<uint64_t>(sel_reads * std::max<uint64_t>(1, ((uint64_t) rs->max_len + 7) / 8), rs->n_bases / 8 + rs->n_reads) + 1;
+}
+
+// what the item list needs of a launch over `count` reads, its buffers apart (ensure_item_buffers)
+bool list_possible(const commet_ctx *c, const commet_readset *rs, uint64_t count)
+{
+    return !c->part_no_uni && c->part_list != 1 && span_bound_of(rs, count) < ITEM_MAX_TRIPLES &&
+           (count + ITEMS_BLOCK - 1) / ITEMS_BLOCK + 1 < (1ull << 24) && items_bound_of(rs, count) < (1ull << 32);
+}
+
+// auto mode (index_mode = 0) on sets with oversize reads: not before the A/B of tools/long_read_bench.py --index-mode has been run on a
+// device (MEASUREMENTS.md says what was measured); index_mode = 2 takes the build wherever partition_eligible says it can
+constexpr bool LONG_INDEX_AUTO = false;
+
+// may a launch over `count` reads of rs take the bucketed construction at all
+bool partition_eligible(const commet_ctx *c, const commet_readset *rs, uint64_t count)
+{
+    return partition_geometry_ok(c) && (!oversize_reads(rs) || list_possible(c, rs, count));
+}
+
+// the item list's buffers in a lane's workspace: `need` items, nblk block sums; false = no room (nothing is held then)
+bool ensure_item_buffers(commet_ctx *c, commet_ctx::PartWs &ws, hipStream_t stream, uint64_t need, uint64_t nblk)
+{
+    if (ws.items_cap >= need && ws.itemblk_cap >= nblk + 1) return true;
+    if (hipStreamSynchronize(stream) != hipSuccess) return false;
+    (void) dm_free(ws.items), (void) dm_free(ws.itemblk);
+    ws.items = ws.itemblk = nullptr, ws.items_cap = ws.itemblk_cap = 0;
+    const uint64_t cap = need + need / 8;
+    ws.items_set = 0;
+    if (dev_alloc(c, (void **) &ws.items, cap * sizeof(uint32_t), true) != hipSuccess ||
+        dev_alloc(c, (void **) &ws.itemblk, (nblk + 1 + 1024) * sizeof(uint32_t), true) != hipSuccess) {
+        (void) hipGetLastError();
+        (void) dm_free(ws.items), (void) dm_free(ws.itemblk);
+        ws.items = ws.itemblk = nullptr;
+        return false;
+    }
+    ws.items_cap = cap, ws.itemblk_cap = nblk + 1 + 1024;
+    return true;
 }
 
 // Bucketed construction of the filter for one chunk (index_part.hpp).  The
@@ -57,7 +114,8 @@ int launch_index_partitioned(commet_ctx *c, const commet_readset *rs, uint64_t f
                              uint64_t pos_first = 0, uint64_t pos_count = 0)
 {
     if (count == 0 || kmers == 0) return 0;
-    if (d_ids && rs->uniform_len != 0 && !c->part_no_uni && pos_count) first = pos_first, count = pos_count, d_sel = nullptr;
+    const bool oversize = oversize_reads(rs);      // a read that no round of the planner holds: the item list, cut by items (see oversize_reads)
+    if (!oversize && d_ids && rs->uniform_len != 0 && !c->part_no_uni && pos_count) first = pos_first, count = pos_count, d_sel = nullptr;
     else d_ids = nullptr;
     commet_ctx::PartWs &ws = c->part[lane];
     hipStream_t stream = lane ? c->aux_stream : c->stream;
@@ -104,55 +162,52 @@ int launch_index_partitioned(commet_ctx *c, const commet_readset *rs, uint64_t f
     }
     const bool wide = c->k > 32;
     // every read of one length and no selection bitmap: items by arithmetic, no round planning (index_part.hpp, UNI)
-    const bool uni = rs->uniform_len != 0 && d_sel == nullptr && !c->part_no_uni;   // (d_ids: positions in the list of selected reads)
+    const bool uni = !oversize && rs->uniform_len != 0 && d_sel == nullptr && !c->part_no_uni;   // (d_ids: positions in the list of selected reads)
     // ragged reads (with or without a selection bitmap): the chunk's items written out once, then walked like a fixed-length set
     // (index_part.hpp, LIST) — where an item's triple, counted from the chunk's first read, fits its 28 bits
-    const uint64_t span_bound = std::min<uint64_t>((rs->n_bases >> 5) + rs->n_reads + 1, count * (((uint64_t) rs->max_len >> 5) + 2));
-    bool list = !uni && rs->uniform_len == 0 && !c->part_no_uni && c->part_list != 1 && span_bound < ITEM_MAX_TRIPLES;
+    // (a set with oversize reads: any shape, launch_index has checked the conditions and made the buffers)
+    bool list = oversize ? list_possible(c, rs, count)
+                         : !uni && rs->uniform_len == 0 && !c->part_no_uni && c->part_list != 1 && span_bound_of(rs, count) < ITEM_MAX_TRIPLES;
     const uint32_t *d_items = nullptr, *d_nitems = nullptr;
+    const uint64_t need = items_bound_of(rs, pos_count ? pos_count : count);
     if (list) {
         const uint64_t nblk = (count + ITEMS_BLOCK - 1) / ITEMS_BLOCK;
-        // items of the chunk at most: every read of it as long as the set's longest / the set's bases in octets plus one per read
-        const uint64_t sel_reads = pos_count ? pos_count : count;
-        const uint64_t need = std::min<uint64_t>(sel_reads * std::max<uint64_t>(1, ((uint64_t) rs->max_len + 7) / 8), rs->n_bases / 8 + rs->n_reads) + 1;
         if (nblk + 1 >= (1ull << 24) || need >= (1ull << 32)) list = false;
-        if (list && (ws.items_cap < need || ws.itemblk_cap < nblk + 1)) {
-            HIP_OK(hipStreamSynchronize(stream));
-            (void) dm_free(ws.items), (void) dm_free(ws.itemblk);
-            ws.items = ws.itemblk = nullptr, ws.items_cap = ws.itemblk_cap = 0;
-            const uint64_t cap = need + need / 8;
-            ws.items_set = 0;
-            if (dev_alloc(c, (void **) &ws.items, cap * sizeof(uint32_t), true) != hipSuccess ||
-                dev_alloc(c, (void **) &ws.itemblk, (nblk + 1 + 1024) * sizeof(uint32_t), true) != hipSuccess) {
-                (void) hipGetLastError();               // no room: the round planner walks the reads, as before
-                (void) dm_free(ws.items), (void) dm_free(ws.itemblk);
-                ws.items = ws.itemblk = nullptr;
-                list = false;
-            } else {
-                ws.items_cap = cap, ws.itemblk_cap = nblk + 1 + 1024;
-            }
-        }
+        if (list && !ensure_item_buffers(c, ws, stream, need, nblk)) list = false;   // no room: the round planner walks the reads, as before
         // the list of an UNSELECTED read range is a function of the set alone: a workspace that still holds it (the same chunk of the same
         // set indexed again: the reference set of a rank's J1 calls, a benchmark's steady state) does not write it again
         // (the key is set only once the launches are queued: a failed write leaves the buffer nobody's)
         const bool held = list && !d_sel && ws.items_set == rs->uid && ws.items_first == first && ws.items_count == count && ws.items_nblk == (uint32_t) nblk;
         if (list && !held) {
             ws.items_set = 0;
-            KScope ks(c, "part_items_kernels", stream);
-            COMMET_LAUNCH(part_items_kernel<false>, dim3((unsigned) nblk), dim3(ITEMS_BLOCK), 0, stream, rs->view(), rs->d_kcnt, d_sel, first, count, c->k,
-                          ws.itemblk, ws.items);
-            COMMET_LAUNCH(sel_scan_kernel, dim3(1), dim3(1024), 0, stream, ws.itemblk, (uint32_t) nblk);
-            COMMET_LAUNCH(part_items_kernel<true>, dim3((unsigned) nblk), dim3(ITEMS_BLOCK), 0, stream, rs->view(), rs->d_kcnt, d_sel, first, count, c->k,
-                          ws.itemblk, ws.items);
+            {
+                KScope ks(c, "part_items_kernels", stream);
+                COMMET_LAUNCH(part_items_kernel<false>, dim3((unsigned) nblk), dim3(ITEMS_BLOCK), 0, stream, rs->view(), rs->d_kcnt, d_sel, first, count, c->k,
+                              ws.itemblk, ws.items);
+                COMMET_LAUNCH(sel_scan_kernel, dim3(1), dim3(1024), 0, stream, ws.itemblk, (uint32_t) nblk);
+                if (!oversize)
+                    COMMET_LAUNCH(part_items_kernel<true>, dim3((unsigned) nblk), dim3(ITEMS_BLOCK), 0, stream, rs->view(), rs->d_kcnt, d_sel, first, count,
+                                  c->k, ws.itemblk, ws.items);
+            }
+            if (oversize) {   // the list cut by items, every piece written by a whole workgroup; need < 2^32: the grid is small
+                KScope ks(c, "part_items_fill_kernel", stream);
+                COMMET_LAUNCH(part_items_fill_kernel, dim3((unsigned) ((need + ITEMS_FILL_PER_WG - 1) / ITEMS_FILL_PER_WG)), dim3(ITEMS_BLOCK), 0, stream,
+                              rs->view(), rs->d_kcnt, d_sel, first, count, c->k, ws.itemblk, (uint32_t) nblk, ws.items);
+            }
             HIP_OK(hipGetLastError());
             ws.items_set = d_sel ? 0 : rs->uid, ws.items_first = first, ws.items_count = count, ws.items_nblk = (uint32_t) nblk;
         }
         if (list) d_items = ws.items, d_nitems = ws.itemblk + nblk;
     }
     const int mode = uni ? 1 : list ? 2 : 0;
+    if (oversize && mode != 2) return fail("internal error: a set with reads of more than %u k-mers reached the round planner", S1_KEYS / 4);
     HIP_OK(hipMemsetAsync(ws.hist, 0, (g.nb + 1) * sizeof(uint32_t), stream));
     // scatter1's grid fixes how the read range is cut; hist counts with the same cut, two ranges per workgroup
-    const uint32_t grid1 = (uint32_t) std::min<uint64_t>(S1_GRID_MAX, (count + 63) / 64);
+    // (by the chunk's READ count: 64 reads of a few hundred bases are a few rounds.  With oversize reads the count says nothing — 51 reads
+    // of 2 Mbases would be one piece — so there the host's bound on the chunk's ITEMS sizes the cut, four rounds of scatter1 per piece at
+    // least; LIST cuts its pieces at equal item counts whatever their number)
+    const uint32_t grid1 = (uint32_t) std::min<uint64_t>(S1_GRID_MAX, oversize ? (need + 4 * S1_ITEMS - 1) / (4 * S1_ITEMS) : (count + 63) / 64);
+    if (oversize) c->kclock.count("part_scatter1_pieces", grid1);
     {
         const unsigned grid = (grid1 + 1) / 2;
         const bool full = g.nb <= HIST_MAX_BUCKETS;
@@ -247,13 +302,16 @@ int launch_index_partitioned(commet_ctx *c, const commet_readset *rs, uint64_t f
     return 0;
 }
 
-// whether a launch of `kmers` complete k-mers takes the bucketed construction
-bool would_partition(const commet_ctx *c, const commet_readset *rs, uint64_t kmers)
+// whether a launch of `kmers` complete k-mers over `count` reads takes the bucketed construction (every caller that prepares for one
+// — lanes, slots that need no zeroing, shared passes — asks here, and launch_index decides by the same call)
+bool would_partition(const commet_ctx *c, const commet_readset *rs, uint64_t kmers, uint64_t count)
 {
-    if (kmers == ~0ull || kmers == 0) return false;
-    if (c->index_mode == 2) return partition_eligible(c, rs);
-    if (c->index_mode == 0) return partition_eligible(c, rs) && kmers >= c->part_min_kmers;
-    return false;
+    if (kmers == ~0ull || kmers == 0 || c->index_mode == 1) return false;
+    if (!partition_eligible(c, rs, count)) return false;
+    if (c->index_mode == 2) return true;
+    // auto: sets with oversize reads follow the rule of the others only where the A/B against index_kernel says so (MEASUREMENTS.md,
+    // "Long reads: the bucketed index")
+    return (LONG_INDEX_AUTO || !oversize_reads(rs)) && kmers >= c->part_min_kmers;
 }
 
 // kmers: exact complete-k-mer count of the launch when known (enables the bucketed path), else ~0.
@@ -263,11 +321,27 @@ int launch_index(commet_ctx *c, const commet_readset *rs, uint64_t first, uint64
                  unsigned long long *d_fed, uint64_t kmers = ~0ull, bool fresh_filter = false, bool filter_zeroed = true,
                  int lane = 0, const uint32_t *d_ids = nullptr, uint64_t pos_first = 0, uint64_t pos_count = 0)
 {
+    const bool oversize = oversize_reads(rs);
     if (c->index_mode == 2) {
-        if (!partition_eligible(c, rs)) return fail("bucketed index construction needs 20 <= k <= 34 and reads of at most %u k-mers", S1_KEYS / 4);
+        if (!partition_geometry_ok(c)) return fail("bucketed index construction needs 20 <= k <= 34");
         if (kmers == ~0ull) return fail("bucketed index construction needs the k-mer count of the launch");
+        if (!partition_eligible(c, rs, count))
+            return fail("bucketed index construction needs the item list for sets with reads of more than %u k-mers (part_list = 0, part_no_uni = 0, "
+                        "a chunk of fewer than 2^28 words and 2^32 items)", S1_KEYS / 4);
     }
-    if (!would_partition(c, rs, kmers)) {
+    bool part = would_partition(c, rs, kmers, count);
+    // oversize reads: the last thing the item path needs is room for the list — asked for here, before the launch commits to a path
+    if (part && oversize && count && !ensure_item_buffers(c, c->part[lane], lane ? c->aux_stream : c->stream,
+                                                          items_bound_of(rs, pos_count ? pos_count : count), (count + ITEMS_BLOCK - 1) / ITEMS_BLOCK)) {
+        if (c->index_mode == 2) return fail("bucketed index construction needs memory for the item list of the chunk");
+        part = false;
+        if (!filter_zeroed) {     // the caller counted on a build that writes every tile: the atomic kernel must meet a zeroed filter
+            if (!fresh_filter) return fail("internal error: atomic index launch on a filter that was not zeroed");
+            if (commet_filter_reset(c)) return 1;
+            filter_zeroed = true;
+        }
+    }
+    if (!part) {
         if (!filter_zeroed) return fail("internal error: atomic index launch on a filter that was not zeroed");
         return launch_index_atomic(c, rs, first, count, d_sel, d_fed);
     }

@@ -342,7 +342,7 @@ int build_group(JobRun &j, uint64_t ci, int g, int gs)
     bool lanes = g == 2 && c->index_lanes > 1 && !c->kclock.on;   // per-kernel times are additive on one stream only
     for (int i = 0; i < g && lanes; ++i) {
         const Chunk &ch = j.plan.chunks[ci + i];
-        lanes = ch.n_reads && would_partition(c, j.index_rs, ch.kmers);
+        lanes = ch.n_reads && would_partition(c, j.index_rs, ch.kmers, ch.last - ch.first + 1);
     }
     // the second stream starts behind everything issued so far (the previous group's searches read the slots)
     if (lanes && (hipEventRecord(c->ev_fork, c->stream) != hipSuccess || hipStreamWaitEvent(c->aux_stream, c->ev_fork, 0) != hipSuccess))
@@ -351,7 +351,7 @@ int build_group(JobRun &j, uint64_t ci, int g, int gs)
         const Chunk &ch = j.plan.chunks[ci + i];
         c->cur_slot = i;
         // new BloomFilter per chunk: zero it, unless the bucketed build is going to write every tile anyway
-        const bool self_zeroing = ch.n_reads && would_partition(c, j.index_rs, ch.kmers);
+        const bool self_zeroing = ch.n_reads && would_partition(c, j.index_rs, ch.kmers, ch.last - ch.first + 1);
         if (j.tm.begin_zero() || (!self_zeroing && commet_filter_reset(c)) || j.tm.end_zero()) return 1;
         if (ch.n_reads) {
             if (launch_index(c, j.index_rs, ch.first, ch.last - ch.first + 1, j.index_sel(), nullptr, ch.kmers, true, !self_zeroing, lanes ? (i & 1) : 0,

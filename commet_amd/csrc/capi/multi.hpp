@@ -107,7 +107,7 @@ int plan_many(ManyRun &m, bool *fast)
         if (plan_index_on_device(c, rs, job.sel, max_kmer, &job.plan)) return 1;
         if (job.plan.chunks.empty() || job.plan.chunks.size() > 8) *fast = false;
         for (const Chunk &ch : job.plan.chunks)
-            if (!ch.n_reads || !would_partition(c, rs, ch.kmers)) *fast = false;    // (the bucketed build writes every tile of its slot itself)
+            if (!ch.n_reads || !would_partition(c, rs, ch.kmers, ch.last - ch.first + 1)) *fast = false;    // (the bucketed build writes every tile of its slot itself)
         job.chunk_pos = chunk_positions(job.plan);
     }
     return 0;

@@ -500,6 +500,15 @@ struct commet_ctx {
             launches[i] += 1;
             total_ms[i] += ms;
         }
+        void count(const char *name, uint64_t n)         // a launch fact that is no time: `launches` of the entry grows by n
+        {
+            if (!on) return;
+            std::lock_guard<std::mutex> lk(mu);
+            size_t i = 0;
+            while (i < names.size() && names[i] != name) ++i;
+            if (i == names.size()) names.push_back(name), launches.push_back(0), total_ms.push_back(0);
+            launches[i] += n;
+        }
         hipEvent_t get()
         {
             hipEvent_t e = nullptr;

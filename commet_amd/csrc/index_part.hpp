@@ -469,6 +469,72 @@ __global__ __launch_bounds__(ITEMS_BLOCK) void part_items_kernel(ReadsView rv, c
     for (uint32_t q = q_first; q < q_first + n; ++q) items[at++] = ((trel + (q >> 2)) << 4) | ((q & 3u) << 2) | min(q >> 2, 3u);
 }
 
+// The fill for chunks with LONG reads (a read of more than S1_KEYS / 4 k-mers or 8 x S1_ITEMS bases in the set: the host decides,
+// capi/index_dispatch.hpp).  part_items_kernel<true> writes all items of a read from one lane: 9 stores at 100 bases, 1.1 M stores
+// for a 9 Mbase contig while the other 1023 lanes of its workgroup wait, and a wave's stores are scattered over 64 reads.  Here the
+// LIST is cut, not the reads: workgroup g writes items [g x ITEMS_FILL_PER_WG, (g + 1) x ITEMS_FILL_PER_WG) of the chunk.  It finds
+// the count pass's blocks of ITEMS_BLOCK reads that overlap its range (binary search in the scanned block sums), repeats the
+// block scan of each — one thread per read, as the count pass did — keeps the reads' first items and first triples in LDS, and
+// thread t writes items t, t + NT, ... of the overlap: the item's read by binary search in the prefixes (item_lookup's search), the
+// descriptor from (trel, q).  Stores are coalesced, a long read is written by whole workgroups and by as many of them as it has
+// items to fill, and no workgroup writes more than ITEMS_FILL_PER_WG items however few reads the chunk has.
+// NT = ITEMS_BLOCK = 1024: one thread per read of a block in the scan; 8.3 KiB of LDS and a few dozen VGPRs, so two workgroups fill a
+// CU's 32 wave slots, and 16 stores per thread amortise the block scan (1024 extents, four barriers) that every workgroup repeats.
+// 32-bit quantities, for a chunk that is one read of 2^31 bases: n = 2^28 items and every block sum < 2^32 (the host checks its
+// bound on the chunk's items), trel + (q >> 2) < 2^28 (the host checks the chunk's triples), the item number is kept in 64 bits
+// because id + NT may pass 2^32.
+constexpr uint32_t ITEMS_FILL_PER_WG = 16u * ITEMS_BLOCK;
+__global__ __launch_bounds__(ITEMS_BLOCK) void part_items_fill_kernel(ReadsView rv, const uint32_t *__restrict__ kcnt,
+                                                                      const uint64_t *__restrict__ sel, uint64_t first, uint64_t count, int k,
+                                                                      const uint32_t *__restrict__ blk /* scanned: nblk + 1 */, uint32_t nblk,
+                                                                      uint32_t *__restrict__ items)
+{
+    constexpr uint32_t NT = ITEMS_BLOCK;
+    __shared__ uint32_t wsum[NT / 64];
+    __shared__ uint32_t pre[NT + 1];          // first item of every read of the block, counted from the block's first; [NT] = the block's items
+    __shared__ uint32_t rel[NT];              // the read's first triple, counted from the chunk's first read
+    const uint64_t total = blk[nblk];
+    const uint64_t i0 = (uint64_t) blockIdx.x * ITEMS_FILL_PER_WG;
+    if (i0 >= total) return;                  // (the grid is sized by the host's bound on the chunk's items)
+    const uint64_t i1 = min(total, i0 + ITEMS_FILL_PER_WG);
+    uint32_t lo = 0, hi = nblk;               // the block that holds item i0: the largest b with blk[b] <= i0
+    while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (blk[mid] <= i0) lo = mid;
+        else hi = mid;
+    }
+    uint64_t tb;
+    uint32_t l0;
+    read_extent(rv, first, tb, l0);
+    for (uint32_t b = lo; b < nblk && blk[b] < i1; ++b) {          // (uniform)
+        const uint64_t b_at = blk[b], b_end = blk[b + 1];
+        if (b_end == b_at) continue;
+        const uint64_t i = (uint64_t) b * NT + threadIdx.x, r = first + i;
+        uint32_t n = 0, len = 0;
+        uint64_t t0 = tb;
+        if (i < count) {
+            const bool on = !sel || ((sel[r >> 6] >> (r & 63)) & 1ull);
+            if (on && kcnt[r]) {
+                read_extent(rv, r, t0, len);
+                n = octets_of(len, k);
+            }
+        }
+        uint32_t tot;
+        const uint32_t ex = block_scan<NT>(n, wsum, &tot);
+        pre[threadIdx.x] = ex;
+        rel[threadIdx.x] = (uint32_t) (t0 - tb);
+        if (threadIdx.x == 0) pre[NT] = tot;
+        __syncthreads();
+        const uint64_t e = min(i1, b_end) - b_at;
+        for (uint64_t id = max(i0, b_at) - b_at + threadIdx.x; id < e; id += NT) {
+            uint32_t slot, q;
+            item_lookup(pre, NT, (uint32_t) id, k, slot, q);       // (reads without items share their successor's prefix: the search ends on the one that has the item)
+            items[b_at + id] = ((rel[slot] + (q >> 2)) << 4) | ((q & 3u) << 2) | min(q >> 2, 3u);
+        }
+        __syncthreads();
+    }
+}
+
 // an item of the list -> what the key loops take: p = the read's first triple as far as they may look back (at most three words),
 // q = the octet's number from there; the read's length is not known here (0xFFFFFFFF: the validity plane decides)
 struct ListItem {

@@ -294,7 +294,11 @@ int commet_index_many_and_search(commet_ctx *ctx, int n_jobs, const commet_reads
 /* Tunables / diagnostics, by name.  Unknown names are an error.  None of them changes a result bit, except the test
  * hook max_kmer.
  *   count_probes (0/1)   the search kernels count the filter words the REFERENCE flow loads (P_ref)
- *   index_mode (0/1/2)   0 auto, 1 atomic-OR kernel, 2 bucketed (LDS-tile) construction
+ *   index_mode (0/1/2)   0 auto, 1 atomic-OR kernel, 2 bucketed (LDS-tile) construction (20 <= k <= 34; an error where a launch cannot
+ *                        take it).  Read length is no limit: a set with a read of more than 4096 k-mers or bases is built through the
+ *                        chunk's item list, written by whole workgroups (part_items_fill_kernel) and cut into pieces of equal item
+ *                        counts; such a set needs the list (part_list = 0, part_no_uni = 0, a chunk of fewer than 2^28 words and
+ *                        2^32 items, room for the list) — without it auto takes the atomic kernel on a zeroed filter and 2 fails
  *   part_min_kmers       auto mode: chunks with fewer k-mers take the atomic kernel
  *   index_lanes (1/2)    2 = the chunks of a group are built on two streams (default)
  *   drop_workspaces      frees the scatter workspaces (the next bucketed index build allocates them again)
@@ -349,7 +353,9 @@ int commet_filter_export_reference(commet_ctx *ctx, uint8_t *out, uint64_t out_b
 int commet_last_kernel_ms(commet_ctx *ctx, double *index_ms, double *search_ms);
 /* Per-kernel device times of the commet_index_and_search calls made since option "kernel_timing" was set to 1:
  * a hipEvent pair around every launch, on the stream the kernel runs on (the chunks of a group are then built on
- * one stream, so that the durations add up).  Fills at most cap entries, *n_out = kernels seen.  Synchronises. */
+ * one stream, so that the durations add up).  Fills at most cap entries, *n_out = kernels seen.  Synchronises.
+ * One entry is no kernel: "part_scatter1_pieces" (launches = pieces the hist / scatter1 launches of long-read chunks were cut
+ * into, summed; total_ms = 0). */
 typedef struct {
     char     name[48];
     uint64_t launches;

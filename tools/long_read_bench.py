@@ -2,8 +2,12 @@
 kernel (long_search = 2, search_long_kernel): 2 x N synthetic reads, a tenth of the second set copied from the first (1 % of the
 copied bases substituted).  Workloads: reads of 450 bases (merged 2 x 250 pairs), ragged 1-10 kb, and a mixed set (99 % 100-300
 bases, 1 % 5 kb).  Every run is a fresh process; A and B alternate; the tags of the two must be the same bytes.
-  python tools/long_read_bench.py [--workloads len450 ragged_1k_10k mixed | len<N> | mixed<N> | ragged<A>_<B>] [--pairs 3] [-k 32] [-t 2] [--scale 1.0]
-Prints one JSON line per workload: search ms (min-max over the pairs), bases/s, per-kernel times, the index's share of the job."""
+  python tools/long_read_bench.py [--workloads len450 ragged_1k_10k mixed | len<N> | mixed<N> | ragged<A>_<B> | huge<N>x<L>] [--pairs 3] [-k 32] [-t 2] [--scale 1.0]
+Prints one JSON line per workload: search ms (min-max over the pairs), bases/s, per-kernel times, the index's share of the job.
+  python tools/long_read_bench.py --index-mode [--part-min-kmers N] ...
+The same protocol on the INDEX side: A = index_mode 1 (index_kernel, a lane per read, atomic ORs), B = index_mode 2 (the bucketed
+build through the item list, part_items_fill_kernel); index ms from the job's own events, the tags byte-compared, and B's launches
+checked: more than one scatter1 piece, no index_kernel.  `huge<N>x<L>`: N reads of L bases per set."""
 import argparse
 import hashlib
 import json
@@ -36,6 +40,9 @@ def workload(name):
     if name.startswith("mixed"):
         L = int(name[5:])
         return 1_000_000, lambda rng, n: np.where(rng.random(n) < 0.01, L, rng.integers(100, 301, size=n)).astype(np.int64)
+    if name.startswith("huge"):
+        n, L = (int(x) for x in name[4:].split("x"))
+        return n, lambda rng, n_: np.full(n_, L, dtype=np.int64)
     if name.startswith("ragged"):
         lo, hi = (int(x) for x in name[6:].split("_"))
         return max(20_000, 660_000_000 // (lo + hi)), lambda rng, n: rng.integers(lo, hi + 1, size=n, dtype=np.int64)
@@ -45,7 +52,7 @@ def workload(name):
 def make_pair(name, scale, d):
     """writes the two sets of a workload as .npy files (bases, offsets); both sets have the same read lengths"""
     n, lens_of = workload(name)
-    n = max(64, int(n * scale))
+    n = max(1, int(n * scale)) if name.startswith("huge") else max(64, int(n * scale))
     lens = lens_of(np.random.default_rng(11), n)
     offs = np.zeros(n + 1, dtype=np.uint64)
     np.cumsum(lens, out=offs[1:].view(np.int64))
@@ -71,6 +78,9 @@ def child(a):
     sets = [np.load(os.path.join(a.dir, f"{a.child}_{s}_bases.npy")) for s in range(2)]
     with commet_amd.Context(k=a.k, t=a.t) as ctx:
         ctx.set_option("long_search", a.long_search)
+        if a.index_mode:
+            ctx.set_option("index_mode", a.child_index_mode)
+            ctx.set_option("part_min_kmers", a.part_min_kmers)
         irs = commet_amd.ReadSet.from_files(ctx, [(sets[0], offs)])
         qrs = commet_amd.ReadSet.from_files(ctx, [(sets[1], offs)])
         ctx.index_and_search(irs, [qrs])             # warm-up: allocations, first launches
@@ -79,7 +89,16 @@ def child(a):
         kt = {k_: [c, round(ms, 3)] for k_, (c, ms) in ctx.kernel_times().items()}
         ctx.set_option("kernel_timing", 0)
         tags2, stats2, info2 = ctx.index_and_search(irs, [qrs])   # untimed kernels: the job's own event times
-    print(json.dumps({"long_search": a.long_search, "search_ms": round(info2["search_ms"], 3), "index_ms": round(info2["index_kernel_ms"], 3),
+        irs_n = irs.num_reads
+        if a.index_mode:     # a selection (every read but the last): the bucketed build's workspace cannot hold the item list from the job before
+            bits = np.full(irs_n // 8 + 1, 0xFF, dtype=np.uint8)
+            bits[(irs_n - 1) // 8] &= np.uint8(~(1 << ((irs_n - 1) % 8)) & 0xFF)
+            ctx.index_and_search(irs, [qrs], bits)
+            sel_info = ctx.index_and_search(irs, [qrs], bits)[2]
+    sel_ms = round(sel_info["index_kernel_ms"], 3) if a.index_mode else None
+    if a.index_mode and a.child_index_mode == 2:     # B must be the bucketed build, its scatter1 cut into more than one piece
+        assert "index_kernel" not in kt and kt["part_scatter1_pieces"][0] > kt["part_scatter1_kernel"][0], kt
+    print(json.dumps({"long_search": a.long_search, "index_mode": a.child_index_mode, "search_ms": round(info2["search_ms"], 3), "index_ms": round(info2["index_kernel_ms"], 3), "index_sel_ms": sel_ms,
                       "total_ms": round(info2["total_ms"], 3), "chunks": info["n_chunks"], "shared": stats[0]["shared"],
                       "kernels": kt, "tags_sha256": hashlib.sha256(tags[0].tobytes() + tags2[0].tobytes()).hexdigest()}))
 
@@ -94,6 +113,9 @@ def main():
     ap.add_argument("--child", default=None)         # (internal) workload of a measuring process
     ap.add_argument("--dir", default=None)
     ap.add_argument("--long-search", type=int, default=2)
+    ap.add_argument("--index-mode", action="store_true", help="A/B of the index side: index_mode 1 against 2")
+    ap.add_argument("--child-index-mode", type=int, default=0)   # (internal)
+    ap.add_argument("--part-min-kmers", type=int, default=1)
     a = ap.parse_args()
     if a.child:
         return child(a)
@@ -103,17 +125,28 @@ def main():
             runs = {1: [], 2: []}
             for _ in range(a.pairs):
                 for mode in (1, 2):                  # A, B, A, B, ...
-                    p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", name, "--dir", d, "--long-search", str(mode),
-                                        "-k", str(a.k), "-t", str(a.t)], capture_output=True, text=True, timeout=600)
+                    what = ["--index-mode", "--child-index-mode", str(mode), "--part-min-kmers", str(a.part_min_kmers), "--long-search", str(a.long_search)] \
+                        if a.index_mode else ["--long-search", str(mode)]
+                    p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", name, "--dir", d, "-k", str(a.k), "-t", str(a.t)] + what,
+                                       capture_output=True, text=True, timeout=600)
                     if p.returncode != 0:
                         sys.stderr.write(p.stderr[-2000:])
-                        raise SystemExit(f"{name}: the run with long_search = {mode} failed (rc {p.returncode})")
+                        raise SystemExit(f"{name}: the run with {'index_mode' if a.index_mode else 'long_search'} = {mode} failed (rc {p.returncode})")
                     runs[mode].append(json.loads(p.stdout.strip().split("\n")[-1]))
             for f in os.listdir(d):
                 os.remove(os.path.join(d, f))
             digests = {r["tags_sha256"] for m in runs for r in runs[m]}
             out = {"workload": name, "reads_per_set": n, "bases_per_set": total, "mean_len": round(total / n, 1), "k": a.k, "t": a.t,
                    "same_tags": len(digests) == 1, "shared": runs[1][0]["shared"], "chunks": runs[1][0]["chunks"]}
+            if a.index_mode:
+                for mode, key in ((1, "index_kernel"), (2, "bucketed")):
+                    out[key] = {"index_ms": [r["index_ms"] for r in runs[mode]], "index_sel_ms": [r["index_sel_ms"] for r in runs[mode]], "search_ms": [r["search_ms"] for r in runs[mode]],
+                                "kernels": runs[mode][-1]["kernels"]}
+                out["bucketed_faster_in_every_pair"] = all(b["index_ms"] < a_["index_ms"] and b["index_sel_ms"] < a_["index_sel_ms"] for a_, b in zip(runs[1], runs[2]))
+                print(json.dumps(out), flush=True)
+                if not out["same_tags"]:
+                    raise SystemExit(f"{name}: the tags of the two index constructions differ")
+                continue
             for mode, key in ((1, "lane_per_read"), (2, "wave_per_read")):
                 ms = [r["search_ms"] for r in runs[mode]]
                 out[key] = {"search_ms": ms, "search_ms_min_max": [min(ms), max(ms)], "bases_per_s": round(total / (min(ms) * 1e-3)) if min(ms) > 0 else None,
