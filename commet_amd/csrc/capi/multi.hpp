@@ -13,6 +13,12 @@
 // The fast path takes what the N x N driver's jobs are: index sets whose chunks (at most eight per job) take the bucketed
 // construction, a search set that is visited whole and qualifies for the register-mask kernel.  Anything else — and n_jobs = 1 — is
 // run job by job through commet_index_and_search itself.
+//
+// Long reads: a search set that takes the wave-per-read kernel (long_ok) shares passes the same way — search_long_kernel with a
+// job_mask, one interleaved plane-A load per window for the filters of every job of the pass (long_search.hpp) — under option
+// multi_job = 2 only: whether such a pass beats the jobs alone has not been measured (MEASUREMENTS.md, "Long reads"), so auto runs
+// them job by job.  For such a search set a chunk may take index_kernel (auto keeps it for sets with reads of more than 4096
+// k-mers): its slot is zeroed first, as in build_group.
 #pragma once
 
 
@@ -38,6 +44,7 @@ struct ManyRun {
     PhaseClock clk;
     double ph_plan = 0, ph_launch = 0, ph_wait = 0;
     JobTimer tm;                                // one bracket per pass: its builds, then its one scan
+    bool lng = false;                           // the search set takes the wave-per-read kernel (long_ok)
     ManyRun(commet_ctx *c_, int n, const commet_readset *const *irs, const uint8_t *const *isel, const commet_readset *srs, const uint8_t *ssel,
             uint8_t *const *tags, commet_pair_stats *st)
         : c(c_), n_jobs(n), index_rs(irs), index_select(isel), search_rs(srs), search_select(ssel), tags_out(tags), stats(st), tm(c_, true, 1)
@@ -82,8 +89,9 @@ int ensure_pass_buffers(ManyRun &m, int need)
 }
 
 // Does a fast path take the call?  What the N x N driver's jobs are: index sets whose chunks (at most eight per job) take the bucketed
-// construction, a search set that is visited whole and qualifies for the register-mask kernel.  Plans every job on the way (the
-// plan from per-block k-mer sums made on the device, as commet_index_and_search does)
+// construction, a search set that is visited whole and qualifies for the register-mask kernel — or, under multi_job = 2, for the
+// wave-per-read kernel, whose passes also take chunks built by index_kernel.  Plans every job on the way (the plan from per-block
+// k-mer sums made on the device, as commet_index_and_search does)
 int plan_many(ManyRun &m, bool *fast)
 {
     commet_ctx *c = m.c;
@@ -91,8 +99,9 @@ int plan_many(ManyRun &m, bool *fast)
     const uint8_t *ssel = m.search_select;
     if (ssel && all_ones(ssel, srs->n_reads)) ssel = nullptr;
     const uint64_t max_kmer = commet_max_kmer(c);
+    m.lng = long_ok(c, srs);
     *fast = m.n_jobs >= 2 && c->k >= 2 && !c->count_probes && c->chunk_group >= 8 && c->multi_job != 1 && srs->n_reads > 0 &&
-            slice_words(c, 8) == 0 && group8_ok(c, srs) && !long_ok(c, srs) && plan_fast_ok(srs->files, ssel, srs->empty_reads, 1) &&
+            slice_words(c, 8) == 0 && (m.lng ? c->multi_job == 2 : group8_ok(c, srs)) && plan_fast_ok(srs->files, ssel, srs->empty_reads, 1) &&
             (srs->n_reads + 255) / 256 < (1ull << 24);
     m.jobs.resize(*fast ? (size_t) m.n_jobs : 0);
     for (int j = 0; j < m.n_jobs && *fast; ++j) {
@@ -107,7 +116,7 @@ int plan_many(ManyRun &m, bool *fast)
         if (plan_index_on_device(c, rs, job.sel, max_kmer, &job.plan)) return 1;
         if (job.plan.chunks.empty() || job.plan.chunks.size() > 8) *fast = false;
         for (const Chunk &ch : job.plan.chunks)
-            if (!ch.n_reads || !would_partition(c, rs, ch.kmers, ch.last - ch.first + 1)) *fast = false;    // (the bucketed build writes every tile of its slot itself)
+            if (!ch.n_reads || (!m.lng && !would_partition(c, rs, ch.kmers, ch.last - ch.first + 1))) *fast = false;    // (the bucketed build writes every tile of its slot itself; a pass of long reads zeroes the slots of the others)
         job.chunk_pos = chunk_positions(job.plan);
     }
     return 0;
@@ -256,7 +265,10 @@ int run_shared_pass(ManyRun &m, int j0, int j1, int g)
         for (size_t ci = 0; ci < job.plan.chunks.size(); ++ci, ++slot) {
             const Chunk &ch = job.plan.chunks[ci];
             c->cur_slot = slot;
-            if (launch_index(c, rs, ch.first, ch.last - ch.first + 1, job.plan.dense ? nullptr : rs->d_sel, nullptr, ch.kmers, true, false, 0, d_ids,
+            // (a pass of long reads only: a chunk that takes index_kernel meets a zeroed slot, as in build_group)
+            const bool self_zeroing = would_partition(c, rs, ch.kmers, ch.last - ch.first + 1);
+            if (!self_zeroing && commet_filter_reset(c)) return 1;
+            if (launch_index(c, rs, ch.first, ch.last - ch.first + 1, job.plan.dense ? nullptr : rs->d_sel, nullptr, ch.kmers, true, !self_zeroing, 0, d_ids,
                              d_ids ? job.chunk_pos[ci] : 0, ch.n_reads))
                 return 1;
             ++m.sum.index_launches;
@@ -267,8 +279,10 @@ int run_shared_pass(ManyRun &m, int j0, int j1, int g)
     if (hipMemsetAsync(c->d_mtags, 0, (size_t) (j1 - j0) * m.tag_words() * sizeof(uint64_t), c->stream) != hipSuccess ||
         hipMemsetAsync(c->d_jobcnt, 0, 16 * sizeof(unsigned long long), c->stream) != hipSuccess)
         return fail("memset failed");
-    // (a ragged search set: its reads in order of their window counts — every job's tags start empty)
-    if (launch_group_pass(c, srs, g, 8, nullptr, c->d_mtags, c->d_jobcnt, 2, nullptr, ActiveList{nullptr, nullptr}, true, 0, job_mask, m.tag_words())) return 1;
+    // (a ragged search set: its reads in order of their window counts — every job's tags start empty; long reads: a wave per read, in the set's order)
+    if (m.lng ? launch_search_long(c, srs, g, 8, nullptr, c->d_mtags, c->d_jobcnt, 2, nullptr, ActiveList{nullptr, nullptr}, 0, job_mask, m.tag_words())
+              : launch_group_pass(c, srs, g, 8, nullptr, c->d_mtags, c->d_jobcnt, 2, nullptr, ActiveList{nullptr, nullptr}, true, 0, job_mask, m.tag_words()))
+        return 1;
     ++m.sum.search_launches;
     if (m.tm.end_set(0)) return 1;
     m.clk.lap(m.ph_launch);
@@ -334,7 +348,7 @@ int commet_index_many_and_search(commet_ctx *c, int n_jobs, const commet_readset
         std::lock_guard<std::mutex> qlk(c->ql_mu);
         if (most <= 2 && tiled_ok(c, search_rs, 2)) {
             fast = false;
-            pairs = most == 1 && c->multi_job != 2;
+            pairs = most == 1;
         }
     }
     if (!fast && !pairs) return run_alone(m, 0, n_jobs) || finish_many(m, info, nullptr);

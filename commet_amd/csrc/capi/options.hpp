@@ -45,8 +45,8 @@ int commet_set_option(commet_ctx *c, const char *name, int64_t value)
         c->tiled_mode = (int) value;
         return 0;
     }
-    if (!strcmp(name, "multi_job")) {         // 0 = commet_index_many_and_search puts the chunk filters of several jobs into one pass where it can, 1 = job by job
-        if (value < 0 || value > 1) return fail("multi_job must be 0 or 1");
+    if (!strcmp(name, "multi_job")) {         // 0 = commet_index_many_and_search puts the chunk filters of several jobs into one pass where it can, 1 = job by job, 2 = as 0, and search sets of long reads share passes too (capi/multi.hpp)
+        if (value < 0 || value > 2) return fail("multi_job must be 0, 1 or 2");
         c->multi_job = (int) value;
         return 0;
     }

@@ -207,32 +207,48 @@ bool long_ok(const commet_ctx *c, const commet_readset *rs)
 }
 
 // one pass of rs over the g filters in slots 0..g-1: nf == 1 (g == 1): slot 0's own plane A; nf = 2, 4, 8: A planes interleaved with stride nf
+// job_mask != 0 (nf == 8 only, no selection, list or probe counting): the g filters belong to several jobs, bit i = filter i opens one;
+// job j's tags at d_tags + j * job_tag_words (zeroed by the caller)
 int launch_search_long(commet_ctx *c, const commet_readset *rs, int g, int nf, const uint64_t *d_sel, uint64_t *d_tags,
-                       unsigned long long *d_counters, uint32_t cstride, unsigned long long *d_probes, ActiveList al, uint64_t n_launch)
+                       unsigned long long *d_counters, uint32_t cstride, unsigned long long *d_probes, ActiveList al, uint64_t n_launch,
+                       uint32_t job_mask = 0, uint64_t job_tag_words = 0)
 {
     if (rs->n_reads == 0) return 0;
     if (al.ids && n_launch == 0) return 0;
     if (g < 1 || g > nf) return fail("internal error: %d filters in a long-read pass of stride %d", g, nf);
+    const bool jobs = job_mask != 0 || job_tag_words != 0;
+    if (jobs && (nf != 8 || d_sel || al.ids || d_probes || !(job_mask & 1u) || (job_mask >> g)))
+        return fail("internal error: a long-read pass of several jobs (mask %#x, %d filters) of stride %d, or with a selection, a list or probe counting", job_mask, g, nf);
     const FilterGroupView fg = filter_group(c, g, 0, nf > 1);
     const uint64_t items = al.ids ? n_launch : rs->n_reads;
     KScope ks(c, "search_long_kernel", c->stream);
+    // persistent grid: the workgroups the device holds at once (4-8 per CU by the instantiation's registers, tools/kernel_resources.py)
+    auto resident_wgs = [&](std::atomic<int> &resident, auto kernel) {
+        int wgs = resident.load(std::memory_order_relaxed);
+        if (!wgs) {
+            int per_cu = 0, cus = 0;
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, LONG_WG, 0) != hipSuccess ||
+                hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess || per_cu < 1 || cus < 1) {
+                (void) hipGetLastError();
+                per_cu = 4, cus = 256;
+            }
+            wgs = per_cu * cus;
+            resident.store(wgs, std::memory_order_relaxed);
+        }
+        return std::min<uint64_t>((items + 3) / 4, (uint64_t) wgs);
+    };
     with_key(c->k, [&](auto key) {
+        if (jobs) {
+            static std::atomic<int> resident{0};
+            const uint64_t blocks = resident_wgs(resident, search_long_kernel<decltype(key), 8, false, true>);
+            COMMET_LAUNCH((search_long_kernel<decltype(key), 8, false, true>), dim3((unsigned) blocks), dim3(LONG_WG), 0, c->stream, rs->view(), fg,
+                          c->k, t_eff(c, rs), d_tags, d_counters, cstride, job_mask, job_tag_words);
+            return;
+        }
         with_value<1, 2, 4, 8>(nf, [&](auto NF) {
             with_value<false, true>(d_probes != nullptr, [&](auto count) {
-                // persistent grid: the workgroups the device holds at once (4-8 per CU by the instantiation's registers, tools/kernel_resources.py)
                 static std::atomic<int> resident{0};
-                int wgs = resident.load(std::memory_order_relaxed);
-                if (!wgs) {
-                    int per_cu = 0, cus = 0;
-                    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, search_long_kernel<decltype(key), NF, count>, LONG_WG, 0) != hipSuccess ||
-                        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess || per_cu < 1 || cus < 1) {
-                        (void) hipGetLastError();
-                        per_cu = 4, cus = 256;
-                    }
-                    wgs = per_cu * cus;
-                    resident.store(wgs, std::memory_order_relaxed);
-                }
-                const uint64_t blocks = std::min<uint64_t>((items + 3) / 4, (uint64_t) wgs);
+                const uint64_t blocks = resident_wgs(resident, search_long_kernel<decltype(key), NF, count>);
                 COMMET_LAUNCH((search_long_kernel<decltype(key), NF, count>), dim3((unsigned) blocks), dim3(LONG_WG), 0, c->stream, rs->view(), fg,
                               c->k, t_eff(c, rs), d_sel, d_tags, d_counters, cstride, d_probes, al);
             });

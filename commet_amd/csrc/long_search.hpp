@@ -19,6 +19,9 @@
 // only if s <= len - (t - count) * k.  That bound grows with every hit, so it is applied by the wave between blocks and after
 // each hit, never per lane within a block.
 //
+// Several jobs in a pass (commet_index_many_and_search, capi/multi.hpp): a second kernel template of the same name and body with a
+// job_mask — see JOBS below.
+//
 // Included by capi.hip behind kernels.hpp (KeyCtx, ItemWords, psi_a, probe_bcd_*, ActiveList); not meant to stand alone.
 #pragma once
 
@@ -45,174 +48,54 @@ template <int NF> __device__ __forceinline__ void long_load_a(const uint32_t *__
     }
 }
 
+// (several jobs in a pass) the filters of filter i's job behind it, and in front of it.  opens: bit j = filter j opens a job (bit 0
+// is set); all: the filters of the pass.  Uniform over the wave
+__device__ __forceinline__ uint32_t job_behind(uint32_t opens, uint32_t all, int i)
+{
+    const uint32_t above = all & ~((2u << i) - 1u);
+    const uint32_t next = opens & above;                   // the jobs opened behind i: the lowest of them ends i's job
+    return next ? above & ((next & (0u - next)) - 1u) : above;
+}
+__device__ __forceinline__ uint32_t job_before(uint32_t opens, int i)
+{
+    const uint32_t upto = opens & ((2u << i) - 1u);        // the jobs opened up to i: the highest of them is i's job
+    return ((1u << i) - 1u) & ~((1u << (31 - __clz((int) upto))) - 1u);
+}
+
 // fg.il_a: the A planes of the pass interleaved with stride NF (NF == 1: the filter's own plane A); fg.g <= NF filters.
 // The grid is persistent: wave w of the launch takes items w, w + waves, ... of the pass — reads of the set (sel and tags decide) or
 // entries of its ActiveList.  Found flags leave as one atomic OR per found read (the reads of a tag word belong to different waves);
 // counters as in search_group_kernel, {scanned_i, found_i} at counters[i * cstride], added once per wave at its end.
+//
+// JOBS (NF == 8, no probe counting): the filters of the pass belong to SEVERAL jobs that search this one set (capi/multi.hpp), the
+// contract of search_group8_kernel: bit i of job_mask = filter i opens a job, a job's filters are consecutive slots, job j's found
+// flags go to tags + j * job_tag_words (zeroed by the host: a job never spans passes); tags is not read, sel is null, there is no
+// list.  The plane-A load of a window serves every job; the rule "not searched in the chunks behind the one that tagged it" holds
+// within a job only, so `found` is a mask over the filter bits (the lowest bit of a job's filters is the chunk that tagged the read
+// for that job) and a hit closes the later filters of its own job alone: the read stays in flight while any job wants an answer.
+// The jobs are uniform over the wave: job_behind / job_before are scalar work on job_mask, no per-job arrays.
 template <typename W, int NF, bool COUNT>
 __global__ __launch_bounds__(LONG_WG) void search_long_kernel(ReadsView rv, FilterGroupView fg, int k, int t, const uint64_t *__restrict__ sel,
                                                               uint64_t *__restrict__ tags, unsigned long long *__restrict__ counters,
                                                               uint32_t cstride, unsigned long long *__restrict__ probe_counter, ActiveList al)
 {
-    const int lane = threadIdx.x & 63;
-    const uint64_t wave0 = (uint64_t) blockIdx.x * (LONG_WG / 64) + (threadIdx.x >> 6);
-    const uint64_t n_waves = (uint64_t) gridDim.x * (LONG_WG / 64);
-    const uint64_t n_items = al.ids ? (uint64_t) *al.n : rv.n;
-    const KeyCtx<W> kc(k);
-    const uint32_t all = (fg.g >= 32) ? ~0u : ((1u << fg.g) - 1u);   // filters of the pass, one bit each
-    unsigned long long probes = 0;
-    uint32_t n_scanned[NF], n_found[NF];
-#pragma unroll
-    for (int i = 0; i < NF; ++i) n_scanned[i] = 0, n_found[i] = 0;
+    constexpr bool JOBS = false;
+    constexpr uint32_t job_mask = 0;
+    constexpr uint64_t job_tag_words = 0;
+#include "long_search_body.hpp"
+}
 
-    for (uint64_t item = wave0; item < n_items; item += n_waves) {   // (uniform per wave)
-        uint64_t r = item;
-        if (al.ids) {
-            r = (uint64_t) al.ids[item];
-        } else {
-            const uint64_t selw = sel ? sel[r >> 6] : ~0ull, tagw = tags ? tags[r >> 6] : 0ull;
-            if (!(((selw & ~tagw) >> (r & 63ull)) & 1ull)) continue;
-        }
-        uint64_t t0;
-        uint32_t len;
-        read_extent(rv, r, t0, len);
-        const uint32_t *p = rv.planes + 3 * t0;
-        const int n_words = (int) ((len + 31u) >> 5);
-        const int n_win = (int) len - k + 1;               // windows of the read, by their start (<= 0: none)
-        int found_chunk = -1;                              // lowest filter of the pass that tagged the read
-        unsigned long long fprobes[NF];                    // (COUNT) what the reference loads for filter i if it gets that far
-#pragma unroll
-        for (int i = 0; i < NF; ++i) fprobes[i] = 0;
-        uint32_t want = all;                               // filters whose answer still matters: below the lowest one that found the read
-        for (int strand = 0; strand < 2 && want; ++strand) {
-            int next_free[NF], count[NF];
-#pragma unroll
-            for (int i = 0; i < NF; ++i) next_free[i] = 0, count[i] = 0;
-            uint32_t open = want;                          // filters whose scan of this strand goes on
-            if constexpr (!COUNT) {
-                if ((int64_t) len < (int64_t) t * k) open = 0;   // no room for t windows
-            }
-            for (int base = 0; base < n_win && open; base += 64) {
-                // the read's words this block's windows stand on, one per lane, handed out by shuffles
-                const int w0 = base >> 5;
-                uint32_t staged = 0;
-                {
-                    const int wi = w0 - 2 + lane / 3;
-                    if (lane < 3 * LONG_STAGE_WORDS && wi >= 0 && wi < n_words) staged = p[3 * wi + lane % 3];
-                }
-                const int s = base + lane, q = s + k - 1;
-                // (every lane takes every shuffle: a lane that sat out would hand out nothing.  Words in front of the read are staged
-                // as zeros, which is what ItemWords::load puts there)
-                ItemWords<W> it;
-                constexpr int NWD = sizeof(W) == 4 ? 2 : 3;
-#pragma unroll
-                for (int j = 0; j < NWD; ++j) {
-                    const int src = 3 * ((q >> 5) - (NWD - 1) + j - (w0 - 2));   // 0 .. 3 * LONG_STAGE_WORDS - 3
-                    it.hi[j] = (uint32_t) __shfl((int) staged, src, 64);
-                    it.lo[j] = (uint32_t) __shfl((int) staged, src + 1, 64);
-                    it.va[j] = (uint32_t) __shfl((int) staged, src + 2, 64);
-                }
-                W ka, kb;
-                const bool valid = kc.window_keys(it, q, strand, ka, kb) && s < n_win;
-                // which filters this lane asks: open ones whose last hit the window does not overlap
-                uint32_t ask = 0;
-#pragma unroll
-                for (int i = 0; i < NF; ++i)
-                    if (valid && ((open >> i) & 1u) && s >= next_free[i]) ask |= 1u << i;
-                uint32_t xa[NF];
-                uint32_t bit = 0;
-                if (ask) {
-                    const W addr = psi_a<W>(ka, k);
-                    long_load_a<NF>(fg.il_a + (uint64_t) (addr >> 5) * NF, xa);
-                    bit = (uint32_t) addr & 31u;
-                } else {
-#pragma unroll
-                    for (int i = 0; i < NF; ++i) xa[i] = 0;
-                }
-#pragma unroll
-                for (int i = 0; i < NF; ++i) {
-                    if (!((open >> i) & 1u)) continue;     // (uniform)
-                    const bool asked = (ask >> i) & 1u;
-                    const bool ha = asked && ((xa[i] >> bit) & 1u);
-                    bool full = false;
-                    uint64_t m_valid = 0, m_a = 0, m_b = 0, m_c = 0;
-                    const PlanesBCD f = planes_bcd(fg, i);
-                    if constexpr (COUNT) {
-                        const bool hb = ha && test_bit<W>(f.b, kb);
-                        const bool hc = hb && test_bit<W>(f.c, ka ^ kb);
-                        full = hc && test_bit<W>(f.d, ka | kb);
-                        m_valid = __ballot(asked), m_a = __ballot(ha), m_b = __ballot(hb), m_c = __ballot(hc);
-                    } else {
-                        full = ha && probe_bcd_chain<W>(f, ka, kb);
-                    }
-                    uint64_t m = __ballot(full);
-                    // the greedy walk, by the whole wave; `passed` = the window starts of this block the reference looks at
-                    uint64_t passed = 0;
-                    int from = max(next_free[i] - base, 0);          // (block-relative)
-                    bool ends = false;
-                    while (true) {
-                        if (from < 64) m &= ~0ull << from;
-                        else m = 0;
-                        if (!m) {
-                            if (from < 64) passed |= ~0ull << from;
-                            break;
-                        }
-                        const int b = __ffsll((unsigned long long) m) - 1;
-                        passed |= (~0ull << from) & (b == 63 ? ~0ull : ((1ull << (b + 1)) - 1ull));
-                        ++count[i];
-                        next_free[i] = base + b + k;
-                        from = b + k;
-                        if (count[i] >= t) {
-                            ends = true;
-                            if (found_chunk < 0 || i < found_chunk) found_chunk = i;
-                            break;
-                        }
-                        if constexpr (!COUNT) {
-                            if (next_free[i] > (int) len - (t - count[i]) * k) {   // the missing hits no longer fit
-                                ends = true;
-                                break;
-                            }
-                        }
-                    }
-                    if constexpr (COUNT)
-                        fprobes[i] += (unsigned long long) (__popcll(passed & m_valid) + __popcll(passed & m_a) + __popcll(passed & m_b) + __popcll(passed & m_c));
-                    if (ends) open &= ~(1u << i);
-                }
-                if (found_chunk >= 0) {
-                    // the reference does not search a read in the chunks behind the one that tagged it
-                    want &= (1u << found_chunk) - 1u;
-                    open &= want;
-                }
-                if constexpr (!COUNT) {
-                    // first window of the next block past every place a missing hit could start: the scan of this strand is over
-#pragma unroll
-                    for (int i = 0; i < NF; ++i)
-                        if (((open >> i) & 1u) && max(base + 64, next_free[i]) > (int) len - (t - count[i]) * k) open &= ~(1u << i);
-                }
-            }
-        }
-        // scanned_i: the read reached chunk i (no earlier chunk of the pass tagged it); found_i: chunk i tagged it
-#pragma unroll
-        for (int i = 0; i < NF; ++i) {
-            if (i < fg.g && (found_chunk < 0 || found_chunk >= i)) {
-                ++n_scanned[i];
-                if constexpr (COUNT) probes += fprobes[i];
-            }
-            if (found_chunk == i) ++n_found[i];
-        }
-        if (found_chunk >= 0 && tags && lane == 0)
-            (void) __hip_atomic_fetch_or(tags + (r >> 6), 1ull << (r & 63ull), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    if (lane == 0) {
-        if (counters) {
-#pragma unroll
-            for (int i = 0; i < NF; ++i) {
-                if (n_scanned[i]) atomicAdd(&counters[(uint64_t) i * cstride], (unsigned long long) n_scanned[i]);
-                if (n_found[i]) atomicAdd(&counters[(uint64_t) i * cstride + 1], (unsigned long long) n_found[i]);
-            }
-        }
-        if (COUNT && probe_counter && probes) atomicAdd(probe_counter, probes);
-    }
+// the filters of several jobs in one pass (JOBS = true, NF = 8, COUNT = false is the one case there is)
+template <typename W, int NF, bool COUNT, bool JOBS>
+__global__ __launch_bounds__(LONG_WG) void search_long_kernel(ReadsView rv, FilterGroupView fg, int k, int t, uint64_t *__restrict__ tags,
+                                                              unsigned long long *__restrict__ counters, uint32_t cstride, uint32_t job_mask,
+                                                              uint64_t job_tag_words)
+{
+    static_assert(JOBS && NF == 8 && !COUNT, "several jobs: passes of eight slots, no probe counting");
+    constexpr const uint64_t *sel = nullptr;
+    constexpr unsigned long long *probe_counter = nullptr;
+    const ActiveList al{nullptr, nullptr};
+#include "long_search_body.hpp"
 }
 
 }  // namespace commet

@@ -283,8 +283,12 @@ int commet_index_and_search(commet_ctx *ctx,
  * whole) the chunk filters of several jobs share a pass over the search set: the lane-a gathers of its reads, two thirds of a
  * job's memory requests, are then made once per pass instead of once per job: up to eight chunk filters per pass of the gather
  * kernel; on a search set that takes the tiled search, jobs of one chunk filter each two per scan (one probe of the set's query list,
- * one replay that keeps the two jobs apart).  Otherwise (and with option "multi_job" = 1, or when the device has no room for the
- * slots of a shared pass) the jobs run one after the other.  info (may be NULL) sums over the jobs. */
+ * one replay that keeps the two jobs apart).  A search set that takes the wave-per-read kernel (option "long_search") shares passes
+ * under option "multi_job" = 2 only (not measured against the jobs alone yet, so not auto's choice): up to eight chunk filters of
+ * several jobs per pass of search_long_kernel, one plane-A load per window for all of them; for such a search set the chunks may
+ * also take the atomic index kernel (their slots are zeroed first).  Otherwise (and with option "multi_job" = 1, under a selection
+ * on the search set, with "count_probes", for k <= 24 unless "slice_mode" = 1, for a job of more than eight chunks, or when the
+ * device has no room for the slots of a shared pass) the jobs run one after the other.  info (may be NULL) sums over the jobs. */
 int commet_index_many_and_search(commet_ctx *ctx, int n_jobs, const commet_readset *const *index_rs,
                                  const uint8_t *const *index_select, const commet_readset *search_rs,
                                  const uint8_t *search_select, uint8_t *const *tags_out, commet_pair_stats *stats,
@@ -320,7 +324,8 @@ int commet_index_many_and_search(commet_ctx *ctx, int n_jobs, const commet_reads
  *   query_list_max_mb    auto mode of tiled_search: largest list (estimated) a set may get, default 4096 (sets of up to ~15 M reads;
  *                        larger lists — a 50 M-read set's is 11 GB — pay in long-lived contexts only: allocating them costs
  *                        15-30 ms per GiB; lists of more than 4 GiB are built for a set's second eligible scan)
- *   multi_job (0/1)      commet_index_many_and_search: 0 = chunk filters of several jobs in one pass where possible, 1 = job by job
+ *   multi_job (0/1/2)    commet_index_many_and_search: 0 = chunk filters of several jobs in one pass where possible (search sets that
+ *                        take long_search: job by job), 1 = job by job, 2 = as 0, and search sets that take long_search share passes too
  *   sparse_search (0/1/2) a pass over a SELECTION of a search set (a filter bv that leaves few reads: file_manager.h:88-112 skips the
  *                        others) walks the list of the selected, not yet tagged reads instead of the set's bitmap, so that every
  *                        lane of a wave has a read: 0 = when the host plan visits less than half of the set's reads, 1 = never,
@@ -329,7 +334,7 @@ int commet_index_many_and_search(commet_ctx *ctx, int n_jobs, const commet_reads
  *                        consecutive windows per step, the reference's greedy rule on the ballots (search_long_kernel), groups of up to
  *                        eight chunk filters: 0 = such sets whose longest read has 5000 bases or more (measured: the lane-per-read
  *                        kernels win below 2500, the wave from 3000 on), 1 = never, 2 = whenever the set has a read (tests);
- *                        commet_index_many_and_search runs such sets job by job
+ *                        commet_index_many_and_search lets the jobs of such a search set share passes under multi_job = 2
  *   ordered_scan (0/1/2) ragged sets (reads of several lengths): the first pass of a gather kernel over a whole set walks its reads in
  *                        order of their first-hit window counts (a list made once per set: a workgroup lives as long as its longest
  *                        read, its other lanes idle meanwhile): 0 = sets of 2^16 reads and more, 1 = never, 2 = any ragged set (tests)

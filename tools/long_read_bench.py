@@ -7,7 +7,12 @@ Prints one JSON line per workload: search ms (min-max over the pairs), bases/s, 
   python tools/long_read_bench.py --index-mode [--part-min-kmers N] ...
 The same protocol on the INDEX side: A = index_mode 1 (index_kernel, a lane per read, atomic ORs), B = index_mode 2 (the bucketed
 build through the item list, part_items_fill_kernel); index ms from the job's own events, the tags byte-compared, and B's launches
-checked: more than one scatter1 piece, no index_kernel.  `huge<N>x<L>`: N reads of L bases per set."""
+checked: more than one scatter1 piece, no index_kernel.  `huge<N>x<L>`: N reads of L bases per set.
+  python tools/long_read_bench.py --jobs 8 [--lib-a PATH] ...
+Several jobs on one long search set through commet_index_many_and_search: N index sets (set 0 of the workload cut into N parts,
+alternately of two chunks and of one under the max_kmer the tool sets) against set 1.  A = the jobs alone (multi_job = 1), B = shared
+passes of search_long_kernel (multi_job = 2), fresh processes, every job's tags byte-compared.  --lib-a: A loads that library file
+instead (a build of another commit: its commet_index_many_and_search as it stands, no multi_job option set)."""
 import argparse
 import hashlib
 import json
@@ -103,6 +108,76 @@ def child(a):
                       "kernels": kt, "tags_sha256": hashlib.sha256(tags[0].tobytes() + tags2[0].tobytes()).hexdigest()}))
 
 
+def child_jobs(a):
+    """N index sets against one search set in one commet_index_many_and_search call; prints search ms of the call and per job"""
+    import commet_amd
+    if a.lib:
+        from commet_amd import lib as lib_
+        lib_.LIB_PATH = a.lib                        # (loaded on first use: this file instead of the tree's library)
+    offs = np.load(os.path.join(a.dir, f"{a.child}_offs.npy"))
+    sets = [np.load(os.path.join(a.dir, f"{a.child}_{s}_bases.npy")) for s in range(2)]
+    n = len(offs) - 1
+    # parts of two shares and of one, alternating; with max_kmer at 1.5 shares the large ones are two chunks, the small ones one
+    weights = [2 - (j & 1) for j in range(a.jobs)]
+    cuts = [n * sum(weights[:j]) // sum(weights) for j in range(a.jobs + 1)]
+    kmers = np.maximum(np.diff(offs.astype(np.int64)) - a.k + 1, 0)
+    share = int(kmers.sum()) // sum(weights)
+    with commet_amd.Context(k=a.k, t=a.t) as ctx:
+        ctx.set_option("long_search", a.long_search)
+        if a.multi_job >= 0:
+            ctx.set_option("multi_job", a.multi_job)
+        qrs = commet_amd.ReadSet.from_files(ctx, [(sets[1], offs)])
+        irs = []
+        for j in range(a.jobs):
+            lo, hi = cuts[j], cuts[j + 1]
+            b0, b1 = int(offs[lo]), int(offs[hi])
+            irs.append(commet_amd.ReadSet.from_files(ctx, [(sets[0][b0:b1].copy(), (offs[lo:hi + 1] - offs[lo]).astype(np.uint64))]))
+        ctx.set_option("max_kmer", share * 3 // 2)
+        ctx.index_many_and_search(irs, qrs)          # warm-up: allocations, first launches
+        ctx.set_option("kernel_timing", 1)
+        tags, stats, info = ctx.index_many_and_search(irs, qrs)
+        kt = {k_: [c, round(ms, 3)] for k_, (c, ms) in ctx.kernel_times().items()}
+        ctx.set_option("kernel_timing", 0)
+        tags2, stats2, info2 = ctx.index_many_and_search(irs, qrs)   # untimed kernels: the call's own event times
+    print(json.dumps({"multi_job": a.multi_job, "lib": a.lib, "search_ms": round(info2["search_ms"], 3), "index_ms": round(info2["index_kernel_ms"], 3),
+                      "total_ms": round(info2["total_ms"], 3), "chunks": info["n_chunks"], "search_launches": info2["search_launches"],
+                      "job_search_ms": [round(s_["search_ms"], 3) for s_ in stats2], "shared": [s_["shared"] for s_ in stats],
+                      "kernels": kt, "tags_sha256": hashlib.sha256(b"".join(t_.tobytes() for t_ in tags + tags2)).hexdigest()}))
+
+
+def main_jobs(a, d):
+    for name in a.workloads:
+        n, total = make_pair(name, a.scale, d)
+        runs = {"A": [], "B": []}
+        for _ in range(a.pairs):
+            for side in ("A", "B"):
+                what = ["--jobs", str(a.jobs), "--long-search", str(a.long_search)]
+                if side == "A":
+                    what += ["--lib", a.lib_a, "--multi-job", "-1"] if a.lib_a else ["--multi-job", "1"]
+                else:
+                    what += ["--multi-job", "2"]
+                p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", name, "--dir", d, "-k", str(a.k), "-t", str(a.t)] + what,
+                                   capture_output=True, text=True, timeout=600)
+                if p.returncode != 0:
+                    sys.stderr.write(p.stderr[-2000:])
+                    raise SystemExit(f"{name}: run {side} failed (rc {p.returncode})")
+                runs[side].append(json.loads(p.stdout.strip().split("\n")[-1]))
+        for f in os.listdir(d):
+            os.remove(os.path.join(d, f))
+        digests = {r["tags_sha256"] for side in runs for r in runs[side]}
+        out = {"workload": name, "jobs": a.jobs, "reads_in_search_set": n, "bases_in_search_set": total, "k": a.k, "t": a.t, "same_tags": len(digests) == 1,
+               "chunks": runs["B"][0]["chunks"], "baseline": a.lib_a or "multi_job = 1"}
+        for side, key in (("A", "jobs_alone"), ("B", "shared_passes")):
+            out[key] = {"search_ms": [r["search_ms"] for r in runs[side]], "search_launches": runs[side][-1]["search_launches"],
+                        "job_search_ms": runs[side][-1]["job_search_ms"], "kernels": runs[side][-1]["kernels"]}
+        out["shared_faster_in_every_pair"] = all(b["search_ms"] < a_["search_ms"] for a_, b in zip(runs["A"], runs["B"]))
+        print(json.dumps(out), flush=True)
+        if not out["same_tags"]:
+            raise SystemExit(f"{name}: the tags of the shared passes and of the jobs alone differ")
+        if runs["B"][0]["search_launches"] >= a.jobs:
+            raise SystemExit(f"{name}: the jobs did not share a pass")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workloads", nargs="+", default=list(WORKLOADS))
@@ -116,10 +191,16 @@ def main():
     ap.add_argument("--index-mode", action="store_true", help="A/B of the index side: index_mode 1 against 2")
     ap.add_argument("--child-index-mode", type=int, default=0)   # (internal)
     ap.add_argument("--part-min-kmers", type=int, default=1)
+    ap.add_argument("--jobs", type=int, default=0, help="N index sets against one long search set through commet_index_many_and_search: alone against shared passes")
+    ap.add_argument("--lib-a", default=None, help="--jobs: the library file run A loads (a build of another commit)")
+    ap.add_argument("--lib", default=None)           # (internal)
+    ap.add_argument("--multi-job", type=int, default=-1)         # (internal) -1 = leave the option alone
     a = ap.parse_args()
     if a.child:
-        return child(a)
+        return child_jobs(a) if a.jobs else child(a)
     with tempfile.TemporaryDirectory(prefix="longbench") as d:
+        if a.jobs:
+            return main_jobs(a, d)
         for name in a.workloads:
             n, total = make_pair(name, a.scale, d)
             runs = {1: [], 2: []}
