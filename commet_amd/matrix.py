@@ -46,151 +46,17 @@ import tempfile
 import threading
 import time
 import traceback
+from concurrent.futures import ThreadPoolExecutor
+from types import SimpleNamespace
 
 import numpy as np
 
 from . import residency, sharding
+from .handover import Handover, wait_file
+from .matrix_io import (_log, c_atoi, concat_bits, default_filter_bv, filter_command, filter_comment, parse_set_file,  # noqa: F401 (re-exported)
+                        popcount, read_bv, split_bits, write_bv, write_filter_bv, write_matrices)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-
-
-# ---- the set file, as Commet.py reads it (Commet.py:42-95) -------------------------------------
-def parse_set_file(path):
-    names, files, bvs = [], [], []
-    with open(path) as fh:
-        lines = [ln for ln in fh.read().split("\n") if ln.strip()]
-    has_bv = bool(lines) and "," in lines[0]                      # only the first line is inspected (Commet.py:72)
-    for ln in lines:
-        names.append(ln.split(":")[0].strip())
-        items = ln.split(":")[1].split(";")
-        files.append([it.strip().split(",")[0] for it in items])
-        if has_bv:
-            bvs.append([it.strip().split(",")[1] for it in items])
-    return names, files, (bvs if has_bv else None)
-
-
-# ---- .bv files (boolean_vector.h:302-414) -----------------------------------------------------------
-def read_bv(path):
-    data = open(path, "rb").read()
-    h = data.index(b"#")
-    nl = data.index(b"\n", h)
-    n = int(data[h + 1:nl])
-    raw = np.frombuffer(data[nl + 1:nl + 1 + n // 8 + 1], dtype=np.uint8)
-    bits = np.zeros(n // 8 + 1, dtype=np.uint8)
-    bits[:raw.size] = raw
-    return n, bits
-
-
-def write_bv(path, comment, n, bits):
-    fd = os.open(path, os.O_RDWR | os.O_CREAT | os.O_TRUNC, 0o600)
-    with os.fdopen(fd, "wb") as fh:
-        fh.write(comment.encode() + b"\n#%d\n" % n)
-        fh.write(np.ascontiguousarray(bits[:n // 8 + 1], dtype=np.uint8).tobytes())
-
-
-def c_atoi(text):
-    """what C's atoi makes of a string: blanks, a sign, then digits up to the first other character (filter_reads reads -l, -n, -m so)"""
-    t = text.lstrip(" \t\n\v\f\r")
-    sign, i = 1, 0
-    if t[:1] in ("+", "-"):
-        sign, i = (-1 if t[0] == "-" else 1), 1
-    j = i
-    while j < len(t) and t[j] in "0123456789":
-        j += 1
-    return sign * int(t[i:j]) if j > i else 0
-
-
-def filter_comment(read_file, l=0, n=-1, e=0.0):
-    """the comment block `filter_reads <read_file> -l l [-n n] -e e` puts in front of its vector (filter_reads.cpp:160-176): the file's base
-    name, then the options as its stream prints them — `infinite` when -n is not given, -e as a C++ stream prints the float it was read into"""
-    i = read_file.rfind("/")
-    return ("----------------\nReference file\n  " + (read_file[i + 1:] if i > 0 else read_file) + "\nFilter Options\n"
-            "  min read size     : %d\n  max number of N   : %s\n  min shannon index : %s\n"
-            % (l, "infinite" if n < 0 else "%d" % n, "%g" % float(np.float32(e))))
-
-
-def write_filter_bv(path, read_file, count, bits, l=0, n=-1, e=0.0):
-    """The .bv `filter_reads <read_file> -l l [-n n] -e e [-m m] -o <path>` writes (boolean_vector.h:302-346), from the file's final bits
-    (count reads; -m shows in the bits only).  Appears complete or not at all (written under another name, renamed)."""
-    write_bv(path + ".part", filter_comment(read_file, l, n, e), count, bits)
-    os.rename(path + ".part", path)
-
-
-def default_filter_bv(path, read_file, n):
-    """What `filter_reads <read_file> -l 0 -e 0 -o <path>` writes (filter_reads.cpp:160-176, boolean_vector.h:148-164, 302-346): with the
-    default options no read can be removed, so the vector is all ones over the file's n reads (padding bits cleared) behind the tool's
-    comment block — written from the parser's record count instead of a second pass over the file.  Returns the bits."""
-    bits = np.full(n // 8 + 1, 0xFF, dtype=np.uint8)
-    bits[-1] = (1 << (n & 7)) - 1                                   # bits n .. of the last byte (all of it when n % 8 == 0) are padding
-    if path is not None:
-        write_filter_bv(path, read_file, n, bits)
-    return bits
-
-
-def filter_command(bin_dir, read_file, bv_path, l, n, e, m, files_in_set):
-    """the filter_reads run Commet.py makes for one file of a set (Commet.py:103-121): -n and -m only when given, -m shared out over the set's files"""
-    cmd = [os.path.join(bin_dir, "filter_reads"), read_file, "-l", str(l), "-e", str(e)]
-    if n >= 0:
-        cmd += ["-n", str(n)]
-    if m >= 0:
-        cmd += ["-m", str(m / files_in_set)]
-    return cmd + ["-o", bv_path]
-
-
-def popcount(bits, n):
-    return int(np.unpackbits(bits[:n // 8 + 1], bitorder="little")[:n].sum())
-
-
-def concat_bits(parts):
-    """[(n, bits)] of the files of a set -> set-wide (N, bits)"""
-    if len(parts) == 1:
-        return parts[0]
-    bools = np.concatenate([np.unpackbits(b[:n // 8 + 1], bitorder="little")[:n] for n, b in parts])
-    out = np.zeros(bools.size // 8 + 1, dtype=np.uint8)
-    pk = np.packbits(bools, bitorder="little")
-    out[:pk.size] = pk
-    return bools.size, out
-
-
-def split_bits(bits, counts):
-    """set-wide bits -> per-file bit arrays (each n/8+1 bytes)"""
-    if len(counts) == 1:
-        return [np.ascontiguousarray(bits[:counts[0] // 8 + 1])]
-    total = sum(counts)
-    bools = np.unpackbits(bits[:total // 8 + 1], bitorder="little")[:total]
-    out, pos = [], 0
-    for c in counts:
-        b = np.zeros(c // 8 + 1, dtype=np.uint8)
-        pk = np.packbits(bools[pos:pos + c], bitorder="little")
-        b[:pk.size] = pk
-        out.append(b)
-        pos += c
-    return out
-
-
-# ---- the three matrices, formatted like Commet.py:276-317 ------------------------------------------
-def write_matrices(out_dir, names, considered, shared):
-    n = len(names)
-    head = "".join(";" + s for s in names) + "\n"
-    with open(out_dir + "matrix_plain.csv", "w") as fh:
-        fh.write(head)
-        for i in range(n):
-            fh.write(names[i] + "".join(";" + str(shared[i][j]) for j in range(n)) + "\n")
-    with open(out_dir + "matrix_percentage.csv", "w") as fh:
-        fh.write(head)
-        for i in range(n):
-            fh.write(names[i] + "".join(";" + str(100 * shared[i][j] / float(considered[i])) for j in range(n)) + "\n")
-    with open(out_dir + "matrix_normalized.csv", "w") as fh:
-        fh.write(head)
-        for i in range(n):
-            fh.write(names[i] + "".join(
-                ";" + str(100 * (shared[i][j] + shared[j][i]) / float(considered[i] + considered[j])) for j in range(n)) + "\n")
-
-
-def _log(out_dir, search_name, index_name, st, index_ms, wall_s):
-    with open(f"{out_dir}{search_name}_in_{index_name}.log", "w") as fh:
-        fh.write(f"Index  time: {index_ms / 1000.0:g} s\nSearch time: {st['search_ms'] / 1000.0:g} s\n"
-                 f"Total  time: {wall_s:g} s\n[indexed {st['indexed']}, searched {st['searched']}, shared {st['shared']}]\n")
 
 
 # ---- the engine: where the reads live and the jobs run ------------------------------------------------
@@ -323,6 +189,459 @@ def _scratch_root():
     return "/dev/shm" if os.path.isdir("/dev/shm") and os.access("/dev/shm", os.W_OK) else tempfile.gettempdir()
 
 
+# ---- the filter step (Commet.py:103-121) ----------------------------------------------------------------
+class Filters:
+    """The filter vectors of the sets, for both drivers: which way they come about (given in the set file / all ones / made on the
+    device / one filter_reads per file), the per-set cache of the device's selections, the seconds the step took (`seconds`).
+    leave(s, rs) writes the .bv files of a set this rank has parsed; selection(s, rs) is what the jobs need of set s."""
+
+    def __init__(self, files, bvs, out_dir, bin_dir, l, n, e, m, eng):
+        self.files, self.bin_dir, self.l, self.n, self.e, self.m, self.eng = files, bin_dir, l, n, e, m, eng
+        tool = os.environ.get("COMMET_MATRIX_FILTER_TOOL", "0") == "1"
+        self.given = bvs is not None
+        # Commet.py's default options (-l 0 -e 0, no -n, no -m) remove no read: the filter vectors are then all ones over each file's
+        # reads and are written from the parser's record counts by the set's owner (default_filter_bv: the tool's bytes, tested), every
+        # rank derives the same selection from the counts of the set it holds — no second pass over the files, nothing to wait for.
+        # COMMET_MATRIX_FILTER_TOOL=1 runs filter_reads all the same.
+        self.synth = not self.given and l == 0 and e == 0 and n < 0 and m < 0 and not tool
+        # Any other options: every read's length and base counts are in the resident set's planes, so the selection is made on the device
+        # from the copy each rank holds (filter_set: commet_readset_filter, the tool's bits) — no filter_reads process re-reads the text,
+        # nothing to wait for; the set's owner leaves the tool's .bv files.  Engines without filter_set and COMMET_MATRIX_FILTER_TOOL=1
+        # run filter_reads as before.
+        self.device = not self.given and not self.synth and not tool and hasattr(eng, "filter_set")
+        self.tool = not (self.given or self.synth or self.device)
+        self.bvs = bvs if self.given else [[out_dir + os.path.basename(f) + ".bv" for f in fl] for fl in files]
+        self.seconds = 0.0
+        self.device_sel = {}                                      # set -> its per-file (count, bits), made on the device
+        self.pool, self.jobs, self.err = None, [], []             # the filter_reads processes of this rank; what one of them raised
+        self.t0 = self.end = time.perf_counter()
+        self.wait = None
+
+    def start_tool(self, owned, ranks, say, wait=None):
+        """One filter_reads per file of the sets in `owned` (the set's parser filters its files, too: one producer per set):
+        independent processes (each one multi-threaded over its file), a few at a time — and beside the parsing of the sets.  A
+        filter's .bv is written under another name and renamed into place, so the file appears complete or not at all: whoever needs
+        set s (any rank) waits for ITS files only (selection), not for every filter of the node — `wait` = (stop_ev, prof) of a
+        driver that loads beside them; one that calls done() before it loads passes none."""
+        self.t0 = self.end = time.perf_counter()
+        cmds = []
+        for s in owned:
+            for f, b in zip(self.files[s], self.bvs[s]):
+                cmds.append(filter_command(self.bin_dir, f, b, self.l, self.n, self.e, self.m, len(self.files[s])))
+                say("Filtering command: " + " ".join(cmds[-1]))
+        for c in cmds:                                             # what an earlier run left in this directory must not be read as this run's
+            for stale in (c[-1], c[-1] + ".part"):
+                try:
+                    os.remove(stale)
+                except OSError:
+                    pass
+        ranks.barrier()                                            # (every rank's stale files are gone before anybody looks for new ones)
+        self.ranks, self.wait = ranks, wait
+        self.pool = ThreadPoolExecutor(max_workers=int(os.environ.get("COMMET_FILTER_JOBS", "3")))
+        # (the sets are loaded last set first: so are their filters)
+        self.jobs = [self.pool.submit(self._run_tool, c) for c in reversed(cmds)]
+        for j in self.jobs:
+            j.add_done_callback(self._tool_over)
+
+    @staticmethod
+    def _run_tool(cmd):
+        subprocess.run(cmd[:-1] + [cmd[-1] + ".part"], check=True, stdout=subprocess.DEVNULL)
+        os.rename(cmd[-1] + ".part", cmd[-1])
+
+    def _tool_over(self, f):
+        self.end = max(self.end, time.perf_counter())             # when the last of them was done
+        if not f.cancelled() and f.exception() is not None:
+            self.err.append(f.exception())                        # whoever waits for a set is told at once
+
+    def done(self):
+        """this rank's filter processes are through (raises what a filter_reads process raised)"""
+        if self.pool is not None:
+            try:
+                for j in self.jobs:
+                    j.result()
+            finally:
+                self.pool.shutdown(wait=True)
+            self.seconds = (self.end if self.jobs else time.perf_counter()) - self.t0
+
+    def shutdown(self):
+        if self.pool is not None:
+            self.pool.shutdown(wait=True, cancel_futures=True)
+
+    def _device(self, s, rs):
+        """the selection of set s from the resident copy this rank holds; the per-file cap is what the tool's atoi makes of the
+        `-m` the driver passes it (str(m / files of the set))"""
+        if s not in self.device_sel:
+            w0 = time.perf_counter()
+            bits, _ = self.eng.filter_set(rs, self.l, self.n, self.e, c_atoi(str(self.m / len(self.files[s]))) if self.m >= 0 else -1)
+            cs = self.eng.file_reads(rs)
+            self.device_sel[s] = list(zip(cs, split_bits(bits, cs)))
+            self.seconds += time.perf_counter() - w0
+        return self.device_sel[s]
+
+    def leave(self, s, rs):
+        """the filter files of a set this rank has just parsed: from its record counts (default options), or the device's selection"""
+        if self.synth:
+            for c_, f_, b_ in zip(self.eng.file_reads(rs), self.files[s], self.bvs[s]):
+                default_filter_bv(b_, f_, c_)
+        elif self.device:
+            parts = self._device(s, rs)
+            w0 = time.perf_counter()
+            for (c_, bits_), f_, b_ in zip(parts, self.files[s], self.bvs[s]):
+                write_filter_bv(b_, f_, c_, bits_, self.l, self.n, self.e)
+            self.seconds += time.perf_counter() - w0
+
+    def selection(self, s, rs):
+        """set s is resident; once its filter files are there (written by whichever rank filtered them): its per-file read counts,
+        the number of reads it was asked about (the matrix's diagonal), its input selection -> (counts, considered, sel);
+        None: this rank is stopping"""
+        counts = self.eng.file_reads(rs)
+        if self.wait is not None:
+            for b in self.bvs[s]:
+                if not wait_file(b, f"the filter of set {s}", os.path.dirname(b), self.wait[0], self.err, self.ranks, self.wait[1]):
+                    return None
+        if self.synth:                                            # all ones (the set's owner has left the files: leave)
+            parts = [(c, default_filter_bv(None, f, c)) for c, f in zip(counts, self.files[s])]
+        elif self.device:                                         # from the copy this rank holds (its owner has left the files, too)
+            parts = self._device(s, rs)
+        else:
+            parts = [read_bv(b) for b in self.bvs[s]]
+        considered = sum(popcount(b, nb) for nb, b in parts)
+        for (nb, _), c, f in zip(parts, counts, self.files[s]):
+            if nb != c:
+                raise self.eng.mismatch_error(f"Number of reads in {f} and boolean vector size are not equal -> quit")
+        _, sel = concat_bits(parts)
+        if considered == sum(counts) and os.environ.get("COMMET_MATRIX_KEEP_SEL", "0") != "1":
+            sel = None                                            # every read selected (the default filters): no bitmap to upload, dense plans
+        return counts, considered, sel
+
+
+# ---- the jobs of a rank: library calls, the files they leave, what they add to the matrix --------------------------
+class Jobs:
+    """Runs jobs on resident sets (sets, sel, counts, considered: filled by the loader as the sets arrive) and leaves their files.
+    shared: (from set, in set) -> reads of `from` found in `in`.  Which job runs when is the driver's business."""
+
+    def __init__(self, eng, sets, sel, counts, considered, prof, names, files, out_dir):
+        self.eng, self.sets, self.sel, self.counts, self.considered, self.prof = eng, sets, sel, counts, considered, prof
+        self.names, self.files, self.out_dir = names, files, out_dir
+        self.shared = {}
+        self.reads_searched = 0
+        self.call_log = os.environ.get("COMMET_MATRIX_CALL_LOG")   # one line per library call: jobs, wall, event-timed device time, python clock
+        self.job_log = prof.setdefault("job_log", [])   # one row per library call: [kind, search set or reference, [the other sets], index ms, search ms, call ms]
+        #                                                 (what tools/schedule_sim.py replays on the pair cut of N ranks)
+        # the .bv and .log files of a job are written by two helper threads while the next job runs (6 MB per 50 M-read file: 3-4 ms
+        # of a job's ~6 ms of host time at configs[3]); all of them are on disk before the jobs' clock stops
+        self.writer, self.written = ThreadPoolExecutor(2), []
+
+    def acc(self, inf, n=1, what=None):
+        prof = self.prof
+        prof["jobs"] += n
+        prof["call_ms"] += inf["total_ms"]
+        prof["device_ms"] += inf["index_ms"] + inf["search_ms"]
+        if what is not None:
+            self.job_log.append([what[0], what[1], list(what[2]), round(inf["index_ms"], 3), round(inf["search_ms"], 3), round(inf["total_ms"], 3)])
+        if self.call_log:
+            with open(self.call_log, "a") as fh:
+                fh.write(f"{prof['rank']} {n} {inf['total_ms']:.3f} {inf['index_ms']:.3f} {inf['search_ms']:.3f} {time.perf_counter():.6f}\n")
+
+    def on_one_search_set(self, index_ids, search_id, selections, kind="J2"):
+        """Jobs that search the SAME set — the J2 jobs of a reference set, the J3 jobs of a target (Commet.py:220, 233) — in one call
+        where the engine has one (commet_index_many_and_search: their chunk filters share passes over the search set: the lane-a
+        gathers of its reads, two thirds of such a job's memory requests, are made once per pass instead of once per job);
+        -> [(tags, stats, index_ms)] in the jobs' order, bit for bit what the jobs give one by one."""
+        eng, sets, sel = self.eng, self.sets, self.sel
+        if not index_ids:
+            return []
+        if hasattr(eng, "index_many_and_search") and len(index_ids) > 1:
+            tags, st, inf = eng.index_many_and_search([sets[x] for x in index_ids], sets[search_id], selections, sel[search_id])
+            self.acc(inf, len(index_ids), (kind, search_id, index_ids))
+            return [(tags[j], st[j], inf["index_ms"] / len(index_ids)) for j in range(len(index_ids))]
+        out = []
+        for x, sl in zip(index_ids, selections):
+            tags, st, inf = eng.index_and_search(sets[x], [sets[search_id]], sl, [sel[search_id]])
+            self.acc(inf, 1, (kind, search_id, [x]))
+            out.append((tags[0], st[0], inf["index_ms"]))
+        return out
+
+    def j1(self, ref, targets):
+        """J1 of a reference set: its index built once for all these targets -> the tags of each target"""
+        sets, sel = self.sets, self.sel
+        tags, _st, inf = self.eng.index_and_search(sets[ref], [sets[i] for i in targets], sel[ref], [sel[i] for i in targets])
+        self.prof["j1_builds"] += 1
+        self.reads_searched += sum(self.considered[i] for i in targets)
+        self.acc(inf, 1, ("J1", ref, targets))
+        return tags
+
+    def leave(self, search, index, tags, st, index_ms, w0):
+        """the files of one J2 / J3 job: <file of `search`>_in_<index>.bv, <search>_in_<index>.log; its entry of the matrix"""
+        names, out_dir = self.names, self.out_dir
+        for f, c, b in zip(self.files[search], self.counts[search], split_bits(tags, self.counts[search])):
+            self.written.append(self.writer.submit(write_bv, out_dir + os.path.basename(f) + "_in_" + names[index] + ".bv", f + " in " + names[index], c, b))
+        self.written.append(self.writer.submit(_log, out_dir, names[search], names[index], st, index_ms, time.perf_counter() - w0))
+        self.shared[(search, index)] = st["shared"]
+        self.reads_searched += self.considered[search]
+
+    def finish(self):
+        """every job is through and every file on disk (what a writer raised is raised here) -> the clock's reading then;
+        the rank's allocation figures and, where they were asked for, its kernel times go into the profile"""
+        eng, prof = self.eng, self.prof
+        eng.synchronize()
+        for f in self.written:
+            f.result()
+        self.writer.shutdown()
+        end = time.perf_counter()
+        if hasattr(eng, "alloc_stats"):
+            a_ = eng.alloc_stats()
+            prof["alloc_wait_ms"], prof["fresh_device_bytes"], prof["alloc_calls"] = round(a_["wait_ms"], 1), a_["fresh_bytes"], a_["calls"]
+        if hasattr(eng, "kernel_times") and eng.kernel_times() is not None:
+            prof["kernel_ms"] = eng.kernel_times()
+        return end
+
+    def cancel(self):
+        """a failing run: what has not been written yet is not waited for"""
+        self.writer.shutdown(wait=False, cancel_futures=True)
+
+
+# ---- residency without a budget: parse my sets once, publish them, take the others I need ---------------------------------
+class Loader:
+    """Makes the sets of this rank's pairs resident and fills sets / counts / sel / considered: everything first (load_first), or on
+    a second thread in the order the jobs want them while the job thread runs them (start; wait_for, there, wait_any are the job
+    thread's side of it)."""
+
+    def __init__(self, eng, cfg, cut, filters, hand, ranks, prof, stop_ev):
+        self.eng, self.files, self.note, self.cut, self.filters, self.hand, self.ranks, self.prof = eng, cfg.files, cfg.note, cut, filters, hand, ranks, prof
+        self.sets, self.counts, self.sel, self.considered = {}, {}, {}, {}
+        self.stop_ev = stop_ev                                    # set when this rank is through (or has failed): ends every wait
+        self.jobs_done = threading.Event()
+        self.thread, self.ready, self.order, self.own_first, self.solo = None, None, [], [], False
+        self.err = []                                             # what the loading thread raised: handed to the job thread
+        self.t0 = self.load_end = time.perf_counter()
+        self.loaded_all = False
+        self.set_wait = 0.0
+
+    def parse(self, s):
+        w0 = time.perf_counter()
+        rs = self.eng.parse(self.files[s])
+        self.prof["parse_s"] += time.perf_counter() - w0
+        self.prof.setdefault("parse_log", []).append([s, round(time.perf_counter() - w0, 4)])
+        self.prof["sets_parsed"] += 1
+        self.filters.leave(s, rs)
+        return rs
+
+    def parse_own(self, s):
+        """one of this rank's sets: parsed here and nowhere else; published for the ranks that need it"""
+        rs = self.parse(s)
+        if s in self.cut.needed_by_others:
+            self.hand.publish(s, rs)
+        if s in self.cut.needed:
+            self.sets[s] = rs
+        elif self.hand is None or s not in self.hand.exported:
+            self.eng.release(rs)
+
+    def fetch(self, s):
+        rs = self.hand.fetch(s)
+        if rs is not None:
+            self.sets[s] = rs
+        return rs is not None
+
+    def prepare(self, s):
+        got = self.filters.selection(s, self.sets[s])
+        if got is not None:
+            self.counts[s], self.considered[s], self.sel[s] = got
+        return got is not None
+
+    def load_first(self):
+        """COMMET_MATRIX_PIPELINE=0: every set resident before the first job"""
+        cut = self.cut
+        for s in cut.owned:
+            if s in cut.needed or s in cut.needed_by_others:
+                self.parse_own(s)
+        self.ranks.barrier()                                      # every image is in place
+        for s in cut.needed:
+            if s not in self.sets:
+                self.fetch(s)                                     # (its owner's descriptor / image is in place behind the barrier)
+        for s in cut.needed:
+            self.prepare(s)
+        self.load_end = time.perf_counter()
+
+    def start(self, refs):
+        """A second host thread makes the sets resident in the order the jobs want them (read sets are made on a stream
+        of their own, include/commet_hip.h) while this one runs the jobs of a reference set as soon as it and its
+        targets are there: the host-bound loading hides behind the device-bound jobs.  One rank: the thread parses
+        the files, last set first, and ref = N-2, N-3, ... need the sets ref .. N-1.  Several ranks: the thread parses
+        this rank's own sets and publishes them, then takes the others' as they appear (no barrier in between)."""
+        cut, N = self.cut, len(self.files)
+        self.ready = [threading.Event() for _ in range(N)]
+        self.solo = cut.world == 1                                # (then the loading thread parses, too)
+        if self.solo:
+            self.order = list(range(N - 1, -1, -1))
+        else:
+            for ref in refs:
+                for s in [ref] + [i for (r, i) in cut.mine if r == ref]:
+                    if s not in self.order:
+                        self.order.append(s)
+            # Several ranks: nobody waits at a barrier for every set of the node to be parsed.  This rank parses its own
+            # sets first — the ones most ranks wait for first — and publishes their images; then it takes the other
+            # ranks' images, in the order its jobs want them, as soon as each file appears.  Its first job starts when
+            # the two sets of that job are there, whatever the other ranks are still parsing.
+            wanted_by = {s_: sum(1 for r in range(cut.world) if any(s_ in cut.pairs[c] for c in cut.runs[r])) for s_ in cut.owned}
+            self.own_first = sorted((s_ for s_ in cut.owned if s_ in cut.needed or s_ in cut.needed_by_others), key=lambda s_: (-wanted_by[s_], s_))
+            # (simulated and NOT adopted in round 6: parsing first the sets some rank cannot start without — in every pair of its run —
+            # helps the ranks that wait for those and delays the one with the longest run: configs[3] at eight ranks 2.50 against 2.58 s
+            # with one run's fitted costs, 2.65 against 2.53 s with another's: tools/schedule_sim.py, blocking_first)
+        self.thread = threading.Thread(target=self.load_all, name="commet-set-loader", daemon=True)
+        self.thread.start()
+
+    def reserve_lists(self):
+        """COMMET_MATRIX_LARGE_LISTS=1 (off by default): query lists above the library's cap (a 50 M-read set's is 11 GB; it saves
+        ~12 ms of every J2 / J3 job that searches the set) for the sets this rank searches three times or more; their memory is asked
+        from the driver HERE, by the loader thread once every set is resident, and a set whose memory waits in the library's device
+        cache gets its list at its next eligible scan but one.  Measured on configs[3] (profiles/r05_large_lists): 11.0 s against
+        11.8 s on a box whose device memory had been used before (the driver's 110 GiB take no time there), 13.4 s on a fresh box —
+        there hipMalloc costs 15-30 ms per GiB (3.4 s), and while one thread is inside hipMalloc the HIP calls of every other thread
+        of the process wait, so the job thread stands still with it.  Hence opt-in: for long-lived hosts."""
+        eng, sets = self.eng, self.sets
+        if os.environ.get("COMMET_MATRIX_LARGE_LISTS", "0") != "1" or not hasattr(eng, "list_estimate"):
+            return
+        scans = {}
+        for (r_, i_) in self.cut.mine:                            # J2 searches the reference set, J3 the target (Commet.py:220, 233)
+            scans[r_] = scans.get(r_, 0) + 1
+            scans[i_] = scans.get(i_, 0) + 1
+        want = [s_ for s_ in sorted(scans, key=lambda s_: -scans[s_]) if scans[s_] >= 3 and s_ in sets]
+        est = {s_: eng.list_estimate(sets[s_]) for s_ in want}
+        want = [s_ for s_ in want if est[s_] > (4 << 30)]          # (smaller lists are the library's default already)
+        budget = 0.4 * eng.device_total()
+        got = 0
+        for s_ in want:
+            if self.stop_ev.is_set() or self.jobs_done.is_set() or sum(est[x] for x in want[:want.index(s_) + 1]) > budget:
+                break
+            eng.reserve_list(sets[s_])
+            got += 1
+        self.prof["lists_reserved"] = got
+        if got:
+            self.note(f"memory of {got} large query lists set aside ({sum(est[x] for x in want[:got]) / 2**30:.0f} GiB)")
+
+    def load_all(self):
+        try:
+            for s in self.own_first:
+                if self.stop_ev.is_set():
+                    return
+                self.parse_own(s)
+            for s in self.order:
+                if self.stop_ev.is_set():                         # the job thread has failed
+                    break
+                if self.solo:
+                    self.sets[s] = self.parse(s)
+                elif s not in self.sets and not self.fetch(s):
+                    break
+                if not self.prepare(s):
+                    break
+                self.ready[s].set()
+                self.note(f"set {s} resident")
+            self.load_end = time.perf_counter()
+            self.loaded_all = True
+            self.reserve_lists()
+        except BaseException as ex:          # handed to the job thread, which is waiting for a set
+            self.err.append(ex)
+            for ev in self.ready:
+                ev.set()
+        finally:
+            if not self.loaded_all:
+                self.load_end = time.perf_counter()
+
+    def there(self, s):
+        return self.thread is None or self.ready[s].is_set()
+
+    def _wait(self, there, every):
+        """the job thread waits for the loading thread; errors of the filters / the loader / another rank end the wait"""
+        w0 = time.perf_counter()
+        polls = 0
+        while not there():
+            if self.filters.err:                                  # a filter_reads process of this rank failed
+                raise self.filters.err[0]
+            if self.err:
+                raise self.err[0]
+            polls += 1
+            if self.cut.world > 1 and polls % every == 0 and hasattr(self.ranks, "check"):
+                self.ranks.check()                                # (has a rank given up?  Its sets will never come)
+        self.set_wait += time.perf_counter() - w0
+        if self.err:
+            raise self.err[0]
+
+    def wait_for(self, s):
+        """set s is resident (raises what the loader raised, if it did)"""
+        if self.thread is not None:
+            self._wait(lambda: self.ready[s].wait(0.05), 5)
+
+    def wait_any(self, left):
+        """nothing can start: until some reference set of `left` is there with one of its targets"""
+        self._wait(lambda: any(self.there(r_) and any(self.there(i) for i in left[r_]) for r_ in left) or time.sleep(0.002), 125)
+
+    def finish(self):
+        """every set is loaded (one rank: a set no pair needs is still loaded and counted) -> seconds the loading took"""
+        if self.thread is not None:
+            for s in self.order:
+                self.wait_for(s)
+            self.thread.join()
+        return self.load_end - self.t0
+
+    def join(self, failed):
+        """-> the loading thread is stuck in a HIP call that does not return: the process is on its way out"""
+        if self.thread is not None and self.thread.is_alive():    # (an error in the job thread)
+            self.thread.join(timeout=5.0 if failed else None)
+        return self.thread is not None and self.thread.is_alive()
+
+
+# ---- what both drivers begin and end with ---------------------------------------------------------------------------------
+def _setup(input_file, out_dir, k, t, l, bin_dir, rank, verbose, progress):
+    if out_dir[-1] != "/":
+        out_dir += "/"
+    os.makedirs(out_dir, exist_ok=True)
+    names, files, bvs = parse_set_file(input_file)
+    if l < k * t and l != 0:                                      # Commet.py:509-513 (l stays 0 by default)
+        l = k * t
+    return SimpleNamespace(out_dir=out_dir, bin_dir=bin_dir or os.path.join(HERE, "bin"), names=names, files=files, bvs=bvs, N=len(names), l=l,
+                           say=print if (verbose and rank == 0) else (lambda *a, **kw: None),
+                           note=progress if progress is not None else (lambda msg: None))
+
+
+def _profile(rank, pairs, handover, ranks, share):
+    return dict(rank=rank, pairs=pairs, sets_parsed=0, sets_loaded=0, j1_builds=0, parse_s=0.0, save_s=0.0, load_s=0.0,
+                jobs=0, call_ms=0.0, device_ms=0.0, handover=handover, backend=getattr(ranks, "backend", None),
+                torch_loaded="torch" in sys.modules, predicted_share=share)
+
+
+def _matrices(cfg, everyone):
+    """the three matrices from every rank's (shared, profile, considered) -> the head of the report"""
+    N = cfg.N
+    mat = [[0] * N for _ in range(N)]
+    diag = {}
+    for d, _, cons in everyone:
+        diag.update(cons)                                         # (every set is in some rank's pairs)
+        for (a, b), v in d.items():
+            mat[a][b] = v
+    considered_all = [diag[s] for s in range(N)]
+    for s in range(N):
+        mat[s][s] = considered_all[s]
+    write_matrices(cfg.out_dir, cfg.names, considered_all, mat)
+    cfg.say("All Commet work is done")
+    cfg.say("\t Output csv matrices are in:")
+    for f in ("matrix_plain.csv", "matrix_percentage.csv", "matrix_normalized.csv"):
+        cfg.say("\t\t" + cfg.out_dir + f)
+    return dict(names=cfg.names, considered=considered_all, matrix=mat)
+
+
+def _report(result, everyone, filter_s, load_s, filter_overlaps_load, load_overlaps_jobs, jobs_s, total_s, searched, world):
+    """the times and rates of a run, in the report of rank 0
+    (the filter processes run beside the parsing: filter_s and load_s overlap, total_s is the wall time of it all)"""
+    prof = everyone[0][1]
+    result.update(filter_s=filter_s, load_s=load_s, filter_overlaps_load=filter_overlaps_load, load_overlaps_jobs=load_overlaps_jobs,
+                  set_wait_s=prof.get("set_wait_s", 0.0), jobs_s=jobs_s, total_s=total_s, reads_searched=searched, world=world,
+                  rank0_profile=prof, per_rank=[p for _, p, _c in everyone],
+                  reads_per_s=searched / jobs_s if jobs_s > 0 else 0.0,
+                  reads_per_s_incl_load_and_filter=searched / total_s if total_s > 0 else 0.0)
+    return result
+
+
 def run(input_file, out_dir, k=33, t=2, l=0, n=-1, e=0.0, m=-1, bin_dir=None, ranks=None, verbose=True,
         engine_factory=None, progress=None, fatal_hook=None, set_budget_gb=None):
     """set_budget_gb (also COMMET_MATRIX_SET_BUDGET_GB, --set-budget-gb; fractions allowed): the most device memory the packed sets may
@@ -335,796 +654,369 @@ def run(input_file, out_dir, k=33, t=2, l=0, n=-1, e=0.0, m=-1, bin_dir=None, ra
     own_ranks = ranks is None
     if ranks is None:
         ranks = sharding.Ranks()
-    world, rank = ranks.world, ranks.rank
     if set_budget_gb is None and os.environ.get("COMMET_MATRIX_SET_BUDGET_GB"):
         set_budget_gb = float(os.environ["COMMET_MATRIX_SET_BUDGET_GB"])
-    if set_budget_gb is not None:
-        if world > 1:
-            raise ValueError(f"--set-budget-gb with {world} ranks: a set budget is kept by one rank only (run without --gpus / a launcher, "
-                             "or without the budget)")
-        try:
-            return _run_under_budget(input_file, out_dir, k, t, l, n, e, m, bin_dir, ranks, verbose, engine_factory, progress,
-                                     int(float(set_budget_gb) * (1 << 30)), t_start)
-        finally:
-            if own_ranks and sys.exc_info()[0] is None:
-                ranks.close()
-    if out_dir[-1] != "/":
-        out_dir += "/"
-    bin_dir = bin_dir or os.path.join(HERE, "bin")
-    os.makedirs(out_dir, exist_ok=True)
-    names, files, bvs = parse_set_file(input_file)
-    N = len(names)
-    say = print if (verbose and rank == 0) else (lambda *a, **kw: None)
-    note = progress if progress is not None else (lambda msg: None)
+    if set_budget_gb is not None and ranks.world > 1:
+        raise ValueError(f"--set-budget-gb with {ranks.world} ranks: a set budget is kept by one rank only (run without --gpus / a launcher, "
+                         "or without the budget)")
+    try:
+        cfg = _setup(input_file, out_dir, k, t, l, bin_dir, ranks.rank, verbose, progress)
+        make_engine = engine_factory or HipEngine
+        if set_budget_gb is not None:
+            return _run_under_budget(cfg, k, t, n, e, m, ranks, make_engine, int(float(set_budget_gb) * (1 << 30)), t_start)
+        return _run_resident(cfg, k, t, n, e, m, ranks, make_engine, fatal_hook, t_start)
+    finally:
+        if own_ranks and sys.exc_info()[0] is None:
+            ranks.close()
 
-    if l < k * t and l != 0:                                      # Commet.py:509-513 (l stays 0 by default)
-        l = k * t
-    # ---- who does what: pairs in contiguous runs of equal cost, every set parsed by one rank (sharding.assign_owners) ----
+
+# ---- every set resident: the pairs of a rank, grouped by reference set ---------------------------------------------------------
+def _cut(files, world, rank):
+    """who does what: pairs in contiguous runs of equal cost, every set parsed by one rank (sharding.assign_owners)"""
+    N = len(files)
     pairs = [(ref, i) for ref in range(N - 1) for i in range(ref + 1, N)]
     size = [float(sum(os.path.getsize(f) for f in fl)) for fl in files]   # cost proxy known before any parsing
     pair_cost = [size[a] + size[b] for a, b in pairs]
     runs = sharding.assign_pairs_contiguous(pair_cost, world)
     mine = [pairs[c] for c in runs[rank]]
-    needed = sorted({s for p in mine for s in p})
     owner = sharding.assign_owners(N, world, [sum(pair_cost[c] for c in runs[r]) for r in range(world)])
-    owned = [s for s in range(N) if owner[s] == rank]
-    needed_by_others = {s for r in range(world) if r != rank for c in runs[r] for s in pairs[c]}
+    return SimpleNamespace(world=world, pairs=pairs, runs=runs, mine=mine, owner=owner, needed=sorted({s for p in mine for s in p}),
+                           owned=[s for s in range(N) if owner[s] == rank],
+                           needed_by_others={s for r in range(world) if r != rank for c in runs[r] for s in pairs[c]},
+                           # what the static cut expects of this rank
+                           share=round(sum(pair_cost[c] for c in runs[rank]) / max(sum(pair_cost), 1e-9), 4))
 
+
+def _foreign(cut, r):
+    """the sets rank r takes from others"""
+    return sorted({s for c in cut.runs[r] for s in cut.pairs[c] if cut.owner[s] != r})
+
+
+def _schedule(cut, refs, loader, jobs, note):
+    """Order of a rank's jobs: per reference set J1 (its index built once for all its targets), then the J2 jobs of its targets
+    together (they all search S_ref); the J3 jobs — (ref, i) searches S_i — are kept back and run target by target at the end, so
+    that the J3 jobs of a target share passes as well.  The files a job writes do not depend on when it runs."""
+    mine, prof = cut.mine, jobs.prof
+    kept_T2 = {}                   # (ref, i) -> J2's result, the index selection of J3(ref, i); freed as J3 consumes it
+    refs_left = {}                 # target -> reference sets of this rank's pairs that have not been through J2 yet
+    for (r_, i_) in mine:
+        refs_left[i_] = refs_left.get(i_, 0) + 1
+
+    def j3_of(i):
+        """J3 of every pair of target i: S_i in (S_ref restricted to J2's result) — overwrites J1's <F>_in_<S_ref>.bv (Commet.py:233)"""
+        w0 = time.perf_counter()
+        loader.wait_for(i)
+        of_i = [r for (r, t_) in mine if t_ == i]
+        for ref, (T3, st3, index_ms) in zip(of_i, jobs.on_one_search_set(of_i, i, [kept_T2.pop((r, i)) for r in of_i], "J3")):
+            jobs.leave(i, ref, T3, st3, index_ms, w0)
+        note(f"J3 jobs of set {i} done ({prof['jobs']} so far)")
+
+    # Which reference set next (round 6): the first of the rank's list that is resident TOGETHER with one of its targets — a rank of a
+    # node starts on whatever pair has arrived instead of waiting for the first reference set of its list (tools/schedule_sim.py on
+    # configs[3]: 2.69 -> 2.53 s at eight ranks, 4.24 -> 3.97 s at four).  A reference set some of whose targets are still on their way
+    # is taken up again later (one more index build of S_ref instead of an idle GPU, as before).  One rank, or everything loaded
+    # first: the list's own order.
+    there = loader.there
+    left = {ref: [i for (r, i) in mine if r == ref] for ref in refs}
+    while left:
+        ref = next((r_ for r_ in refs if r_ in left and there(r_) and any(there(i) for i in left[r_])), None)
+        if ref is None:
+            loader.wait_any(left)
+            continue
+        targets = [i for i in left[ref] if there(i)]
+        left[ref] = [i for i in left[ref] if i not in targets]
+        for s_need in [ref] + targets:
+            loader.wait_for(s_need)                                  # (resident: raises what the loader raised, if it did)
+        w0 = time.perf_counter()
+        tags1 = jobs.j1(ref, targets)
+        # J2 of every target: X_i = S_i restricted to (S_i in S_ref); S_ref in X_i
+        for i, (T2, st2, index_ms) in zip(targets, jobs.on_one_search_set(targets, ref, list(tags1))):
+            jobs.leave(ref, i, T2, st2, index_ms, w0)
+            kept_T2[(ref, i)] = T2
+        if not left[ref]:
+            del left[ref]
+            note(f"J1 and J2 jobs of set {ref} done ({prof['jobs']} so far)")
+        # The J3 jobs — (ref, i) searches S_i — are kept back so that the J3 jobs of a target share passes as well, but no longer than
+        # needed: a target's batch runs as soon as the last of its reference sets on this rank has been through J2 (its J2 bitmaps are
+        # freed with it, its files are on disk: a late failure loses little).  The files a job writes do not depend on when it runs.
+        for i in targets:
+            refs_left[i] -= 1
+        for i in sorted(targets):
+            if refs_left[i] == 0:
+                j3_of(i)
+    assert not any(refs_left.values()) and not kept_T2            # (every target's references are in `refs`: no J3 is left over)
+
+
+def _tell_the_others(ranks, ex):
+    """a failing rank of several: tell the others at once (their waits end with an error naming this rank) instead of leaving them
+    in a gather until the timeout"""
+    if not isinstance(ex, RuntimeError) or "rendezvous" not in str(ex):
+        try:                                                      # what this rank ran into may only be the wake of another rank's failure
+            ranks.check()                                         # (scratch gone under its feet): then THAT is the error to report
+        except RuntimeError as first:
+            raise first from ex
+    ranks.abort(f"{type(ex).__name__}: {ex}")
+
+
+def _run_resident(cfg, k, t, n, e, m, ranks, make_engine, fatal_hook, t_start):
+    """The matrix with every set of a rank's pairs resident, on one rank or several."""
+    world, rank = ranks.world, ranks.rank
+    N, say, note = cfg.N, cfg.say, cfg.note
+    cut = _cut(cfg.files, world, rank)
+    stop_ev = threading.Event()                                   # set when this rank is through (or has failed): ends every wait
+    prof = _profile(rank, len(cut.mine), "image", ranks, cut.share)
     # ---- filter step (Commet.py:103-121): one filter_reads per file, run by the rank that parses the set ---------
-    t_filter = time.perf_counter()
-    filter_err = []
-    # Commet.py's default options (-l 0 -e 0, no -n, no -m) remove no read: the filter vectors are then all ones over each file's
-    # reads and are written from the parser's record counts by the set's owner (default_filter_bv: the tool's bytes, tested), every
-    # rank derives the same selection from the counts of the set it holds — no second pass over the files, nothing to wait for.
-    # COMMET_MATRIX_FILTER_TOOL=1 runs filter_reads all the same.
-    synth_filters = bvs is None and l == 0 and e == 0 and n < 0 and m < 0 and os.environ.get("COMMET_MATRIX_FILTER_TOOL", "0") != "1"
-    # Any other options: every read's length and base counts are in the resident set's planes, so the selection is made on the device
-    # from the copy each rank holds (filter_set: commet_readset_filter, the tool's bits) — no filter_reads process re-reads the text,
-    # nothing to wait for; the set's owner leaves the tool's .bv files.  Engines without filter_set and COMMET_MATRIX_FILTER_TOOL=1
-    # run filter_reads as before.
-    eng = None
-    device_filters = False
-    if bvs is None and not synth_filters and os.environ.get("COMMET_MATRIX_FILTER_TOOL", "0") != "1":
-        eng = (engine_factory or HipEngine)(k, t, ranks.local_rank)
-        device_filters = hasattr(eng, "filter_set")
-    device_filter_s = [0.0]
-    if synth_filters or device_filters:
-        bvs = [[out_dir + os.path.basename(f) + ".bv" for f in fl] for fl in files]
-        filter_pool, filter_jobs, filtered_here = None, [], False
-    elif bvs is None:
-        bvs = [[out_dir + os.path.basename(f) + ".bv" for f in fl] for fl in files]
-        todo = [(s, j) for s in range(N) for j in range(len(files[s]))]
-        cmds = []
-        for s, j in todo:
-            if owner[s] != rank:                                   # (the set's parser filters its files, too: one producer per set)
-                continue
-            cmd = filter_command(bin_dir, files[s][j], bvs[s][j], l, n, e, m, len(files[s]))
-            say("Filtering command: " + " ".join(cmd))
-            cmds.append(cmd)
-        # independent processes (each one multi-threaded over its file), a few at a time — and beside the parsing of
-        # the sets below.  A filter's .bv is written under another name and renamed into place, so the file appears complete
-        # or not at all: whoever needs set s (any rank) waits for ITS files only (`prepare`), not for every filter of the node.
-        from concurrent.futures import ThreadPoolExecutor
-        for c in cmds:                                             # what an earlier run left in this directory must not be read as this run's
-            for stale in (c[-1], c[-1] + ".part"):
-                try:
-                    os.remove(stale)
-                except OSError:
-                    pass
-        ranks.barrier()                                            # (every rank's stale files are gone before anybody looks for new ones)
-
-        def run_filter(cmd):
-            subprocess.run(cmd[:-1] + [cmd[-1] + ".part"], check=True, stdout=subprocess.DEVNULL)
-            os.rename(cmd[-1] + ".part", cmd[-1])
-
-        filter_pool = ThreadPoolExecutor(max_workers=int(os.environ.get("COMMET_FILTER_JOBS", "3")))
-        # (the sets are loaded last set first, see below: so are their filters)
-        filter_jobs = [filter_pool.submit(run_filter, c) for c in reversed(cmds)]
-        filter_end = [t_filter]
-
-        def filter_over(f):
-            filter_end[0] = max(filter_end[0], time.perf_counter())   # when the last of them was done
-            if not f.cancelled() and f.exception() is not None:
-                filter_err.append(f.exception())                   # whoever waits for a set (here) is told at once
-
-        for j in filter_jobs:
-            j.add_done_callback(filter_over)
-        filtered_here = True
-    else:
-        filter_pool, filter_jobs = None, []
-        filtered_here = False
-    filter_s = 0.0
-
-    def filters_done():
-        """this rank's filter processes are through (raises what a filter_reads process raised)"""
-        nonlocal filter_s
-        if filter_pool is not None:
-            try:
-                for j in filter_jobs:
-                    j.result()
-            finally:
-                filter_pool.shutdown(wait=True)
-            filter_s = (filter_end[0] if filter_jobs else time.perf_counter()) - t_filter
-        elif device_filters:
-            filter_s = device_filter_s[0]
-
-    scratch = None
+    eng = make_engine(k, t, ranks.local_rank)
+    filters = Filters(cfg.files, cfg.bvs, cfg.out_dir, cfg.bin_dir, cfg.l, n, e, m, eng)
+    if filters.tool:
+        filters.start_tool(cut.owned, ranks, say, wait=(stop_ev, prof))
+    hand = None
     if world > 1:
         # rank 0 makes the directory (mkdtemp: a fresh name, mode 0700 — the scratch root is shared with other users)
         scratch = ranks.broadcast_object(tempfile.mkdtemp(prefix="commet_pk_", dir=_scratch_root()) if rank == 0 else None)
+        hand = Handover(eng, ranks, scratch, cut.owned, prof, note, fatal_hook, stop_ev, filters.err)
+        if hand.probe(say):
+            prof["handover"] = "ipc"
     # sets are made resident by a second thread while the jobs run (COMMET_MATRIX_PIPELINE=0: everything first)
     pipelined = N >= 2 and os.environ.get("COMMET_MATRIX_PIPELINE", "1") != "0"
-    if eng is None:
-        eng = (engine_factory or HipEngine)(k, t, ranks.local_rank)
-    # How a set parsed by one rank reaches the others: device to device over HIP IPC (the owner exports its buffers, the
-    # others copy them over xGMI: no file, tens of ms for a 50 M-read set) when every rank can import a probe set of its
-    # neighbour and of rank 0; else as a packed image in the scratch directory (0.5 s to write, 0.2 s to read).
-    use_ipc = False
-
-    def import_guarded(blob, limit_s=None):
-        """eng.import_set with a deadline: a HIP call that hangs cannot be cancelled from inside the process, so a rank whose
-        import does not return leaves (non-zero; the launcher ends the job) rather than keep its peers waiting for good.
-        COMMET_IPC_LOCK=1 also takes a lock file of the node around the import (one import at a time on the node: a round-3
-        precaution against two processes attaching to each other's buffers at the same moment, never needed without torch)."""
-        def give_up():
-            msg = f"commet_amd.matrix, rank {rank}: commet_readset_import did not return within {limit:.0f} s; leaving"
-            print(msg, file=sys.stderr, flush=True)
-            if fatal_hook is not None:
-                try:
-                    fatal_hook(msg)
-                except Exception:
-                    pass
-            for s_ in owned:
-                for ext in ("pk", "ipc"):
-                    try:
-                        os.remove(os.path.join(scratch, f"set{s_}.{ext}"))
-                    except OSError:
-                        pass
-            os._exit(4)
-
-        limit = float(limit_s if limit_s is not None else os.environ.get("COMMET_IPC_IMPORT_LIMIT_S", "120"))
-        watch = threading.Timer(limit, give_up)
-        watch.daemon = True
-        watch.start()
-        try:
-            if os.environ.get("COMMET_IPC_LOCK", "0") == "1":
-                import fcntl
-                with open(os.path.join(scratch, "import.lock"), "a+") as lf:
-                    fcntl.flock(lf, fcntl.LOCK_EX)
-                    try:
-                        return eng.import_set(blob)
-                    finally:
-                        fcntl.flock(lf, fcntl.LOCK_UN)
-            return eng.import_set(blob)
-        finally:
-            watch.cancel()
-
-    # The default since round 4 (COMMET_MATRIX_IPC=0: packed images).  Round 3 had to make it opt-in: an import of a 50 M-read set
-    # did not return when the rank process had imported torch (for the gloo barrier) — two ROCm runtimes in one process.  The ranks
-    # meet over sharding's TCP store now and hold one runtime.  Two nets stay under the large imports, which the probe below (a
-    # four-read set) says nothing about: the first REAL set is imported by a fresh child process first (the canary: killed when it
-    # does not come back, and every rank then asks the owners for packed images), and an import of this process that does not
-    # return within COMMET_IPC_IMPORT_LIMIT_S ends the rank non-zero instead of leaving the job hung.
-    if world > 1 and os.environ.get("COMMET_MATRIX_IPC", "1") != "0" and hasattr(eng, "export_set"):
-        probe = blob = None
-        try:
-            probe = eng.parse_probe()
-            blob = eng.export_set(probe)
-        except Exception as ex:
-            say(f"device-to-device hand-over of sets not available ({ex}): packed images instead")
-        blobs = ranks.gather_objects(blob)                        # (every rank, whatever happened above)
-        ok = int(blob is not None)
-        if ok:
-            try:
-                for src in sorted({0, (rank + 1) % world} - {rank}):
-                    if blobs[src] is None:
-                        ok = 0
-                    else:
-                        got = import_guarded(blobs[src], os.environ.get("COMMET_IPC_PROBE_LIMIT_S", "30"))   # (four reads: seconds are generous) every rank's probe set holds the same reads:
-                        if hasattr(eng, "same_set") and not eng.same_set(got, probe):   # a copy that arrives damaged counts as no hand-over
-                            say("device-to-device hand-over of sets: the probe set did not arrive intact: packed images instead")
-                            ok = 0
-                        eng.release(got)
-            except Exception as ex:
-                say(f"device-to-device hand-over of sets not available ({ex}): packed images instead")
-                ok = 0
-        use_ipc = ranks.sum_int(ok) == world                      # (also: every import of the probes is done)
-        if probe is not None:
-            eng.release(probe)
-    note(f"{N} sets, {len(mine)} of {len(pairs)} pairs on this rank; sets are handed over " + ("device to device" if use_ipc else "as packed images" if world > 1 else "nowhere (one rank)"))
-    exported = {}                                                 # sets this rank keeps alive for the others' imports
-    loader, loader_stop = None, None
-    prof = dict(rank=rank, pairs=len(mine), sets_parsed=0, sets_loaded=0, j1_builds=0, parse_s=0.0, save_s=0.0, load_s=0.0,
-                jobs=0, call_ms=0.0, device_ms=0.0, handover="ipc" if use_ipc else "image", backend=getattr(ranks, "backend", None),
-                torch_loaded="torch" in sys.modules,
-                predicted_share=round(sum(pair_cost[c] for c in runs[rank]) / max(sum(pair_cost), 1e-9), 4))   # what the static cut expects of this rank
-    # the canary: of the ranks that take sets from others, the first one starts a fresh child process that imports the first
-    # real set to appear (tests/engines without a child command: no canary)
-    def foreign(r):
-        return sorted({s_ for c in runs[r] for s_ in pairs[c] if owner[s_] != r})
-
-    canary_rank = next((r for r in range(world) if foreign(r)), None) if use_ipc else None
-    canary = None
-    if use_ipc and rank == canary_rank and hasattr(eng, "canary_argv") and os.environ.get("COMMET_IPC_CANARY", "1") != "0":
-        canary = subprocess.Popen(eng.canary_argv(scratch, foreign(rank)), stdout=subprocess.DEVNULL)
-    server, serve_stop, stop_ev = None, None, None
+    note(f"{N} sets, {len(cut.mine)} of {len(cut.pairs)} pairs on this rank; sets are handed over "
+         + ("device to device" if prof["handover"] == "ipc" else "as packed images" if world > 1 else "nowhere (one rank)"))
+    if hand is not None:
+        canary_rank = next((r for r in range(world) if _foreign(cut, r)), None)
+        hand.start_canary(canary_rank, _foreign(cut, rank))
+    loader = Loader(eng, cfg, cut, filters, hand, ranks, prof, stop_ev)
     try:
-        # ---- residency: parse my sets once, publish their packed images, load the others I need ----------------
-        t0 = time.perf_counter()
-        sets = {}
-        solo = pipelined and world == 1                           # (then the loading thread parses, too)
-
-        device_sel = {}                                           # set -> its per-file (count, bits), made on the device (device_filters)
-
-        def device_filter(s, rs):
-            """the selection of set s from the resident copy this rank holds; the per-file cap is what the tool's atoi makes of the
-            `-m` the driver passes it (str(m / files of the set))"""
-            if s not in device_sel:
-                w0 = time.perf_counter()
-                bits, _ = eng.filter_set(rs, l, n, e, c_atoi(str(m / len(files[s]))) if m >= 0 else -1)
-                cs = eng.file_reads(rs)
-                device_sel[s] = list(zip(cs, split_bits(bits, cs)))
-                device_filter_s[0] += time.perf_counter() - w0
-            return device_sel[s]
-
-        def leave_filters(s, rs):
-            """the filter files of a set this rank has just parsed: from its record counts (default options), or the device's selection"""
-            if synth_filters:
-                for c_, f_, b_ in zip(eng.file_reads(rs), files[s], bvs[s]):
-                    default_filter_bv(b_, f_, c_)
-            elif device_filters:
-                parts = device_filter(s, rs)
-                w0 = time.perf_counter()
-                for (c_, bits_), f_, b_ in zip(parts, files[s], bvs[s]):
-                    write_filter_bv(b_, f_, c_, bits_, l, n, e)
-                device_filter_s[0] += time.perf_counter() - w0
-
-        def parse_own(s):
-            """one of this rank's sets: parsed here and nowhere else; its packed image published for the ranks that need it
-            (commet_readset_save writes a .tmp and renames it: the file appears complete or not at all)"""
-            w0 = time.perf_counter()
-            rs = eng.parse(files[s])
-            prof["parse_s"] += time.perf_counter() - w0
-            prof.setdefault("parse_log", []).append([s, round(time.perf_counter() - w0, 4)])
-            prof["sets_parsed"] += 1
-            leave_filters(s, rs)
-            if s in needed_by_others:
-                w0 = time.perf_counter()
-                if use_ipc:                                       # a small descriptor file; the set stays alive for the importers
-                    path = os.path.join(scratch, f"set{s}.ipc")
-                    with open(path + ".tmp", "wb") as fh:
-                        fh.write(eng.export_set(rs))
-                    os.rename(path + ".tmp", path)
-                    exported[s] = rs
-                else:
-                    eng.save(rs, os.path.join(scratch, f"set{s}.pk"))
-                prof["save_s"] += time.perf_counter() - w0
-            if s in needed:
-                sets[s] = rs
-            elif s not in exported:
-                eng.release(rs)
-
-        if not pipelined:
-            for s in owned:
-                if s in needed or s in needed_by_others:
-                    parse_own(s)
-            ranks.barrier()                                      # every image is in place
-        counts, sel, considered = {}, {}, {}
-
-        def prepare(s):
-            """set s is resident; once its filter files are there (written by whichever rank filtered them): its per-file read
-            counts, its input selection, the number of reads it was asked about (the matrix's diagonal)"""
-            counts[s] = eng.file_reads(sets[s])
-            if filtered_here:
-                for b in bvs[s]:
-                    if not wait_file(b, f"the filter of set {s}", where=os.path.dirname(b)):
-                        return False
-            if synth_filters:                                     # all ones (the set's owner has left the files: leave_filters)
-                parts = [(c, default_filter_bv(None, f, c)) for c, f in zip(counts[s], files[s])]
-            elif device_filters:                                  # from the copy this rank holds (its owner has left the files, too)
-                parts = device_filter(s, sets[s])
-            else:
-                parts = [read_bv(b) for b in bvs[s]]
-            considered[s] = sum(popcount(b, nb) for nb, b in parts)
-            for (nb, _), c, f in zip(parts, counts[s], files[s]):
-                if nb != c:
-                    raise eng.mismatch_error(f"Number of reads in {f} and boolean vector size are not equal -> quit")
-            _, sel[s] = concat_bits(parts)
-            if considered[s] == sum(counts[s]) and os.environ.get("COMMET_MATRIX_KEEP_SEL", "0") != "1":
-                sel[s] = None                                     # every read selected (the default filters): no bitmap to upload, dense plans
-            return True
-
-        stop_ev = threading.Event()                               # set when this rank is through (or has failed): ends every wait below
-        hand = dict(ipc=use_ipc, canary=None)
-
-        def wait_file(path, what, where=None):
-            """a file another rank publishes (renamed into place: complete or absent): there once its owner has got that far
-            (or never, if that rank died: the launcher then ends this process; the deadline only bounds a stray wait)"""
-            deadline = time.perf_counter() + float(os.environ.get("COMMET_DIST_TIMEOUT_S", "600"))
-            w0 = time.perf_counter()
-            polls = 0
-            while not os.path.exists(path):
-                if filter_err:
-                    raise filter_err[0]
-                if stop_ev.is_set():
-                    return False
-                polls += 1
-                if polls % 128 == 0 and hasattr(ranks, "check"):   # (every quarter of a second: has the rank that is to publish it given up?)
-                    ranks.check()
-                if time.perf_counter() > deadline:
-                    raise RuntimeError(f"{what} did not appear in {where or scratch}")
-                time.sleep(0.002)
-            prof["image_wait_s"] = prof.get("image_wait_s", 0.0) + time.perf_counter() - w0
-            return True
-
-        def canary_verdict():
-            """Did the fresh child process of `canary_rank` get the first real set across?  That rank waits for its child (and
-            kills it by its pid when it does not answer in COMMET_IPC_CANARY_S), says so in the scratch directory, the others
-            read it there.  True: this process imports, too."""
-            if hand["canary"] is None:
-                ok_path, fail_path = os.path.join(scratch, "canary.ok"), os.path.join(scratch, "canary.fail")
-                if rank == canary_rank:
-                    verdict = "passed"
-                    if canary is not None:
-                        limit = float(os.environ.get("COMMET_IPC_CANARY_S", "30"))
-                        try:
-                            rc = canary.wait(timeout=limit)
-                            verdict = "passed" if rc == 0 else f"failed (exit code {rc})"
-                        except subprocess.TimeoutExpired:
-                            canary.kill()
-                            try:
-                                canary.wait(timeout=5)
-                            except subprocess.TimeoutExpired:
-                                pass
-                            verdict = f"failed (no answer within {limit:.0f} s: killed)"
-                    path = ok_path if verdict == "passed" else fail_path
-                    with open(path + ".tmp", "w") as fh:
-                        fh.write(verdict)
-                    os.rename(path + ".tmp", path)
-                else:
-                    deadline = time.perf_counter() + float(os.environ.get("COMMET_DIST_TIMEOUT_S", "600"))
-                    while not (os.path.exists(ok_path) or os.path.exists(fail_path)):
-                        if stop_ev.is_set() or time.perf_counter() > deadline:
-                            break
-                        time.sleep(0.002)
-                    verdict = "passed" if os.path.exists(ok_path) else (open(fail_path).read() if os.path.exists(fail_path) else "failed (no verdict)")
-                hand["canary"] = verdict
-                prof["ipc_canary"] = verdict
-            return hand["canary"] == "passed"
-
-        def fetch(s):
-            """another rank's set: from its owner's device buffers, or from its packed image; False: this rank is stopping"""
-            ipc_path, pk_path = os.path.join(scratch, f"set{s}.ipc"), os.path.join(scratch, f"set{s}.pk")
-            if hasattr(ranks, "check"):
-                ranks.check()                                     # (no import from a job that has lost a rank: its owner may be leaving)
-            if hand["ipc"]:
-                if not wait_file(ipc_path, f"the descriptor of set {s}"):
-                    return False
-                if not canary_verdict():                          # (the first set only)
-                    hand["ipc"] = False
-                    prof["handover"] = "image"
-                    note(f"device-to-device hand-over given up (canary {hand['canary']}): packed images from here on")
-            w0 = time.perf_counter()
-            if hand["ipc"]:
-                with open(ipc_path, "rb") as fh:
-                    sets[s] = import_guarded(fh.read())
-            else:
-                if use_ipc:                                       # the owners published descriptors only: ask for the image
-                    open(os.path.join(scratch, f"set{s}.want.{rank}"), "w").close()
-                w0 = time.perf_counter()
-                if not wait_file(pk_path, f"the packed image of set {s}"):
-                    return False
-                w0 = time.perf_counter()
-                sets[s] = eng.load(pk_path)
-            prof["load_s"] += time.perf_counter() - w0
-            prof["sets_loaded"] += 1
-            return True
-
-        def serve_images():
-            """the way back: a rank that gave the device-to-device hand-over up asks for `set<s>.pk`; its owner, which keeps
-            every exported set alive, writes it"""
-            served = set()
-            while not serve_stop.wait(0.005):
-                for s_ in list(exported):
-                    if s_ not in served and any(f.startswith(f"set{s_}.want.") for f in os.listdir(scratch)):
-                        w0 = time.perf_counter()
-                        eng.save(exported[s_], os.path.join(scratch, f"set{s_}.pk"))
-                        prof["save_s"] += time.perf_counter() - w0
-                        served.add(s_)
-
-        server, serve_stop = None, threading.Event()
-        if use_ipc and any(s_ in needed_by_others for s_ in owned):
-            server = threading.Thread(target=serve_images, name="commet-image-server", daemon=True)
-            server.start()
-
-        refs = sorted({p[0] for p in mine}, reverse=pipelined)    # pipelined: last reference set first
-        if not pipelined:
-            for s in needed:
-                if s not in sets:
-                    fetch(s)                                      # (its owner's descriptor / image is in place behind the barrier)
-            for s in needed:
-                prepare(s)
-            load_s = time.perf_counter() - t0
-            say(f"loaded {N} sets in {load_s:.2f} s (rank 0: {prof['sets_parsed']} parsed, {prof['sets_loaded']} from packed images)")
+        if hand is not None and hand.use_ipc and any(s in cut.needed_by_others for s in cut.owned):
+            hand.start_server()
+        refs = sorted({p[0] for p in cut.mine}, reverse=pipelined)    # pipelined: last reference set first
+        if pipelined:
+            loader.start(refs)
         else:
-            # A second host thread makes the sets resident in the order the jobs want them (read sets are made on a stream
-            # of their own, include/commet_hip.h) while this one runs the jobs of a reference set as soon as it and its
-            # targets are there: the host-bound loading hides behind the device-bound jobs.  One rank: the thread parses
-            # the files, last set first, and ref = N-2, N-3, ... need the sets ref .. N-1.  Several ranks: the thread parses
-            # this rank's own sets and publishes them, then takes the others' as they appear (no barrier in between).
-            ready = [threading.Event() for _ in range(N)]
-            jobs_done = threading.Event()
-            loader_stop = stop_ev
-            load_err = []
-            load_end = [t0]
-            if solo:
-                order = list(range(N - 1, -1, -1))
-                own_first = []
-            else:
-                order = []
-                for ref in refs:
-                    for s in [ref] + [i for (r, i) in mine if r == ref]:
-                        if s not in order:
-                            order.append(s)
-                # Several ranks: nobody waits at a barrier for every set of the node to be parsed.  This rank parses its own
-                # sets first — the ones most ranks wait for first — and publishes their images; then it takes the other
-                # ranks' images, in the order its jobs want them, as soon as each file appears.  Its first job starts when
-                # the two sets of that job are there, whatever the other ranks are still parsing.
-                wanted_by = {s_: sum(1 for r in range(world) if any(s_ in pairs[c] for c in runs[r])) for s_ in owned}
-                own_first = sorted((s_ for s_ in owned if s_ in needed or s_ in needed_by_others), key=lambda s_: (-wanted_by[s_], s_))
-                # (simulated and NOT adopted in round 6: parsing first the sets some rank cannot start without — in every pair of its run —
-                # helps the ranks that wait for those and delays the one with the longest run: configs[3] at eight ranks 2.50 against 2.58 s
-                # with one run's fitted costs, 2.65 against 2.53 s with another's: tools/schedule_sim.py, blocking_first)
-
-            loaded_all = [False]
-
-            def reserve_lists():
-                """COMMET_MATRIX_LARGE_LISTS=1 (off by default): query lists above the library's cap (a 50 M-read set's is 11 GB; it saves
-                ~12 ms of every J2 / J3 job that searches the set) for the sets this rank searches three times or more; their memory is asked
-                from the driver HERE, by the loader thread once every set is resident, and a set whose memory waits in the library's device
-                cache gets its list at its next eligible scan but one.  Measured on configs[3] (profiles/r05_large_lists): 11.0 s against
-                11.8 s on a box whose device memory had been used before (the driver's 110 GiB take no time there), 13.4 s on a fresh box —
-                there hipMalloc costs 15-30 ms per GiB (3.4 s), and while one thread is inside hipMalloc the HIP calls of every other thread
-                of the process wait, so the job thread stands still with it.  Hence opt-in: for long-lived hosts."""
-                if os.environ.get("COMMET_MATRIX_LARGE_LISTS", "0") != "1" or not hasattr(eng, "list_estimate"):
-                    return
-                scans = {}
-                for (r_, i_) in mine:                            # J2 searches the reference set, J3 the target (Commet.py:220, 233)
-                    scans[r_] = scans.get(r_, 0) + 1
-                    scans[i_] = scans.get(i_, 0) + 1
-                want = [s_ for s_ in sorted(scans, key=lambda s_: -scans[s_]) if scans[s_] >= 3 and s_ in sets]
-                est = {s_: eng.list_estimate(sets[s_]) for s_ in want}
-                want = [s_ for s_ in want if est[s_] > (4 << 30)]          # (smaller lists are the library's default already)
-                budget = 0.4 * eng.device_total()
-                got = 0
-                for s_ in want:
-                    if loader_stop.is_set() or jobs_done.is_set() or sum(est[x] for x in want[:want.index(s_) + 1]) > budget:
-                        break
-                    eng.reserve_list(sets[s_])
-                    got += 1
-                prof["lists_reserved"] = got
-                if got:
-                    note(f"memory of {got} large query lists set aside ({sum(est[x] for x in want[:got]) / 2**30:.0f} GiB)")
-
-            def load_all():
-                try:
-                    for s in own_first:
-                        if loader_stop.is_set():
-                            return
-                        parse_own(s)
-                    for s in order:
-                        if loader_stop.is_set():                 # the job thread has failed
-                            break
-                        if solo:
-                            w0 = time.perf_counter()
-                            sets[s] = eng.parse(files[s])
-                            prof["parse_s"] += time.perf_counter() - w0
-                            prof.setdefault("parse_log", []).append([s, round(time.perf_counter() - w0, 4)])
-                            prof["sets_parsed"] += 1
-                            leave_filters(s, sets[s])
-                        elif s not in sets and not fetch(s):
-                            break
-                        if not prepare(s):
-                            break
-                        ready[s].set()
-                        note(f"set {s} resident")
-                    load_end[0] = time.perf_counter()
-                    loaded_all[0] = True
-                    reserve_lists()
-                except BaseException as ex:          # handed to the job thread, which is waiting for a set
-                    load_err.append(ex)
-                    for ev in ready:
-                        ev.set()
-                finally:
-                    if not loaded_all[0]:
-                        load_end[0] = time.perf_counter()
-
-            loader = threading.Thread(target=load_all, name="commet-set-loader", daemon=True)
-            loader.start()
-        set_wait = [0.0]
-
-        def wait_for(s):
-            if loader is not None:
-                w0 = time.perf_counter()
-                polls = 0
-                while not ready[s].wait(0.05):
-                    if filter_err:                               # a filter_reads process of this rank failed
-                        raise filter_err[0]
-                    polls += 1
-                    if world > 1 and polls % 5 == 0 and hasattr(ranks, "check"):
-                        ranks.check()                            # (has a rank given up?  Its sets will never come)
-                set_wait[0] += time.perf_counter() - w0
-                if load_err:
-                    raise load_err[0]
-
-        # ---- my pairs, grouped by ref ------------------------------------------------------------------------
-        shared = {}                    # (from set, in set) -> reads of `from` found in `in`
-        reads_searched = 0
-
-        call_log = os.environ.get("COMMET_MATRIX_CALL_LOG")   # one line per library call: jobs, wall, event-timed device time, python clock
-
-        job_log = prof.setdefault("job_log", [])   # one row per library call: [kind, search set or reference, [the other sets], index ms, search ms, call ms]
-                                                   # (what tools/schedule_sim.py replays on the pair cut of N ranks)
-
-        def _acc(inf, n=1, what=None):
-            prof["jobs"] += n
-            prof["call_ms"] += inf["total_ms"]
-            prof["device_ms"] += inf["index_ms"] + inf["search_ms"]
-            if what is not None:
-                job_log.append([what[0], what[1], list(what[2]), round(inf["index_ms"], 3), round(inf["search_ms"], 3), round(inf["total_ms"], 3)])
-            if call_log:
-                with open(call_log, "a") as fh:
-                    fh.write(f"{rank} {n} {inf['total_ms']:.3f} {inf['index_ms']:.3f} {inf['search_ms']:.3f} {time.perf_counter():.6f}\n")
-
-        # the .bv and .log files of a job are written by two helper threads while the next job runs (6 MB per 50 M-read file: 3-4 ms
-        # of a job's ~6 ms of host time at configs[3]); all of them are on disk before the jobs' clock stops
-        from concurrent.futures import ThreadPoolExecutor
-        writer, written = ThreadPoolExecutor(2), []
-
-        def out_bv(path, comment, c, b):
-            written.append(writer.submit(write_bv, path, comment, c, b))
-
-        def out_log(*a):
-            written.append(writer.submit(_log, *a))
-
-        def jobs_on_one_search_set(index_ids, search_id, selections, kind="J2"):
-            """Jobs that search the SAME set — the J2 jobs of a reference set, the J3 jobs of a target (Commet.py:220, 233) — in one call
-            where the engine has one (commet_index_many_and_search: their chunk filters share passes over the search set: the lane-a
-            gathers of its reads, two thirds of such a job's memory requests, are made once per pass instead of once per job);
-            -> [(tags, stats, index_ms)] in the jobs' order, bit for bit what the jobs give one by one."""
-            if not index_ids:
-                return []
-            if hasattr(eng, "index_many_and_search") and len(index_ids) > 1:
-                tags, st, inf = eng.index_many_and_search([sets[x] for x in index_ids], sets[search_id], selections, sel[search_id])
-                _acc(inf, len(index_ids), (kind, search_id, index_ids))
-                return [(tags[j], st[j], inf["index_ms"] / len(index_ids)) for j in range(len(index_ids))]
-            out = []
-            for x, sl in zip(index_ids, selections):
-                tags, st, inf = eng.index_and_search(sets[x], [sets[search_id]], sl, [sel[search_id]])
-                _acc(inf, 1, (kind, search_id, [x]))
-                out.append((tags[0], st[0], inf["index_ms"]))
-            return out
-
-        # Order of a rank's jobs: per reference set J1 (its index built once for all its targets), then the J2 jobs of its targets
-        # together (they all search S_ref); the J3 jobs — (ref, i) searches S_i — are kept back and run target by target at the end, so
-        # that the J3 jobs of a target share passes as well.  The files a job writes do not depend on when it runs.
+            loader.load_first()
+            say(f"loaded {N} sets in {loader.load_end - loader.t0:.2f} s (rank 0: {prof['sets_parsed']} parsed, {prof['sets_loaded']} from packed images)")
+        jobs = Jobs(eng, loader.sets, loader.sel, loader.counts, loader.considered, prof, cfg.names, cfg.files, cfg.out_dir)
         t_jobs = time.perf_counter()
-        kept_T2 = {}                   # (ref, i) -> J2's result, the index selection of J3(ref, i); freed as J3 consumes it
-        refs_left = {}                 # target -> reference sets of this rank's pairs that have not been through J2 yet
-        for (r_, i_) in mine:
-            refs_left[i_] = refs_left.get(i_, 0) + 1
-
-        def j3_of(i):
-            """J3 of every pair of target i: S_i in (S_ref restricted to J2's result) — overwrites J1's <F>_in_<S_ref>.bv (Commet.py:233)"""
-            nonlocal reads_searched
-            w0 = time.perf_counter()
-            wait_for(i)
-            of_i = [r for (r, t_) in mine if t_ == i]
-            for ref, (T3, st3, index_ms) in zip(of_i, jobs_on_one_search_set(of_i, i, [kept_T2.pop((r, i)) for r in of_i], "J3")):
-                for f, c, b in zip(files[i], counts[i], split_bits(T3, counts[i])):
-                    out_bv(out_dir + os.path.basename(f) + "_in_" + names[ref] + ".bv", f + " in " + names[ref], c, b)
-                out_log(out_dir, names[i], names[ref], st3, index_ms, time.perf_counter() - w0)
-                shared[(i, ref)] = st3["shared"]
-                reads_searched += considered[i]
-            note(f"J3 jobs of set {i} done ({prof['jobs']} so far)")
-
         try:
-            # Which reference set next (round 6): the first of the rank's list that is resident TOGETHER with one of its targets — a rank of a
-            # node starts on whatever pair has arrived instead of waiting for the first reference set of its list (tools/schedule_sim.py on
-            # configs[3]: 2.69 -> 2.53 s at eight ranks, 4.24 -> 3.97 s at four).  A reference set some of whose targets are still on their way
-            # is taken up again later (one more index build of S_ref instead of an idle GPU, as before).  One rank, or everything loaded
-            # first: the list's own order.
-            def there(s_):
-                return loader is None or ready[s_].is_set()
-
-            left = {ref: [i for (r, i) in mine if r == ref] for ref in refs}
-            while left:
-                ref = next((r_ for r_ in refs if r_ in left and there(r_) and any(there(i) for i in left[r_])), None)
-                if ref is None:                                      # nothing can start: until some set arrives (errors of the loader / the filters / another rank end the wait)
-                    w0 = time.perf_counter()
-                    polls = 0
-                    while not any(there(r_) and any(there(i) for i in left[r_]) for r_ in left):
-                        if filter_err:
-                            raise filter_err[0]
-                        if load_err:
-                            raise load_err[0]
-                        polls += 1
-                        if world > 1 and polls % 125 == 0 and hasattr(ranks, "check"):
-                            ranks.check()
-                        time.sleep(0.002)
-                    set_wait[0] += time.perf_counter() - w0
-                    continue
-                targets = [i for i in left[ref] if there(i)]
-                left[ref] = [i for i in left[ref] if i not in targets]
-                for s_need in [ref] + targets:
-                    wait_for(s_need)                                 # (resident: raises what the loader raised, if it did)
-                w0 = time.perf_counter()
-                tags1, st1, inf1 = eng.index_and_search(sets[ref], [sets[i] for i in targets], sel[ref], [sel[i] for i in targets])
-                prof["j1_builds"] += 1
-                reads_searched += sum(considered[i] for i in targets)
-                _acc(inf1, 1, ("J1", ref, targets))
-                # J2 of every target: X_i = S_i restricted to (S_i in S_ref); S_ref in X_i
-                for i, (T2, st2, index_ms) in zip(targets, jobs_on_one_search_set(targets, ref, list(tags1))):
-                    for f, c, b in zip(files[ref], counts[ref], split_bits(T2, counts[ref])):
-                        out_bv(out_dir + os.path.basename(f) + "_in_" + names[i] + ".bv", f + " in " + names[i], c, b)
-                    out_log(out_dir, names[ref], names[i], st2, index_ms, time.perf_counter() - w0)
-                    shared[(ref, i)] = st2["shared"]
-                    kept_T2[(ref, i)] = T2
-                    reads_searched += considered[ref]
-                if not left[ref]:
-                    del left[ref]
-                    note(f"J1 and J2 jobs of set {ref} done ({prof['jobs']} so far)")
-                # The J3 jobs — (ref, i) searches S_i — are kept back so that the J3 jobs of a target share passes as well, but no longer than
-                # needed: a target's batch runs as soon as the last of its reference sets on this rank has been through J2 (its J2 bitmaps are
-                # freed with it, its files are on disk: a late failure loses little).  The files a job writes do not depend on when it runs.
-                for i in targets:
-                    refs_left[i] -= 1
-                for i in sorted(targets):
-                    if refs_left[i] == 0:
-                        j3_of(i)
-            for i in sorted(i_ for i_, n_ in refs_left.items() if n_ > 0):     # (never: every target's references are in `refs`)
-                j3_of(i)
+            _schedule(cut, refs, loader, jobs, note)
         except BaseException:
-            writer.shutdown(wait=False, cancel_futures=True)
+            jobs.cancel()
             raise
-        eng.synchronize()
-        if loader is not None:
-            jobs_done.set()                                      # (no list memory is set aside for jobs that are over)
-        for f in written:                                        # (what a writer raised is raised here)
-            f.result()
-        writer.shutdown()
-        jobs_s = time.perf_counter() - t_jobs - set_wait[0]      # (pipelined: without the waits for sets still being loaded)
-        prof["jobs_s"] = jobs_s
-        prof["set_wait_s"] = set_wait[0]
-        if hasattr(eng, "alloc_stats"):
-            a_ = eng.alloc_stats()
-            prof["alloc_wait_ms"], prof["fresh_device_bytes"], prof["alloc_calls"] = round(a_["wait_ms"], 1), a_["fresh_bytes"], a_["calls"]
-        if hasattr(eng, "kernel_times") and eng.kernel_times() is not None:
-            prof["kernel_ms"] = eng.kernel_times()
-        if loader is not None:
-            for s in order:                                      # (one rank: a set no pair needs is still loaded and counted)
-                wait_for(s)
-            loader.join()
-            load_s = load_end[0] - t0
-        filters_done()                                           # (this rank's filter processes: what one of them raised is raised here)
+        loader.jobs_done.set()                                    # (no list memory is set aside for jobs that are over)
+        jobs_s = jobs.finish() - t_jobs - loader.set_wait         # (pipelined: without the waits for sets still being loaded)
+        prof["jobs_s"], prof["set_wait_s"] = jobs_s, loader.set_wait
+        load_s = loader.finish()
+        filters.done()                                            # (this rank's filter processes: what one of them raised is raised here)
         # ---- matrices on rank 0 -----------------------------------------------------------------------------
-        everyone = ranks.gather_objects((shared, prof, considered))   # (every rank is through its jobs: nobody asks for a set any more)
-        if server is not None:
-            serve_stop.set()
-            server.join()
-        result = None
-        if rank == 0:
-            mat = [[0] * N for _ in range(N)]
-            diag = {}
-            for d, _, cons in everyone:
-                diag.update(cons)                                # (every set is in some rank's pairs)
-                for (a, b), v in d.items():
-                    mat[a][b] = v
-            considered_all = [diag[s] for s in range(N)]
-            for s in range(N):
-                mat[s][s] = considered_all[s]
-            write_matrices(out_dir, names, considered_all, mat)
-            result = dict(names=names, considered=considered_all, matrix=mat)
-            say("All Commet work is done")
-            say("\t Output csv matrices are in:")
-            for f in ("matrix_plain.csv", "matrix_percentage.csv", "matrix_normalized.csv"):
-                say("\t\t" + out_dir + f)
+        everyone = ranks.gather_objects((jobs.shared, prof, loader.considered))   # (every rank is through its jobs: nobody asks for a set any more)
+        if hand is not None:
+            hand.stop()
+        result = _matrices(cfg, everyone) if rank == 0 else None
         slowest = ranks.max_seconds(jobs_s)
         slowest_load = ranks.max_seconds(load_s)
-        slowest_filter = ranks.max_seconds(filter_s)
-        total_searched = ranks.sum_int(reads_searched)
+        slowest_filter = ranks.max_seconds(filters.seconds)
+        total_searched = ranks.sum_int(jobs.reads_searched)
         total_s = ranks.max_seconds(time.perf_counter() - t_start)
         if result is not None:
-            # (the filter processes run beside the parsing: filter_s and load_s overlap, total_s is the wall time of it all)
-            result.update(filter_s=slowest_filter, load_s=slowest_load, filter_overlaps_load=filter_pool is not None,
-                          load_overlaps_jobs=pipelined, set_wait_s=prof.get("set_wait_s", 0.0), jobs_s=slowest, total_s=total_s,
-                          reads_searched=total_searched, world=world, rank0_profile=prof,
-                          per_rank=[p for _, p, _c in everyone],
-                          reads_per_s=total_searched / slowest if slowest > 0 else 0.0,
-                          reads_per_s_incl_load_and_filter=total_searched / total_s if total_s > 0 else 0.0)
+            _report(result, everyone, slowest_filter, slowest_load, filters.pool is not None, pipelined, slowest, total_s, total_searched, world)
             say(f"{total_searched} reads searched in {slowest:.3f} s of jobs on {world} GPU(s): {result['reads_per_s'] / 1e6:.1f} M reads/s "
                 f"({result['reads_per_s_incl_load_and_filter'] / 1e6:.1f} M reads/s with filter {slowest_filter:.2f} s + load {slowest_load:.2f} s)")
-        # (the gathers above come after every rank's loading: no import of an exported set is still under way)
-        for s_, rs in exported.items():
-            if s_ not in sets:
-                eng.release(rs)
-        for rs in sets.values():
+        if hand is not None:
+            hand.release_exported(loader.sets)
+        for rs in loader.sets.values():
             eng.release(rs)
         return result
     except BaseException as ex:
-        # with several ranks: tell the others at once (their waits end with an error naming this rank) instead of leaving them in a
-        # gather until the timeout
         if world > 1 and hasattr(ranks, "abort"):
-            if not isinstance(ex, RuntimeError) or "rendezvous" not in str(ex):
-                try:                                              # what this rank ran into may only be the wake of another rank's failure
-                    ranks.check()                                 # (scratch gone under its feet): then THAT is the error to report
-                except RuntimeError as first:
-                    raise first from ex
-            ranks.abort(f"{type(ex).__name__}: {ex}")
+            _tell_the_others(ranks, ex)
         raise
     finally:
         failed = sys.exc_info()[0] is not None
-        if stop_ev is not None:
-            stop_ev.set()
-        if failed and world > 1 and exported:
-            # the other ranks may be in the middle of importing a set of this one: they notice the abort within a quarter of a second
-            # and start no new import; what is under way takes tens of ms.  An exporter that left at once would leave them in a HIP
-            # call that never returns (seen: 120 s until their own watchdog).
-            time.sleep(float(os.environ.get("COMMET_ABORT_LINGER_S", "2")))
-        if loader is not None and loader.is_alive():             # (an error in the job thread)
-            loader.join(timeout=5.0 if failed else None)
-        stuck = loader is not None and loader.is_alive()         # in a HIP call that does not return: the process is on its way out
-        if server is not None and server.is_alive():
-            serve_stop.set()
-            server.join()
-        if canary is not None and canary.poll() is None:         # (never asked: this rank failed first)
-            canary.kill()
-        if filter_pool is not None:
-            filter_pool.shutdown(wait=True, cancel_futures=True)
+        stop_ev.set()
+        if failed and hand is not None:
+            hand.linger()
+        stuck = loader.join(failed)
+        if hand is not None:
+            hand.stop()
+        filters.shutdown()
         if not stuck:
-            eng.close()                                          # (never under a thread that is still inside the library)
-        if scratch is not None:
-            # rank 0 removes the scratch directory once everybody is through; a failing rank removes its own images
-            if sys.exc_info()[0] is None and not getattr(ranks, "failed", False):
-                ranks.barrier()
-                if rank == 0:
-                    shutil.rmtree(scratch, ignore_errors=True)
+            eng.close()                                           # (never under a thread that is still inside the library)
+        if hand is not None:
+            hand.cleanup(failed or getattr(ranks, "failed", False))
+
+
+# ---- a set budget: the plan's loads and evicts on one thread, its jobs on another --------------------------------------------------
+class PlanLoader:
+    """The loader thread of a run under a set budget: the plan's "load" and "evict" steps.  It parses a set at its first "load" (its
+    filter runs then, while the set is resident), offloads it at an "evict" it will come back from (releases it at its last one) and
+    restores it at a later "load" — as far ahead of the job thread as the budget allows, one load past a pending evict at most.
+    The job thread waits for a load (wait_load) and says how far it is (advance)."""
+
+    def __init__(self, eng, cfg, filters, steps, sizes, budget_bytes, prof, res, stop):
+        self.eng, self.files, self.names, self.note, self.filters = eng, cfg.files, cfg.names, cfg.note, filters
+        self.steps, self.sizes, self.budget_bytes, self.prof, self.res, self.stop = steps, sizes, budget_bytes, prof, res, stop
+        self.sets, self.counts, self.sel, self.considered = {}, {}, {}, {}
+        self.cv = threading.Condition()
+        self.done = [False] * len(steps)                          # "load" steps carried out
+        self.progress, self.resident, self.err = 0, 0, None       # progress: the job thread is through every step before it
+        self.t0 = self.load_end = time.perf_counter()
+        self.set_wait = 0.0
+        self.last_use = {}
+        for idx, st in enumerate(steps):
+            for s in ([st[1]] if st[0] in ("load", "evict") else [st[1]] + (list(st[2]) if st[0] == "j1" else [st[2]])):
+                self.last_use[s] = idx
+        self.thread = threading.Thread(target=self.load_all, name="commet-set-loader", daemon=True)
+
+    def first_load(self, s):
+        eng, prof = self.eng, self.prof
+        w0 = time.perf_counter()
+        rs = eng.parse(self.files[s])
+        prof["parse_s"] += time.perf_counter() - w0
+        prof["sets_parsed"] += 1
+        if hasattr(eng, "set_bytes") and eng.set_bytes(rs) > self.sizes[s]:
+            raise RuntimeError(f"set {self.names[s]} holds {eng.set_bytes(rs)} bytes on the device, {self.sizes[s]} were planned")
+        self.sets[s] = rs
+        self.filters.leave(s, rs)                                 # (while the set is resident, before its first offload)
+        self.counts[s], self.considered[s], self.sel[s] = self.filters.selection(s, rs)
+
+    def do_load(self, idx):
+        s, res = self.steps[idx][1], self.res
+        assert self.resident + self.sizes[s] <= self.budget_bytes
+        self.resident += self.sizes[s]                            # (counted before the memory is asked for)
+        res["peak_set_bytes"] = max(res["peak_set_bytes"], self.resident)
+        if s not in self.sets:
+            self.first_load(s)
+        else:
+            w0 = time.perf_counter()
+            self.eng.restore(self.sets[s])
+            res["reload_s"] += time.perf_counter() - w0
+            res["set_reloads"] += 1
+        res["set_loads"] += 1
+        self.load_end = time.perf_counter()
+        with self.cv:
+            self.done[idx] = True
+            self.cv.notify_all()
+        self.note(f"set {s} resident")
+
+    def load_all(self):
+        steps, sizes, cv = self.steps, self.sizes, self.cv
+        try:
+            for idx, st in enumerate(steps):
+                if self.stop.is_set():
+                    return
+                if st[0] == "load" and not self.done[idx]:
+                    self.do_load(idx)
+                elif st[0] == "evict":
+                    s = st[1]
+                    while True:
+                        with cv:
+                            if self.progress >= idx or self.stop.is_set():
+                                break
+                            nxt = idx + 1                         # one load ahead of the evict, where the budget has the room
+                            ahead = (nxt < len(steps) and steps[nxt][0] == "load" and not self.done[nxt]
+                                     and self.resident + sizes[steps[nxt][1]] <= self.budget_bytes)
+                            if not ahead:
+                                cv.wait(0.05)
+                                continue
+                        self.do_load(nxt)
+                    if self.stop.is_set():
+                        return
+                    if self.last_use[s] > idx:
+                        self.eng.offload(self.sets[s])
+                        self.res["set_offloads"] += 1
+                    else:
+                        self.eng.release(self.sets.pop(s))
+                    self.resident -= sizes[s]
+        except BaseException as ex:
+            with cv:
+                self.err = ex
+                cv.notify_all()
+
+    def wait_load(self, p):
+        """the job thread: step p, a load, is carried out (raises what the loader raised)"""
+        w0 = time.perf_counter()
+        with self.cv:
+            while not self.done[p] and self.err is None:
+                self.cv.wait(0.05)
+            if self.err is not None:
+                raise self.err
+        self.set_wait += time.perf_counter() - w0
+
+    def advance(self, p):
+        with self.cv:
+            self.progress = p
+            self.cv.notify_all()
+
+    def join(self, failed):
+        """-> the thread is stuck inside the library"""
+        if self.thread.is_alive():
+            self.thread.join(timeout=5.0 if failed else None)
+        return self.thread.is_alive()
+
+
+def _plan_jobs(steps, loader, jobs):
+    """the job thread of a run under a set budget: the plan's jobs, in its order"""
+    sel, considered, prof = jobs.sel, jobs.considered, jobs.prof
+    T1 = {}                                                       # (ref, i) -> J1's tags of S_i, until the pair's J2 takes them
+    p = 0
+    while p < len(steps):
+        st = steps[p]
+        if st[0] == "load":
+            loader.wait_load(p)
+            p += 1
+        elif st[0] == "evict":
+            p += 1
+        elif st[0] == "j1":
+            _, ref, targets = st
+            q = p + 1                                             # J1 of several reference sets against ONE streamed target: they all search it
+            while len(targets) == 1 and q < len(steps) and steps[q][0] == "j1" and steps[q][2] == targets:
+                q += 1
+            if q - p > 1:
+                i, of_i = targets[0], [r_ for _, r_, _t in steps[p:q]]
+                for r_, (tg, _st1, _ms) in zip(of_i, jobs.on_one_search_set(of_i, i, [sel[r_] for r_ in of_i], "J1")):
+                    T1[(r_, i)] = tg
+                prof["j1_builds"] += len(of_i)
+                jobs.reads_searched += considered[i] * len(of_i)
             else:
-                for s in owned:
-                    for ext in ("pk", "ipc"):
-                        try:
-                            os.remove(os.path.join(scratch, f"set{s}.{ext}"))
-                        except OSError:
-                            pass
-        if own_ranks and sys.exc_info()[0] is None:
-            ranks.close()
+                for i, tg in zip(targets, jobs.j1(ref, targets)):
+                    T1[(ref, i)] = tg
+            p = q
+        else:
+            q = p
+            while q < len(steps) and steps[q][0] == "pair":
+                q += 1
+            run_ = [(r_, i_) for _, r_, i_ in steps[p:q]]
+            w0 = time.perf_counter()
+            T2 = {}
+            a = 0
+            while a < len(run_):                                  # J2: consecutive pairs of one reference set search it together
+                b = a
+                while b < len(run_) and run_[b][0] == run_[a][0]:
+                    b += 1
+                ref, targets = run_[a][0], [i_ for _, i_ in run_[a:b]]
+                for i, (tg, st2, index_ms) in zip(targets, jobs.on_one_search_set(targets, ref, [T1.pop((ref, i)) for i in targets], "J2")):
+                    jobs.leave(ref, i, tg, st2, index_ms, w0)
+                    T2[(ref, i)] = tg
+                a = b
+            for i in dict.fromkeys(i_ for _, i_ in run_):         # J3: the pairs of one target search it together
+                of_i = [r_ for r_, i_ in run_ if i_ == i]
+                for ref, (tg, st3, index_ms) in zip(of_i, jobs.on_one_search_set(of_i, i, [T2.pop((r_, i)) for r_ in of_i], "J3")):
+                    jobs.leave(i, ref, tg, st3, index_ms, w0)
+            p = q
+        loader.advance(p)
 
 
-def _run_under_budget(input_file, out_dir, k, t, l, n, e, m, bin_dir, ranks, verbose, engine_factory, progress, budget_bytes, t_start):
+def _run_under_budget(cfg, k, t, n, e, m, ranks, make_engine, budget_bytes, t_start):
     """The matrix of one rank when the packed sets may hold at most budget_bytes of device memory together (--set-budget-gb).
 
     The reference runs one job at a time from disk and so finishes whatever N is (Commet.py:186-240); here residency.plan orders the
-    pair chains block by block, and two threads follow it: the loader parses a set at its first "load" (its filter runs then, while
-    the set is resident), offloads it at an "evict" it will come back from (releases it at its last one) and restores it at a later
-    "load" — as far ahead of the job thread as the budget allows, one load past a pending evict at most; the job thread runs the
-    plan's jobs in order.  J2 jobs that search one reference set and J3 jobs that search one target, their sets loaded together, still
-    share passes (jobs_on_one_search_set).  Every file written is what the unconstrained run writes: a job's result does not
+    pair chains block by block, and two threads follow it: the loader (PlanLoader) and the job thread, which runs the plan's jobs in
+    order (_plan_jobs).  J2 jobs that search one reference set and J3 jobs that search one target, their sets loaded together, still
+    share passes (Jobs.on_one_search_set).  Every file written is what the unconstrained run writes: a job's result does not
     depend on when it runs, nor on how J1 of its reference set was split (residency.py)."""
-    from concurrent.futures import ThreadPoolExecutor
-    if out_dir[-1] != "/":
-        out_dir += "/"
-    bin_dir = bin_dir or os.path.join(HERE, "bin")
-    os.makedirs(out_dir, exist_ok=True)
-    names, files, bvs = parse_set_file(input_file)
-    N = len(names)
-    say = print if verbose else (lambda *a, **kw: None)
-    note = progress if progress is not None else (lambda msg: None)
-    if l < k * t and l != 0:                                      # Commet.py:509-513
-        l = k * t
-    eng = (engine_factory or HipEngine)(k, t, ranks.local_rank)
-    writer = None
+    N, names, files, say, note = cfg.N, cfg.names, cfg.files, cfg.say, cfg.note
+    eng = make_engine(k, t, ranks.local_rank)
+    jobs, loader, filters = None, None, None
     stop = threading.Event()
-    loader = None
     try:
         lacking = [a for a in ("packed_bytes", "offload", "restore") if not hasattr(eng, a)]
         if lacking:
@@ -1142,255 +1034,40 @@ def _run_under_budget(input_file, out_dir, k, t, l, n, e, m, bin_dir, ranks, ver
             raise ValueError(f"{ex} [{', '.join(names[s] for s in big)}]") from None
         note(f"{N} sets of {sum(sizes) / 2**30:.2f} GiB under a set budget of {budget_bytes / 2**30:.2f} GiB: "
              f"{sum(1 for st in steps if st[0] == 'load')} loads planned")
-        # ---- filters (Commet.py:103-121), as in run(): all ones from the record counts, the device's selection, or filter_reads -----
-        tool = os.environ.get("COMMET_MATRIX_FILTER_TOOL", "0") == "1"
-        synth_filters = bvs is None and l == 0 and e == 0 and n < 0 and m < 0 and not tool
-        device_filters = bvs is None and not synth_filters and not tool and hasattr(eng, "filter_set")
-        t_filter = time.perf_counter()
-        filter_s = [0.0]
-        if bvs is None:
-            bvs = [[out_dir + os.path.basename(f) + ".bv" for f in fl] for fl in files]
-            if not synth_filters and not device_filters:
-                cmds = []
-                for s in range(N):
-                    for j in range(len(files[s])):
-                        cmds.append(filter_command(bin_dir, files[s][j], bvs[s][j], l, n, e, m, len(files[s])))
-                        say("Filtering command: " + " ".join(cmds[-1]))
-                with ThreadPoolExecutor(max_workers=int(os.environ.get("COMMET_FILTER_JOBS", "3"))) as pool:
-                    list(pool.map(lambda c: subprocess.run(c, check=True, stdout=subprocess.DEVNULL), cmds))
-                filter_s[0] = time.perf_counter() - t_filter
-
-        sets, counts, sel, considered = {}, {}, {}, {}
-        prof = dict(rank=0, pairs=N * (N - 1) // 2, sets_parsed=0, sets_loaded=0, j1_builds=0, parse_s=0.0, save_s=0.0, load_s=0.0, jobs=0,
-                    call_ms=0.0, device_ms=0.0, handover="none", backend=getattr(ranks, "backend", None), torch_loaded="torch" in sys.modules,
-                    predicted_share=1.0, job_log=[])
+        # ---- filters (Commet.py:103-121): filter_reads, where it is the way, is through before the first load
+        filters = Filters(files, cfg.bvs, cfg.out_dir, cfg.bin_dir, cfg.l, n, e, m, eng)
+        if filters.tool:
+            filters.start_tool(range(N), ranks, say)
+            filters.done()
+        prof = _profile(0, N * (N - 1) // 2, "none", ranks, 1.0)
         res = dict(set_budget_bytes=int(budget_bytes), set_sizing_s=sizing_s, set_loads=0, set_reloads=0, set_offloads=0, peak_set_bytes=0, reload_s=0.0)
-        last_use = {}
-        for idx, st in enumerate(steps):
-            for s in ([st[1]] if st[0] in ("load", "evict") else [st[1]] + (list(st[2]) if st[0] == "j1" else [st[2]])):
-                last_use[s] = idx
-
-        def first_load(s):
-            w0 = time.perf_counter()
-            rs = eng.parse(files[s])
-            prof["parse_s"] += time.perf_counter() - w0
-            prof["sets_parsed"] += 1
-            if hasattr(eng, "set_bytes") and eng.set_bytes(rs) > sizes[s]:
-                raise RuntimeError(f"set {names[s]} holds {eng.set_bytes(rs)} bytes on the device, {sizes[s]} were planned")
-            sets[s] = rs
-            counts[s] = eng.file_reads(rs)
-            if synth_filters:
-                parts = [(c_, default_filter_bv(b_, f_, c_)) for c_, f_, b_ in zip(counts[s], files[s], bvs[s])]
-            elif device_filters:                                  # while the set is resident, before its first offload
-                w0 = time.perf_counter()
-                bits, _ = eng.filter_set(rs, l, n, e, c_atoi(str(m / len(files[s]))) if m >= 0 else -1)
-                parts = list(zip(counts[s], split_bits(bits, counts[s])))
-                for (c_, bits_), f_, b_ in zip(parts, files[s], bvs[s]):
-                    write_filter_bv(b_, f_, c_, bits_, l, n, e)
-                filter_s[0] += time.perf_counter() - w0
-            else:
-                parts = [read_bv(b) for b in bvs[s]]
-            considered[s] = sum(popcount(b, nb) for nb, b in parts)
-            for (nb, _), c, f in zip(parts, counts[s], files[s]):
-                if nb != c:
-                    raise eng.mismatch_error(f"Number of reads in {f} and boolean vector size are not equal -> quit")
-            _, sel[s] = concat_bits(parts)
-            if considered[s] == sum(counts[s]) and os.environ.get("COMMET_MATRIX_KEEP_SEL", "0") != "1":
-                sel[s] = None
-
-        # ---- the loader thread: the plan's "load" and "evict" steps ----------------------------------------------------------------
-        cv = threading.Condition()
-        done = [False] * len(steps)                               # "load" steps carried out
-        state = dict(progress=0, resident=0, err=None)            # progress: the job thread is through every step before it
-        t0 = time.perf_counter()
-        load_end = [t0]
-
-        def do_load(idx):
-            s = steps[idx][1]
-            assert state["resident"] + sizes[s] <= budget_bytes
-            state["resident"] += sizes[s]                         # (counted before the memory is asked for)
-            res["peak_set_bytes"] = max(res["peak_set_bytes"], state["resident"])
-            if s not in sets:
-                first_load(s)
-            else:
-                w0 = time.perf_counter()
-                eng.restore(sets[s])
-                res["reload_s"] += time.perf_counter() - w0
-                res["set_reloads"] += 1
-            res["set_loads"] += 1
-            load_end[0] = time.perf_counter()
-            with cv:
-                done[idx] = True
-                cv.notify_all()
-            note(f"set {s} resident")
-
-        def load_all():
-            try:
-                for idx, st in enumerate(steps):
-                    if stop.is_set():
-                        return
-                    if st[0] == "load" and not done[idx]:
-                        do_load(idx)
-                    elif st[0] == "evict":
-                        s = st[1]
-                        while True:
-                            with cv:
-                                if state["progress"] >= idx or stop.is_set():
-                                    break
-                                nxt = idx + 1                     # one load ahead of the evict, where the budget has the room
-                                ahead = (nxt < len(steps) and steps[nxt][0] == "load" and not done[nxt]
-                                         and state["resident"] + sizes[steps[nxt][1]] <= budget_bytes)
-                                if not ahead:
-                                    cv.wait(0.05)
-                                    continue
-                            do_load(nxt)
-                        if stop.is_set():
-                            return
-                        if last_use[s] > idx:
-                            eng.offload(sets[s])
-                            res["set_offloads"] += 1
-                        else:
-                            eng.release(sets.pop(s))
-                        state["resident"] -= sizes[s]
-            except BaseException as ex:
-                with cv:
-                    state["err"] = ex
-                    cv.notify_all()
-
-        loader = threading.Thread(target=load_all, name="commet-set-loader", daemon=True)
-        loader.start()
-
-        # ---- the job thread: the plan's jobs, in its order ----------------------------------------------------------------------------
-        writer, written = ThreadPoolExecutor(2), []
-        shared, reads_searched, set_wait = {}, 0, 0.0
-        T1 = {}                                                   # (ref, i) -> J1's tags of S_i, until the pair's J2 takes them
-
-        def _acc(inf, njobs, what):
-            prof["jobs"] += njobs
-            prof["call_ms"] += inf["total_ms"]
-            prof["device_ms"] += inf["index_ms"] + inf["search_ms"]
-            prof["job_log"].append([what[0], what[1], list(what[2]), round(inf["index_ms"], 3), round(inf["search_ms"], 3), round(inf["total_ms"], 3)])
-
-        def jobs_on_one_search_set(index_ids, search_id, selections, kind):
-            if hasattr(eng, "index_many_and_search") and len(index_ids) > 1:
-                tags, st, inf = eng.index_many_and_search([sets[x] for x in index_ids], sets[search_id], selections, sel[search_id])
-                _acc(inf, len(index_ids), (kind, search_id, index_ids))
-                return [(tags[j], st[j], inf["index_ms"] / len(index_ids)) for j in range(len(index_ids))]
-            out = []
-            for x, sl in zip(index_ids, selections):
-                tags, st, inf = eng.index_and_search(sets[x], [sets[search_id]], sl, [sel[search_id]])
-                _acc(inf, 1, (kind, search_id, [x]))
-                out.append((tags[0], st[0], inf["index_ms"]))
-            return out
-
-        def leave(search, index, tags, st, index_ms, w0):
-            """the files of one J2 / J3 job: <file of `search`>_in_<index>.bv, <search>_in_<index>.log"""
-            for f, c, b in zip(files[search], counts[search], split_bits(tags, counts[search])):
-                written.append(writer.submit(write_bv, out_dir + os.path.basename(f) + "_in_" + names[index] + ".bv", f + " in " + names[index], c, b))
-            written.append(writer.submit(_log, out_dir, names[search], names[index], st, index_ms, time.perf_counter() - w0))
-            shared[(search, index)] = st["shared"]
-
+        loader = PlanLoader(eng, cfg, filters, steps, sizes, budget_bytes, prof, res, stop)
+        loader.thread.start()
+        jobs = Jobs(eng, loader.sets, loader.sel, loader.counts, loader.considered, prof, names, files, cfg.out_dir)
         t_jobs = time.perf_counter()
-        p = 0
-        while p < len(steps):
-            st = steps[p]
-            if st[0] == "load":
-                w0 = time.perf_counter()
-                with cv:
-                    while not done[p] and state["err"] is None:
-                        cv.wait(0.05)
-                    if state["err"] is not None:
-                        raise state["err"]
-                set_wait += time.perf_counter() - w0
-                p += 1
-            elif st[0] == "evict":
-                p += 1
-            elif st[0] == "j1":
-                _, ref, targets = st
-                q = p + 1                                         # J1 of several reference sets against ONE streamed target: they all search it
-                while len(targets) == 1 and q < len(steps) and steps[q][0] == "j1" and steps[q][2] == targets:
-                    q += 1
-                if q - p > 1:
-                    i, of_i = targets[0], [r_ for _, r_, _t in steps[p:q]]
-                    for r_, (tg, _st1, _ms) in zip(of_i, jobs_on_one_search_set(of_i, i, [sel[r_] for r_ in of_i], "J1")):
-                        T1[(r_, i)] = tg
-                    prof["j1_builds"] += len(of_i)
-                    reads_searched += considered[i] * len(of_i)
-                else:
-                    tags1, _st1, inf1 = eng.index_and_search(sets[ref], [sets[i] for i in targets], sel[ref], [sel[i] for i in targets])
-                    prof["j1_builds"] += 1
-                    reads_searched += sum(considered[i] for i in targets)
-                    _acc(inf1, 1, ("J1", ref, targets))
-                    for i, tg in zip(targets, tags1):
-                        T1[(ref, i)] = tg
-                p = q
-            else:
-                q = p
-                while q < len(steps) and steps[q][0] == "pair":
-                    q += 1
-                run_ = [(r_, i_) for _, r_, i_ in steps[p:q]]
-                w0 = time.perf_counter()
-                T2 = {}
-                a = 0
-                while a < len(run_):                              # J2: consecutive pairs of one reference set search it together
-                    b = a
-                    while b < len(run_) and run_[b][0] == run_[a][0]:
-                        b += 1
-                    ref, targets = run_[a][0], [i_ for _, i_ in run_[a:b]]
-                    for i, (tg, st2, index_ms) in zip(targets, jobs_on_one_search_set(targets, ref, [T1.pop((ref, i)) for i in targets], "J2")):
-                        leave(ref, i, tg, st2, index_ms, w0)
-                        T2[(ref, i)] = tg
-                        reads_searched += considered[ref]
-                    a = b
-                for i in dict.fromkeys(i_ for _, i_ in run_):     # J3: the pairs of one target search it together
-                    of_i = [r_ for r_, i_ in run_ if i_ == i]
-                    for ref, (tg, st3, index_ms) in zip(of_i, jobs_on_one_search_set(of_i, i, [T2.pop((r_, i)) for r_ in of_i], "J3")):
-                        leave(i, ref, tg, st3, index_ms, w0)
-                        reads_searched += considered[i]
-                p = q
-            with cv:
-                state["progress"] = p
-                cv.notify_all()
-        eng.synchronize()
-        for f in written:
-            f.result()
-        writer.shutdown()
-        writer = None
-        jobs_s = time.perf_counter() - t_jobs - set_wait
-        loader.join()
-        if state["err"] is not None:
-            raise state["err"]
-        prof["jobs_s"], prof["set_wait_s"] = jobs_s, set_wait
-        if hasattr(eng, "alloc_stats"):
-            a_ = eng.alloc_stats()
-            prof["alloc_wait_ms"], prof["fresh_device_bytes"], prof["alloc_calls"] = round(a_["wait_ms"], 1), a_["fresh_bytes"], a_["calls"]
-        mat = [[0] * N for _ in range(N)]
-        for (a, b), v in shared.items():
-            mat[a][b] = v
-        considered_all = [considered[s] for s in range(N)]
-        for s in range(N):
-            mat[s][s] = considered_all[s]
-        write_matrices(out_dir, names, considered_all, mat)
-        say("All Commet work is done")
+        _plan_jobs(steps, loader, jobs)
+        jobs_s = jobs.finish() - t_jobs - loader.set_wait
+        loader.thread.join()
+        if loader.err is not None:
+            raise loader.err
+        prof["jobs_s"], prof["set_wait_s"] = jobs_s, loader.set_wait
+        everyone = [(jobs.shared, prof, loader.considered)]
+        res.update(_matrices(cfg, everyone))
         total_s = time.perf_counter() - t_start
-        res.update(names=names, considered=considered_all, matrix=mat, filter_s=filter_s[0], load_s=load_end[0] - t0, filter_overlaps_load=False,
-                   load_overlaps_jobs=True, set_wait_s=set_wait, jobs_s=jobs_s, total_s=total_s, reads_searched=reads_searched, world=1,
-                   rank0_profile=prof, per_rank=[prof], j1_builds=prof["j1_builds"], reload_s=round(res["reload_s"], 6),
-                   reads_per_s=reads_searched / jobs_s if jobs_s > 0 else 0.0,
-                   reads_per_s_incl_load_and_filter=reads_searched / total_s if total_s > 0 else 0.0)
-        say(f"{reads_searched} reads searched in {jobs_s:.3f} s of jobs; {res['set_loads']} set loads ({res['set_reloads']} reloads, "
+        _report(res, everyone, filters.seconds, loader.load_end - loader.t0, False, True, jobs_s, total_s, jobs.reads_searched, 1)
+        res.update(j1_builds=prof["j1_builds"], reload_s=round(res["reload_s"], 6))
+        say(f"{jobs.reads_searched} reads searched in {jobs_s:.3f} s of jobs; {res['set_loads']} set loads ({res['set_reloads']} reloads, "
             f"{res['reload_s']:.3f} s), at most {res['peak_set_bytes'] / 2**30:.2f} of {budget_bytes / 2**30:.2f} GiB of sets resident")
-        for rs in sets.values():
+        for rs in loader.sets.values():
             eng.release(rs)
         return res
     finally:
         stop.set()
-        if writer is not None:
-            writer.shutdown(wait=False, cancel_futures=True)
-        failed = sys.exc_info()[0] is not None
-        if loader is not None and loader.is_alive():
-            loader.join(timeout=5.0 if failed else None)
-        if not (loader is not None and loader.is_alive()):
+        if jobs is not None:
+            jobs.cancel()
+        if filters is not None:
+            filters.shutdown()
+        if not (loader is not None and loader.join(sys.exc_info()[0] is not None)):
             eng.close()                                           # (never under a thread that is still inside the library)
 
 

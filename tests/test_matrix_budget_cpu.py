@@ -171,3 +171,59 @@ def test_an_engine_whose_sets_cannot_leave_is_refused(tmp_path):
     sets_txt, _ = _six_sets(tmp_path)
     with pytest.raises(RuntimeError, match="offload"):
         matrix.run(sets_txt, str(tmp_path / "out"), k=20, t=2, verbose=False, engine_factory=OracleEngine, set_budget_gb=1.0)
+
+
+def test_given_filter_files_under_a_budget(tmp_path):
+    """the set file names a .bv per file (Commet.py then runs no filter): the budgeted run reads them at a set's first load as the
+    unconstrained run does when the set arrives — the vectors are a default run's, a few reads taken out by hand"""
+    from commet_amd import matrix
+    sets_txt, sizes = _six_sets(tmp_path)
+    BudgetedOracle.budget = None
+    matrix.run(sets_txt, str(tmp_path / "prior"), k=20, t=2, verbose=False, engine_factory=BudgetedOracle)
+    os.makedirs(tmp_path / "given")
+    lines, reads = [], []
+    for ln in open(sets_txt).read().split("\n")[:6]:
+        name, fl = ln.split(":")[0], [f.strip() for f in ln.split(":")[1].split(";")]
+        items, total = [], 0
+        for f in fl:
+            nb, bits = matrix.read_bv(str(tmp_path / "prior" / (os.path.basename(f) + ".bv")))
+            bits = bits.copy()
+            for r in (0, 9, nb // 2, nb - 1):                     # (the first and the last read of the file among them)
+                bits[r >> 3] &= 0xFF ^ (1 << (r & 7))
+            bv = str(tmp_path / "given" / (os.path.basename(f) + ".bv"))
+            matrix.write_filter_bv(bv, f, nb, bits)
+            items.append(f + "," + bv)
+            total += nb
+        lines.append(name + ": " + "; ".join(items) + "\n")
+        reads.append(total)
+    (tmp_path / "sets_bv.txt").write_text("".join(lines))
+    free = matrix.run(str(tmp_path / "sets_bv.txt"), str(tmp_path / "free"), k=20, t=2, verbose=False, engine_factory=BudgetedOracle)
+    budget = sum(sorted(sizes)[-3:])
+    BudgetedOracle.budget = budget
+    res = matrix.run(str(tmp_path / "sets_bv.txt"), str(tmp_path / "tight"), k=20, t=2, verbose=False, engine_factory=BudgetedOracle,
+                     set_budget_gb=(budget + 0.5) / 2**30)
+    n_files = sum(ln.count(",") for ln in lines)
+    assert _same_files(str(tmp_path / "free"), str(tmp_path / "tight")) == n_files * 5       # (no filter files: they were given)
+    assert res["matrix"] == free["matrix"] and res["considered"] == free["considered"]
+    assert reads == [500, 700, 400, 650, 550, 600]
+    assert all(c < r for c, r in zip(res["considered"], reads))
+    assert res["considered"] == [r - 4 * ln.count(",") for r, ln in zip(reads, lines)]
+    assert res["set_reloads"] > 0 and BudgetedOracle.log["peak"] <= budget
+
+
+def test_job_order_of_one_rank_with_everything_loaded_first(tmp_path, monkeypatch):
+    """COMMET_MATRIX_PIPELINE=0 on one rank: the reference sets in their order, J1 then the J2 jobs of each, a target's J3 jobs as soon as
+    its last reference set is through — the [kind, search set or reference, other sets] of every library call (the CPU checker has no
+    call for several jobs on one search set: one row per job), as the driver made them before its scheduler was a function of its own"""
+    from commet_amd import matrix
+    sets_txt, _ = _six_sets(tmp_path)
+    monkeypatch.setenv("COMMET_MATRIX_PIPELINE", "0")
+    BudgetedOracle.budget = None
+    res = matrix.run(sets_txt, str(tmp_path / "out"), k=20, t=2, verbose=False, engine_factory=BudgetedOracle)
+    assert [row[:3] for row in res["per_rank"][0]["job_log"]] == [
+        ["J1", 0, [1, 2, 3, 4, 5]], ["J2", 0, [1]], ["J2", 0, [2]], ["J2", 0, [3]], ["J2", 0, [4]], ["J2", 0, [5]], ["J3", 1, [0]],
+        ["J1", 1, [2, 3, 4, 5]], ["J2", 1, [2]], ["J2", 1, [3]], ["J2", 1, [4]], ["J2", 1, [5]], ["J3", 2, [0]], ["J3", 2, [1]],
+        ["J1", 2, [3, 4, 5]], ["J2", 2, [3]], ["J2", 2, [4]], ["J2", 2, [5]], ["J3", 3, [0]], ["J3", 3, [1]], ["J3", 3, [2]],
+        ["J1", 3, [4, 5]], ["J2", 3, [4]], ["J2", 3, [5]], ["J3", 4, [0]], ["J3", 4, [1]], ["J3", 4, [2]], ["J3", 4, [3]],
+        ["J1", 4, [5]], ["J2", 4, [5]], ["J3", 5, [0]], ["J3", 5, [1]], ["J3", 5, [2]], ["J3", 5, [3]], ["J3", 5, [4]]]
+    assert all(len(row) == 6 for row in res["per_rank"][0]["job_log"])

@@ -61,7 +61,7 @@ def fit(job_log):
 
 
 def simulate(n_sets, world, model, parse_s, import_s, sizes=None, canary_s=0.0, ready_first=True, interleave=False, blocking_first=False):
-    """-> per-rank dicts + total seconds.  Mirrors matrix.run: pair cut, owner map, loader thread, job thread.
+    """-> per-rank dicts + total seconds.  Mirrors the unconstrained driver of commet_amd.matrix: _cut (pair cut, owner map), Loader (loader thread), _schedule (job thread).
     canary_s: no rank imports a set before the canary process has its verdict.  ready_first: the job thread starts with a reference
     set that is resident together with one of its targets (round 6; False = the fixed order of rounds 4-5, for comparison).
     interleave: the loader takes foreign sets that have appeared between two parses of its own — simulated and NOT adopted: it delays
