@@ -24,6 +24,16 @@ def bits_nbytes(n):
     return n // 8 + 1
 
 
+def tags_at(hits, t):
+    """BooleanVector bytes (bits_nbytes(n) long, padding bits zero) of the reads with at least t hits: from the counts of
+    Context.index_and_profile, the tags of a job at threshold t"""
+    h = np.asarray(hits, dtype=np.uint8)
+    out = np.zeros(bits_nbytes(h.size), dtype=np.uint8)
+    packed = np.packbits(h >= int(t), bitorder="little")
+    out[:packed.size] = packed
+    return out
+
+
 def _as_bits(arr, n, what):
     if arr is None:
         return None
@@ -193,6 +203,24 @@ class Context:
         st = [dict(indexed=int(stats[i].indexed), searched=int(stats[i].searched), shared=int(stats[i].shared),
                    search_ms=float(stats[i].search_ms)) for i in range(nj)]
         return tags, st, {f: getattr(info, f) for f, _ in _l.JobInfo._fields_}
+
+    def index_and_profile(self, index_rs, search_sets, index_select=None, search_selects=None, max_hits=8):
+        """commet_index_and_profile: the chunk loop with a search that does not stop at t.  Returns (hits, info): hits[i] = np.uint8
+        per read of search set i, min(max_hits, the read's greedy non-overlapping full hits on its better strand, in its best chunk);
+        tags_at(hits[i], t) is the BooleanVector index_and_search gives on a context of this k and that t, for every t in 1..max_hits."""
+        ns = len(search_sets)
+        isel = _as_bits(index_select, index_rs.num_reads, "index_select")
+        ssel = [None] * ns
+        if search_selects is not None:
+            ssel = [_as_bits(s, rs.num_reads, "search_select") for s, rs in zip(search_selects, search_sets)]
+        hits = [np.zeros(rs.num_reads, dtype=np.uint8) for rs in search_sets]
+        rs_arr = (C.c_void_p * max(ns, 1))(*[rs._h for rs in search_sets])
+        sel_arr = (C.c_void_p * max(ns, 1))(*[(_ptr(s).value if s is not None else None) for s in ssel])
+        hit_arr = (C.c_void_p * max(ns, 1))(*[(_ptr(h).value if h.size else None) for h in hits])
+        info = _l.JobInfo()
+        self._check(self._lib.commet_index_and_profile(self._h, index_rs._h, _ptr(isel), ns, rs_arr, sel_arr, int(max_hits), hit_arr,
+                                                       C.byref(info)))
+        return hits, {f: getattr(info, f) for f, _ in _l.JobInfo._fields_}
 
     def export_filter_reference(self):
         nbytes = int(2 ** (self.k - 1))

@@ -10,6 +10,7 @@
 #include "slice_search.hpp"
 #include "tile_search.hpp"
 #include "long_search.hpp"
+#include "hit_profile.hpp"
 #include "read_filter.hpp"
 #include "read_iter.hpp"
 #include "host/fasta_source.hpp"
@@ -55,5 +56,6 @@
 #include "capi/job_parts.hpp"        // what the two job entry points share: phase clock, timing recorder, device planner, pass steps
 #include "capi/job.hpp"              // commet_index_reads / _search_reads / _index_and_search
 #include "capi/multi.hpp"            // commet_index_many_and_search: several jobs on one search set, their filters in one pass
+#include "capi/profile.hpp"          // commet_index_and_profile: per-read hit counts, the tags of every t from one job
 #include "capi/options.hpp"          // commet_set_option, measurement hooks
 #include "capi/microbench.hpp"       // commet_membench / _ldsbench

@@ -422,6 +422,52 @@ int run_job(JobRun &j, bool want_times)
     return rc;
 }
 
+// the end of a job's device work (commet_index_and_search, commet_index_and_profile): the stream drained, the per-kernel times taken,
+// the selection list's length against the plan's
+int drain_job(JobRun &j, int rc)
+{
+    commet_ctx *c = j.c;
+    if (hipStreamSynchronize(c->stream) != hipSuccess && !rc) rc = fail("stream synchronize failed: %s", hipGetErrorString(hipGetLastError()));
+    c->kclock.collect();
+    j.clk.lap(j.ph_wait);
+    if (!rc && j.d_ids && (c->h_counters[N_COUNTERS - 1] & 0xFFFFFFFFull) != (j.ids_expected & 0xFFFFFFFFull))
+        rc = fail("internal error: the selection list holds %llu reads, the plan indexes %llu", (unsigned long long) (c->h_counters[N_COUNTERS - 1] & 0xFFFFFFFFull),
+                  (unsigned long long) j.ids_expected);
+    return rc;
+}
+
+// the job's account: the plan's numbers, the launches, the device times summed from the timer's brackets (stats[s].search_ms too)
+void fill_job_info(JobRun &j, int rc, commet_pair_stats *stats, commet_job_info *info, uint64_t scans, uint64_t probes)
+{
+    const int n_search = j.n_search;
+    double idx_ms = 0, srch_ms = 0, zero_ms = 0;
+    if (j.tm.timed && !rc) {
+        zero_ms = j.tm.zero_ms();
+        float ms = 0;
+        for (size_t i = 0; i < j.tm.brackets(); ++i) {
+            if (j.tm.index_ms(i, &ms)) idx_ms += ms;
+            for (int s = 0; s < n_search; ++s)
+                if (j.tm.set_ms(i, s, &ms)) {
+                    srch_ms += ms;
+                    if (stats) stats[s].search_ms += ms;
+                }
+        }
+    }
+    if (info) {
+        info->n_chunks = j.n_chunks();
+        info->kmers_indexed = j.plan.kmers;
+        info->reads_scanned = scans;
+        info->reads_indexed = j.plan.indexed_reads;
+        info->index_launches = j.n_index_launches;
+        info->search_launches = j.n_search_launches;
+        info->probes = probes;
+        info->zero_ms = zero_ms;
+        info->index_ms = idx_ms;
+        info->index_kernel_ms = idx_ms - zero_ms;
+        info->search_ms = srch_ms;
+    }
+}
+
 // counters and tags to the host, the device's counts against the plan's, stats and info
 int collect(JobRun &j, int rc, uint8_t *const *tags_out, commet_pair_stats *stats, commet_job_info *info)
 {
@@ -435,12 +481,7 @@ int collect(JobRun &j, int rc, uint8_t *const *tags_out, commet_pair_stats *stat
         if (tags_out && tags_out[s] &&
             hipMemcpyAsync(tags_out[s], j.search_rs[s]->d_tags, bitmap_bytes_host(j.search_rs[s]->n_reads), hipMemcpyDeviceToHost, c->stream) != hipSuccess)
             rc = fail("tag copy failed");
-    if (hipStreamSynchronize(c->stream) != hipSuccess && !rc) rc = fail("stream synchronize failed: %s", hipGetErrorString(hipGetLastError()));
-    c->kclock.collect();
-    j.clk.lap(j.ph_wait);
-    if (!rc && j.d_ids && (c->h_counters[N_COUNTERS - 1] & 0xFFFFFFFFull) != (j.ids_expected & 0xFFFFFFFFull))
-        rc = fail("internal error: the selection list holds %llu reads, the plan indexes %llu", (unsigned long long) (c->h_counters[N_COUNTERS - 1] & 0xFFFFFFFFull),
-                  (unsigned long long) j.ids_expected);
+    rc = drain_job(j, rc);
     if (rc) return rc;
     uint64_t scans = 0;
     for (int s = 0; s < n_search; ++s) {
@@ -462,32 +503,7 @@ int collect(JobRun &j, int rc, uint8_t *const *tags_out, commet_pair_stats *stat
             stats[s].search_ms = 0;
         }
     }
-    double idx_ms = 0, srch_ms = 0, zero_ms = 0;
-    if (j.tm.timed && !rc) {
-        zero_ms = j.tm.zero_ms();
-        float ms = 0;
-        for (size_t i = 0; i < j.tm.brackets(); ++i) {
-            if (j.tm.index_ms(i, &ms)) idx_ms += ms;
-            for (int s = 0; s < n_search; ++s)
-                if (j.tm.set_ms(i, s, &ms)) {
-                    srch_ms += ms;
-                    if (stats) stats[s].search_ms += ms;
-                }
-        }
-    }
-    if (info) {
-        info->n_chunks = n_chunks;
-        info->kmers_indexed = j.plan.kmers;
-        info->reads_scanned = scans;
-        info->reads_indexed = j.plan.indexed_reads;
-        info->index_launches = j.n_index_launches;
-        info->search_launches = j.n_search_launches;
-        info->probes = h_cnt[j.n_cnt - 1];
-        info->zero_ms = zero_ms;
-        info->index_ms = idx_ms;
-        info->index_kernel_ms = idx_ms - zero_ms;
-        info->search_ms = srch_ms;
-    }
+    fill_job_info(j, rc, stats, info, scans, h_cnt[j.n_cnt - 1]);
     return rc;
 }
 

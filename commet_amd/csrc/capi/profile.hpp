@@ -1,0 +1,136 @@
+// capi/profile.hpp — commet_index_and_profile: per-read hit counts of a job's chunk loop, the tags of every t in 1..max_hits from one call
+// (a part of the one translation unit capi.hip: included there, in order, after job.hpp, whose plan, group build, timer and account it uses)
+//
+// Why one number per read is exact ("Hit profile"): the index does not depend on t (index_reads.h:41-63, and max_kmer
+// depends on k alone), so the chunk plan and every chunk filter are the same for every t; within a filter t only decides when
+// search_reads stops (search_reads.h:45-83), so a read is found at t iff max(F, R) >= t with F / R the greedy non-overlapping full
+// hits of the whole forward / reverse-complement strand; across chunks the tags are ORed, and skipping tagged reads never changes
+// which other reads are visited (read_iter.hpp, SetIterator::next).  Hence hits(r) = min(T, max over chunks of max(F, R)).
+//
+// One chunk filter per pass: the existing index dispatch builds chunk ci into slot 0, then every search set takes one hits pass
+// (hit_profile.hpp).  A job of thousands of chunks (k <= 24 on large sets) is correct and slow.
+// Out of scope here: hits passes that share a gather across chunk filters (groups, bit-sliced tables, the tiled probe), and a profile
+// form of commet_index_many_and_search.
+#pragma once
+
+namespace {
+
+// which hits kernel a set takes: option "long_search" as in long_ok (search_dispatch.hpp) — 0: sets whose longest read has
+// LONG_MIN_MAX_LEN bases (such a read has more than MASK_MAX_WIN windows whatever t), 1 never, 2 whenever the set has a read.
+// The context's t plays no part
+bool hits_wave_ok(const commet_ctx *c, const commet_readset *rs)
+{
+    if (c->long_search == 1 || c->k < 2 || rs->n_reads == 0) return false;
+    if (c->long_search == 2) return true;
+    return rs->max_len >= LONG_MIN_MAX_LEN;
+}
+
+// persistent grid of hits_wave_kernel<W>: the workgroups the device holds at once, four reads each
+template <typename W>
+uint64_t hits_wave_blocks(const commet_ctx *c, uint64_t items)
+{
+    static std::atomic<int> resident{0};
+    int wgs = resident.load(std::memory_order_relaxed);
+    if (!wgs) {
+        int per_cu = 0, cus = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, hits_wave_kernel<W>, LONG_WG, 0) != hipSuccess ||
+            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess || per_cu < 1 || cus < 1) {
+            (void) hipGetLastError();
+            per_cu = 4, cus = 256;
+        }
+        wgs = per_cu * cus;
+        resident.store(wgs, std::memory_order_relaxed);
+    }
+    return std::min<uint64_t>((items + 3) / 4, (uint64_t) wgs);
+}
+
+// one pass of rs over the filter in slot 0; al.ids != nullptr: over the n_launch (at most) listed reads
+int launch_hits(commet_ctx *c, const commet_readset *rs, int max_hits, const uint64_t *d_sel, uint8_t *d_hits, unsigned long long *d_walked,
+                ActiveList al, uint64_t n_launch)
+{
+    if (rs->n_reads == 0) return 0;
+    if (al.ids && n_launch == 0) return 0;
+    const uint64_t items = al.ids ? n_launch : rs->n_reads;
+    if (hits_wave_ok(c, rs)) {
+        KScope ks(c, "hits_wave_kernel", c->stream);
+        with_key(c->k, [&](auto key) {
+            using W = decltype(key);
+            COMMET_LAUNCH(hits_wave_kernel<W>, dim3((unsigned) hits_wave_blocks<W>(c, items)), dim3(LONG_WG), 0, c->stream, rs->view(), c->view(), c->k,
+                          max_hits, d_sel, d_hits, d_walked, al);
+        });
+    } else {
+        if (launch_size_ok(items)) return 1;
+        KScope ks(c, "hits_kernel", c->stream);
+        with_key(c->k, [&](auto key) {
+            COMMET_LAUNCH(hits_kernel<decltype(key)>, dim3((unsigned) ((items + 255) / 256)), dim3(256), 0, c->stream, rs->view(), c->view(), c->k, max_hits,
+                          d_sel, d_hits, d_walked, al);
+        });
+    }
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+// search set s against the chunk filter in slot 0.  A pass over few of the set's reads walks their list (sparse_pass; no tags: a
+// saturated read is skipped by the kernel itself)
+int hits_pass(JobRun &j, int s, int max_hits, uint8_t *d_hits, unsigned long long *d_walked)
+{
+    commet_ctx *c = j.c;
+    const commet_readset *rs = j.search_rs[s];
+    const uint64_t *sel_s = j.sel_of(s);
+    ActiveList al{nullptr, nullptr};
+    if (rs->n_reads && sparse_pass(c, rs, sel_s, j.visited[s]) && build_active_list(c, rs, sel_s, nullptr, j.visited[s], &al))
+        al = ActiveList{nullptr, nullptr};         // (no room: the bitmap form)
+    c->cur_slot = 0;
+    if (launch_hits(c, rs, max_hits, sel_s, d_hits, d_walked, al, j.visited[s])) return 1;
+    if (rs->n_reads) ++j.n_search_launches;
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int commet_index_and_profile(commet_ctx *c, const commet_readset *index_rs, const uint8_t *index_select, int n_search,
+                             const commet_readset *const *search_rs, const uint8_t *const *search_select, int max_hits, uint8_t *const *hits_out,
+                             commet_job_info *info)
+{
+    if (n_search < 0) return fail("n_search must not be negative (got %d)", n_search);
+    if (max_hits < 1 || max_hits > 255) return fail("max_hits must be in 1..255 (got %d)", max_hits);
+    JobRun j(c, index_rs, n_search, search_rs);
+    if (validate_job(c, index_rs, n_search, search_rs)) return 1;
+    HIP_OK(hipSetDevice(c->device));
+    SetUse in_job(c, index_rs);                    // offload / export cannot take a set mid-call
+    for (int s = 0; s < n_search; ++s) in_job.add(search_rs[s]);
+    if (in_job.enter()) return 1;
+    if (plan_job(j, index_select, search_select)) return 1;
+    // a byte per read and search set (each set's bytes start on a 256-byte line), and the count of walked reads
+    std::vector<uint64_t> at((size_t) n_search + 1, 0);
+    for (int s = 0; s < n_search; ++s) at[(size_t) s + 1] = at[(size_t) s] + ((search_rs[s]->n_reads + 255) & ~255ull);
+    const uint64_t n_bytes = std::max<uint64_t>(at[(size_t) n_search], 256);
+    if (grow_kept(c, c->d_hits, c->hits_cap, n_bytes, n_bytes) || grow_kept(c, c->d_jobcnt, c->jobcnt_cap, 1, 64)) return 1;
+    unsigned long long *d_walked = c->d_jobcnt;
+    HIP_OK(hipMemsetAsync(c->d_hits, 0, n_bytes, c->stream));
+    HIP_OK(hipMemsetAsync(d_walked, 0, sizeof(unsigned long long), c->stream));
+    const uint64_t n_chunks = j.n_chunks();
+    j.tm.timed = info != nullptr && n_chunks * (uint64_t) (n_search + 4) <= 16384;
+    int rc = 0;
+    for (uint64_t ci = 0; ci < n_chunks && !rc; ++ci) {
+        rc = j.tm.begin_index() || build_group(j, ci, 1, 2) || j.tm.end_index();
+        for (int s = 0; s < n_search && !rc; ++s) rc = hits_pass(j, s, max_hits, c->d_hits + at[(size_t) s], d_walked) || j.tm.end_set(s);
+    }
+    c->cur_slot = 0;
+    j.clk.lap(j.ph_launch);
+    if (!rc && hipMemcpyAsync(&c->h_counters[0], d_walked, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream) != hipSuccess)
+        rc = fail("counter copy failed");
+    for (int s = 0; s < n_search && !rc; ++s)
+        if (hits_out && hits_out[s] && search_rs[s]->n_reads &&
+            hipMemcpyAsync(hits_out[s], c->d_hits + at[(size_t) s], search_rs[s]->n_reads, hipMemcpyDeviceToHost, c->stream) != hipSuccess)
+            rc = fail("hit count copy failed");
+    rc = drain_job(j, rc);
+    if (rc) return rc;
+    fill_job_info(j, rc, nullptr, info, c->h_counters[0], 0);
+    if (info) info->total_ms = j.clk.total_ms();
+    return 0;
+}
+
+}  // extern "C"

@@ -294,6 +294,23 @@ int commet_index_many_and_search(commet_ctx *ctx, int n_jobs, const commet_reads
                                  const uint8_t *search_select, uint8_t *const *tags_out, commet_pair_stats *stats,
                                  commet_job_info *info);
 
+/* Hit profile: the chunk loop above with a search that does not stop at t.  No counterpart in the reference, whose tools answer one t
+ * per run; one call here answers every t in 1..max_hits, and the filters, which do not depend on t, are built once.
+ * hits_out[i]: n_i bytes, one per read of search set i (set-wide read numbers):
+ * 0 for a read the search pass does not visit (search_select bit 0, plan_search), else
+ * min(max_hits, max over the index set's chunks of max(F, R)), F / R = the greedy non-overlapping full hits of the
+ * forward / reverse-complement scan of search_reads.h:45-83 run to the end of the read.  For every t in 1..max_hits,
+ * (hits_out[i][r] >= t) is bit for bit the tag commet_index_and_search gives on a context of this k and that t.
+ * The context's own t is not used.  max_hits in 1..255.
+ * One chunk filter per pass (hits_kernel, a lane per read; hits_wave_kernel, a wave per read, by option "long_search"); index_mode,
+ * max_kmer and index_lanes are honoured.  info (may be NULL) as in a job; reads_scanned = the reads the passes walked (a read whose
+ * count has reached max_hits is not walked again), probes = 0.
+ * Not done here: passes that share a gather across chunk filters (groups, bit-sliced tables, tiled probe) — a job of thousands of
+ * chunks is correct and slow —, and a profile form of commet_index_many_and_search. */
+int commet_index_and_profile(commet_ctx *ctx, const commet_readset *index_rs, const uint8_t *index_select,
+                             int n_search, const commet_readset *const *search_rs, const uint8_t *const *search_select,
+                             int max_hits, uint8_t *const *hits_out, commet_job_info *info);
+
 /* ---- test / measurement hooks --------------------------------------------- */
 /* Tunables / diagnostics, by name.  Unknown names are an error.  None of them changes a result bit, except the test
  * hook max_kmer.

@@ -1,0 +1,176 @@
+"""hits_bench.py — does one profile job beat a job per threshold?  On the configs[1] shape (2 x 10 M x 100 bp, k = 32, sets generated as
+bench.py does):
+  (a) one Context.index_and_profile(max_hits = T)                       -> the tags of t = 1..T
+  (b) the T Context.index_and_search jobs at t = 1..T, one context each -> the same tags, the way there was before
+The T tag vectors of (a) and (b) are byte-compared.  Every figure comes from a fresh child process under its own time limit, (a) and
+(b) alternating over `--rounds`; a child warms up once, times `--reps` calls with a host clock around the whole call (it ends in a
+stream synchronise and the copy back) and then runs once more with option kernel_timing for the per-kernel split.
+  --jobs-lib PATH   the library (b) runs on (a build of the commit before the profile existed); default: the one in the tree
+  --many-chunks     also one profile job of a few hundred chunks (configs[4]'s k = 21, 150 bp, scaled down): one filter per pass
+  python tools/hits_bench.py [--reads 10000000] [--read-len 100] [-k 32] [--max-t 8] [--rounds 2] [--reps 3] [--out FILE]"""
+import argparse
+import json
+import os
+import shutil
+import subprocess
+import sys
+import tempfile
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def _sets(work, tag):
+    return [(np.load(os.path.join(work, f"{tag}{i}_b.npy")), np.load(os.path.join(work, f"{tag}{i}_o.npy"))) for i in (0, 1)]
+
+
+def _kernels(ctx):
+    return {name: [cnt, round(ms, 3)] for name, (cnt, ms) in sorted(ctx.kernel_times().items(), key=lambda kv: -kv[1][1])}
+
+
+def child_profile(a):
+    import commet_amd
+    (b0, o0), (b1, o1) = _sets(a.work, a.tag)
+    out = {}
+    with commet_amd.Context(k=a.k, t=2) as ctx:
+        if a.max_kmer:
+            ctx.set_option("max_kmer", a.max_kmer)
+        irs = commet_amd.ReadSet.from_files(ctx, [(b0, o0)])
+        qrs = commet_amd.ReadSet.from_files(ctx, [(b1, o1)])
+        ctx.index_and_profile(irs, [qrs], max_hits=a.max_t)                      # warm-up
+        calls = []
+        for _ in range(a.reps):
+            hits, info = ctx.index_and_profile(irs, [qrs], max_hits=a.max_t)
+            calls.append(info)
+        ctx.set_option("kernel_timing", 1)
+        ctx.index_and_profile(irs, [qrs], max_hits=a.max_t)
+        out["kernels_ms"] = _kernels(ctx)
+        ctx.set_option("kernel_timing", 0)
+        out["total_ms"] = [round(i["total_ms"], 3) for i in calls]
+        out["index_ms"] = [round(i["index_ms"], 3) for i in calls]
+        out["search_ms"] = [round(i["search_ms"], 3) for i in calls]
+        out["chunks"], out["reads_walked"] = int(calls[-1]["n_chunks"]), int(calls[-1]["reads_scanned"])
+        out["windows"] = int(qrs.kmer_counts().astype(np.uint64).sum())          # complete windows of the search set: one plane-A request each at most
+        out["histogram"] = np.bincount(hits[0], minlength=a.max_t + 1).tolist()
+        if a.ceiling:
+            acc = 1 << 30
+            out["gather_ceiling_per_s"] = acc / (ctx.membench(0, (4 << a.k) // 8, acc) * 1e-3)
+        np.save(os.path.join(a.work, f"{a.tag}_profile_tags.npy"), np.stack([commet_amd.tags_at(hits[0], t) for t in range(1, a.max_t + 1)]))
+    print("RESULT " + json.dumps(out), flush=True)
+
+
+def child_jobs(a):
+    from commet_amd import lib
+    if a.jobs_lib:
+        lib.LIB_PATH = a.jobs_lib
+        import ctypes
+        if not hasattr(ctypes.CDLL(a.jobs_lib), "commet_index_and_profile"):
+            lib.SIGNATURES.pop("commet_index_and_profile")                      # (a library from before the profile)
+    import commet_amd
+    (b0, o0), (b1, o1) = _sets(a.work, a.tag)
+    out = {"lib": lib.LIB_PATH, "per_t": {}}
+    tags_all = []
+    for t in a.ts:
+        with commet_amd.Context(k=a.k, t=t) as ctx:
+            if a.max_kmer:
+                ctx.set_option("max_kmer", a.max_kmer)
+            irs = commet_amd.ReadSet.from_files(ctx, [(b0, o0)])
+            qrs = commet_amd.ReadSet.from_files(ctx, [(b1, o1)])
+            ctx.index_and_search(irs, [qrs])                                     # warm-up (query lists, workspaces)
+            calls = []
+            for _ in range(a.reps):
+                tags, stats, info = ctx.index_and_search(irs, [qrs])
+                calls.append(info)
+            ctx.set_option("kernel_timing", 1)
+            ctx.index_and_search(irs, [qrs])
+            out["per_t"][str(t)] = {"total_ms": [round(i["total_ms"], 3) for i in calls], "index_ms": [round(i["index_ms"], 3) for i in calls],
+                                    "search_ms": [round(i["search_ms"], 3) for i in calls], "shared": stats[0]["shared"], "kernels_ms": _kernels(ctx)}
+            tags_all.append(tags[0].copy())
+    np.save(os.path.join(a.work, f"{a.tag}_job_tags.npy"), np.stack(tags_all))
+    print("RESULT " + json.dumps(out), flush=True)
+
+
+def run_child(a, mode, tag, limit, extra=()):
+    cmd = ["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--child", mode, "--work", a.work, "--tag", tag, "-k", str(a.k if tag == "c1" else 21),
+           "--max-t", str(a.max_t), "--reps", str(a.reps)] + list(extra)
+    p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
+    if p.returncode != 0:
+        raise SystemExit(f"child {mode} ({tag}) ended with status {p.returncode}; nothing more is started\n{p.stdout[-1500:]}\n{p.stderr[-1500:]}")
+    return json.loads([ln for ln in p.stdout.split("\n") if ln.startswith("RESULT ")][-1][7:])
+
+
+def med(x):
+    return float(np.median(x))
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--reads", type=int, default=10_000_000)
+    ap.add_argument("--read-len", type=int, default=100)
+    ap.add_argument("-k", type=int, default=32)
+    ap.add_argument("--max-t", type=int, default=8)
+    ap.add_argument("--rounds", type=int, default=2)
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--jobs-lib", default=None)
+    ap.add_argument("--many-chunks", action="store_true")
+    ap.add_argument("--many-reads", type=int, default=600_000)
+    ap.add_argument("--limit", type=int, default=240, help="seconds a child may take")
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--child", default=None, help=argparse.SUPPRESS)
+    ap.add_argument("--work", default=None, help=argparse.SUPPRESS)
+    ap.add_argument("--tag", default="c1", help=argparse.SUPPRESS)
+    ap.add_argument("--ts", type=int, nargs="+", default=None, help=argparse.SUPPRESS)
+    ap.add_argument("--max-kmer", type=int, default=0, help=argparse.SUPPRESS)
+    ap.add_argument("--ceiling", action="store_true", help=argparse.SUPPRESS)
+    a = ap.parse_args()
+    if a.ts is None:
+        a.ts = list(range(1, a.max_t + 1))
+    if a.child:
+        return {"profile": child_profile, "jobs": child_jobs}[a.child](a)
+    if a.jobs_lib:
+        a.jobs_lib = os.path.abspath(a.jobs_lib)
+    from commet_amd import synth
+    a.work = tempfile.mkdtemp(prefix="hits_bench_")
+    try:
+        for i in (0, 1):
+            b, o = synth.synth_set(i, a.reads, a.read_len, base_set=0)
+            np.save(os.path.join(a.work, f"c1{i}_b.npy"), b), np.save(os.path.join(a.work, f"c1{i}_o.npy"), o)
+        res = {"workload": f"2 x {a.reads} x {a.read_len} bp, k={a.k}, t=1..{a.max_t}", "profile": [], "jobs": []}
+        lib_args = ["--jobs-lib", a.jobs_lib] if a.jobs_lib else []
+        for r in range(a.rounds):                                                # (a) and (b) alternate
+            res["profile"].append(run_child(a, "profile", "c1", a.limit, ["--ceiling"] if r == 0 else []))
+            res["jobs"].append(run_child(a, "jobs", "c1", a.limit, lib_args))
+            pt, jt = np.load(os.path.join(a.work, "c1_profile_tags.npy")), np.load(os.path.join(a.work, "c1_job_tags.npy"))
+            res.setdefault("tags_equal", []).append(bool(pt.shape == jt.shape and (pt == jt).all()))
+        prof = med([med(p["total_ms"]) for p in res["profile"]])
+        jobs = sum(med([med(j["per_t"][str(t)]["total_ms"]) for j in res["jobs"]]) for t in range(1, a.max_t + 1))
+        p0 = res["profile"][0]
+        hk = p0["kernels_ms"].get("hits_kernel", [0, 0.0])
+        res["summary"] = {"profile_ms": round(prof, 3), "jobs_sum_ms": round(jobs, 3), "profile_over_jobs": round(prof / jobs, 4) if jobs else None,
+                          "tags_equal": all(res["tags_equal"]), "hits_kernel_ms": hk[1], "hits_kernel_launches": hk[0],
+                          "plane_a_requests_per_s_at_most": (p0["windows"] * hk[0] / (hk[1] * 1e-3)) if hk[1] else None,
+                          "gather_ceiling_per_s": p0.get("gather_ceiling_per_s")}
+        if a.many_chunks:
+            n, L = a.many_reads, 150
+            for i in (0, 1):
+                b, o = synth.synth_set(i, n, L, base_set=0)
+                np.save(os.path.join(a.work, f"c4{i}_b.npy"), b), np.save(os.path.join(a.work, f"c4{i}_o.npy"), o)
+            res["many_chunks"] = {"workload": f"2 x {n} x {L} bp, k=21", "profile": run_child(a, "profile", "c4", a.limit),
+                                  "job_t5": run_child(a, "jobs", "c4", a.limit, lib_args + ["--ts", "5"])}
+    finally:
+        shutil.rmtree(a.work, ignore_errors=True)
+    text = json.dumps(res)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        open(a.out, "w").write(text + "\n")
+    print(json.dumps(res["summary"]))
+    if "many_chunks" in res:
+        m = res["many_chunks"]
+        print(json.dumps({"many_chunks": m["workload"], "chunks": m["profile"]["chunks"], "profile_ms": m["profile"]["total_ms"],
+                          "job_t5_ms": m["job_t5"]["per_t"]["5"]["total_ms"]}))
+
+
+if __name__ == "__main__":
+    main()
