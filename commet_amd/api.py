@@ -207,7 +207,9 @@ class Context:
     def index_and_profile(self, index_rs, search_sets, index_select=None, search_selects=None, max_hits=8):
         """commet_index_and_profile: the chunk loop with a search that does not stop at t.  Returns (hits, info): hits[i] = np.uint8
         per read of search set i, min(max_hits, the read's greedy non-overlapping full hits on its better strand, in its best chunk);
-        tags_at(hits[i], t) is the BooleanVector index_and_search gives on a context of this k and that t, for every t in 1..max_hits."""
+        tags_at(hits[i], t) is the BooleanVector index_and_search gives on a context of this k and that t, for every t in 1..max_hits.
+        The chunk filters are searched in groups of up to set_option("chunk_group", 1..8) per pass over a search set (default 8; 1: one
+        filter per pass); the bytes do not depend on it, info["search_launches"] counts the passes."""
         ns = len(search_sets)
         isel = _as_bits(index_select, index_rs.num_reads, "index_select")
         ssel = [None] * ns

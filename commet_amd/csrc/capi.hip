@@ -11,6 +11,7 @@
 #include "tile_search.hpp"
 #include "long_search.hpp"
 #include "hit_profile.hpp"
+#include "hit_profile_group.hpp"
 #include "read_filter.hpp"
 #include "read_iter.hpp"
 #include "host/fasta_source.hpp"

@@ -7,10 +7,13 @@
 // hits of the whole forward / reverse-complement strand; across chunks the tags are ORed, and skipping tagged reads never changes
 // which other reads are visited (read_iter.hpp, SetIterator::next).  Hence hits(r) = min(T, max over chunks of max(F, R)).
 //
-// One chunk filter per pass: the existing index dispatch builds chunk ci into slot 0, then every search set takes one hits pass
-// (hit_profile.hpp).  A job of thousands of chunks (k <= 24 on large sets) is correct and slow.
-// Out of scope here: hits passes that share a gather across chunk filters (groups, bit-sliced tables, the tiled probe), and a profile
-// form of commet_index_many_and_search.
+// Up to eight chunk filters per pass: the chunks are taken in groups as run_slots (job.hpp) forms them — g = min(cap, chunks left)
+// filters built into slots 0 .. g - 1, their A planes interleaved with stride gs = 2 / 4 / 8 — and every search set takes ONE hits
+// pass per group (hit_profile_group.hpp: one walk of the read, one plane-A request per window for all g filters and both strands).
+// cap = option "chunk_group" (default 8); 1 when k < 2 or the job has one chunk, and down the ladder 8 -> 4 -> 1 when the slots do
+// not fit.  A group of one chunk takes the one-filter kernels (hit_profile.hpp); chunk_group = 1 is the one-filter-per-pass form,
+// launch for launch.  No group8_ok condition: these kernels keep no masks.
+// Not done here: profiles through the bit-sliced tables or the tiled probe, and a profile form of commet_index_many_and_search.
 #pragma once
 
 namespace {
@@ -44,6 +47,57 @@ uint64_t hits_wave_blocks(const commet_ctx *c, uint64_t items)
     return std::min<uint64_t>((items + 3) / 4, (uint64_t) wgs);
 }
 
+// persistent grid of hits_group_wave_kernel<W, NF>, as above
+template <typename W, int NF>
+uint64_t hits_group_wave_blocks(const commet_ctx *c, uint64_t items)
+{
+    static std::atomic<int> resident{0};
+    int wgs = resident.load(std::memory_order_relaxed);
+    if (!wgs) {
+        int per_cu = 0, cus = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, hits_group_wave_kernel<W, NF>, LONG_WG, 0) != hipSuccess ||
+            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess || per_cu < 1 || cus < 1) {
+            (void) hipGetLastError();
+            per_cu = 4, cus = 256;
+        }
+        wgs = per_cu * cus;
+        resident.store(wgs, std::memory_order_relaxed);
+    }
+    return std::min<uint64_t>((items + 3) / 4, (uint64_t) wgs);
+}
+
+// one pass of rs over the g filters in slots 0 .. g - 1 (g >= 2, their A planes interleaved with stride gs); al as in launch_hits below
+int launch_hits_group(commet_ctx *c, const commet_readset *rs, int g, int gs, int max_hits, const uint64_t *d_sel, uint8_t *d_hits,
+                      unsigned long long *d_walked, ActiveList al, uint64_t n_launch)
+{
+    if (rs->n_reads == 0) return 0;
+    if (al.ids && n_launch == 0) return 0;
+    const uint64_t items = al.ids ? n_launch : rs->n_reads;
+    const FilterGroupView fg = filter_group(c, g, 0, true);
+    if (hits_wave_ok(c, rs)) {
+        KScope ks(c, "hits_group_wave_kernel", c->stream);
+        with_key(c->k, [&](auto key) {
+            using W = decltype(key);
+            with_value<2, 4, 8>(gs, [&](auto NF) {
+                COMMET_LAUNCH((hits_group_wave_kernel<W, NF>), dim3((unsigned) hits_group_wave_blocks<W, NF>(c, items)), dim3(LONG_WG), 0, c->stream,
+                              rs->view(), fg, c->k, max_hits, d_sel, d_hits, d_walked, al);
+            });
+        });
+    } else {
+        if (launch_size_ok(items)) return 1;
+        KScope ks(c, "hits_group_kernel", c->stream);
+        with_key(c->k, [&](auto key) {
+            using W = decltype(key);
+            with_value<2, 4, 8>(gs, [&](auto NF) {
+                COMMET_LAUNCH((hits_group_kernel<W, NF>), dim3((unsigned) ((items + 255) / 256)), dim3(256), 0, c->stream, rs->view(), fg, c->k, max_hits,
+                              d_sel, d_hits, d_walked, al);
+            });
+        });
+    }
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
 // one pass of rs over the filter in slot 0; al.ids != nullptr: over the n_launch (at most) listed reads
 int launch_hits(commet_ctx *c, const commet_readset *rs, int max_hits, const uint64_t *d_sel, uint8_t *d_hits, unsigned long long *d_walked,
                 ActiveList al, uint64_t n_launch)
@@ -70,9 +124,9 @@ int launch_hits(commet_ctx *c, const commet_readset *rs, int max_hits, const uin
     return 0;
 }
 
-// search set s against the chunk filter in slot 0.  A pass over few of the set's reads walks their list (sparse_pass; no tags: a
-// saturated read is skipped by the kernel itself)
-int hits_pass(JobRun &j, int s, int max_hits, uint8_t *d_hits, unsigned long long *d_walked)
+// search set s against the g chunk filters in slots 0 .. g - 1 (g == 1: the filter in slot 0, the one-filter kernels).  A pass over
+// few of the set's reads walks their list (sparse_pass; no tags: a saturated read is skipped by the kernel itself)
+int hits_pass(JobRun &j, int s, int g, int gs, int max_hits, uint8_t *d_hits, unsigned long long *d_walked)
 {
     commet_ctx *c = j.c;
     const commet_readset *rs = j.search_rs[s];
@@ -81,7 +135,9 @@ int hits_pass(JobRun &j, int s, int max_hits, uint8_t *d_hits, unsigned long lon
     if (rs->n_reads && sparse_pass(c, rs, sel_s, j.visited[s]) && build_active_list(c, rs, sel_s, nullptr, j.visited[s], &al))
         al = ActiveList{nullptr, nullptr};         // (no room: the bitmap form)
     c->cur_slot = 0;
-    if (launch_hits(c, rs, max_hits, sel_s, d_hits, d_walked, al, j.visited[s])) return 1;
+    if (g > 1 ? launch_hits_group(c, rs, g, gs, max_hits, sel_s, d_hits, d_walked, al, j.visited[s])
+              : launch_hits(c, rs, max_hits, sel_s, d_hits, d_walked, al, j.visited[s]))
+        return 1;
     if (rs->n_reads) ++j.n_search_launches;
     return 0;
 }
@@ -114,9 +170,23 @@ int commet_index_and_profile(commet_ctx *c, const commet_readset *index_rs, cons
     const uint64_t n_chunks = j.n_chunks();
     j.tm.timed = info != nullptr && n_chunks * (uint64_t) (n_search + 4) <= 16384;
     int rc = 0;
-    for (uint64_t ci = 0; ci < n_chunks && !rc; ++ci) {
-        rc = j.tm.begin_index() || build_group(j, ci, 1, 2) || j.tm.end_index();
-        for (int s = 0; s < n_search && !rc; ++s) rc = hits_pass(j, s, max_hits, c->d_hits + at[(size_t) s], d_walked) || j.tm.end_set(s);
+    // the chunks in groups, as run_slots forms them (no group8_ok condition: the hits kernels keep no masks)
+    int group_cap = (c->k >= 2 && n_chunks >= 2) ? std::max(1, std::min(8, c->chunk_group)) : 1;
+    for (uint64_t ci = 0; ci < n_chunks && !rc;) {
+        int g = (int) std::min<uint64_t>((uint64_t) group_cap, n_chunks - ci);
+        const int gs = g <= 2 ? 2 : g <= 4 ? 4 : 8;
+        if (g > 1 && ensure_slots(c, g, gs)) {   // not enough memory for the group
+            (void) hipGetLastError();
+            if (g > 4) {                          // eight slots do not fit: groups of four
+                group_cap = 4;
+                continue;
+            }
+            g = 1;                                // one chunk at a time
+            group_cap = 1;
+        }
+        rc = j.tm.begin_index() || build_group(j, ci, g, gs) || j.tm.end_index();
+        for (int s = 0; s < n_search && !rc; ++s) rc = hits_pass(j, s, g, gs, max_hits, c->d_hits + at[(size_t) s], d_walked) || j.tm.end_set(s);
+        ci += (uint64_t) g;
     }
     c->cur_slot = 0;
     j.clk.lap(j.ph_launch);

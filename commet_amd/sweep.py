@@ -1,6 +1,6 @@
 """Threshold sweep: the `.bv` vectors of `index_and_search -t t` for every t in 1..T from ONE profile job.
 
-    python -m commet_amd.sweep -i index.txt -s search.txt -k K --max-t T -o OUT
+    python -m commet_amd.sweep -i index.txt -s search.txt -k K --max-t T -o OUT [--chunk-group N]
 
 -i / -s take the reference's set-config grammar (`name:file[,bv];file[,bv]...`, one set per line; the index file holds exactly one
 set).  The sets are parsed and packed by the library's own ingest (ReadSet.from_fasta), one Context.index_and_profile(max_hits=T) gives a hit count per read, and
@@ -8,7 +8,9 @@ set).  The sets are parsed and packed by the library's own ingest (ReadSet.from_
     OUT/t<t>/<file>_in_<index>.bv   for t = 1..T: byte for byte what `index_and_search -t t` writes for the same configs
     OUT/sweep.csv                   t;set;file;reads;shared  (shared = reads of the file with at least t hits)
 
-The filters, which do not depend on t, are built once instead of T times.  No .log files are written: the reference's `searched`
+The filters, which do not depend on t, are built once instead of T times, and every search set is walked once per GROUP of up to
+--chunk-group chunk filters (1..8, the library's option "chunk_group"; default: the library's, 8); the closing line reports the
+passes that took.  No .log files are written: the reference's `searched`
 figure is the read count of the LAST chunk pass, which depends on t through the tags of the earlier chunks, and one pass over the
 chunks does not reproduce it."""
 import argparse
@@ -70,6 +72,7 @@ def parser():
     p.add_argument("-k", dest="k", type=int, required=True, help="k-mer size")
     p.add_argument("--max-t", dest="max_t", type=int, required=True, help="largest threshold T (1..255); OUT/t1 .. OUT/tT are written")
     p.add_argument("-o", dest="out", required=True, help="output directory")
+    p.add_argument("--chunk-group", dest="chunk_group", type=int, default=None, help="chunk filters per search pass (1..8; default: the library's)")
     p.add_argument("--device", type=int, default=0)
     return p
 
@@ -81,6 +84,8 @@ def main(argv=None):
         ap.error("--max-t must be in 1..255")
     if a.k < 1:
         ap.error("-k must be positive")
+    if a.chunk_group is not None and not 1 <= a.chunk_group <= 8:
+        ap.error("--chunk-group must be in 1..8")
     for path in (a.index, a.search):
         if not os.path.isfile(path):
             ap.error(f"Cannot read file {path}")
@@ -92,6 +97,8 @@ def main(argv=None):
     with api.Context(k=a.k, t=1, device=a.device) as ctx:
         irs, _, isel = _load(api, ctx, index_entries)
         loaded = [(tag, entries) + _load(api, ctx, entries) for tag, entries in search_sets]
+        if a.chunk_group is not None:
+            ctx.set_option("chunk_group", a.chunk_group)
         hits, info = ctx.index_and_profile(irs, [l[2] for l in loaded], isel, [l[4] for l in loaded], max_hits=a.max_t)
         rows = []
         for t in range(1, a.max_t + 1):
@@ -108,7 +115,8 @@ def main(argv=None):
             fh.write("t;set;file;reads;shared\n")
             for r in rows:
                 fh.write(";".join(str(x) for x in r) + "\n")
-    print(f"sweep: k={a.k} t=1..{a.max_t}, {int(info['n_chunks'])} chunk filter(s) built once, {len(rows)} vectors under {a.out}")
+    print(f"sweep: k={a.k} t=1..{a.max_t}, {int(info['n_chunks'])} chunk filter(s) built once, {int(info['search_launches'])} search pass(es), "
+          f"{len(rows)} vectors under {a.out}")
     return 0
 
 

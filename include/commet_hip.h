@@ -302,11 +302,14 @@ int commet_index_many_and_search(commet_ctx *ctx, int n_jobs, const commet_reads
  * forward / reverse-complement scan of search_reads.h:45-83 run to the end of the read.  For every t in 1..max_hits,
  * (hits_out[i][r] >= t) is bit for bit the tag commet_index_and_search gives on a context of this k and that t.
  * The context's own t is not used.  max_hits in 1..255.
- * One chunk filter per pass (hits_kernel, a lane per read; hits_wave_kernel, a wave per read, by option "long_search"); index_mode,
- * max_kmer and index_lanes are honoured.  info (may be NULL) as in a job; reads_scanned = the reads the passes walked (a read whose
- * count has reached max_hits is not walked again), probes = 0.
- * Not done here: passes that share a gather across chunk filters (groups, bit-sliced tables, tiled probe) — a job of thousands of
- * chunks is correct and slow —, and a profile form of commet_index_many_and_search. */
+ * Up to eight chunk filters per pass over a search set, by option "chunk_group" (groups formed as in a job; 1 when k < 2): one walk
+ * of the read and one plane-A request per window serve the whole group and both strands (hits_group_kernel, a lane per read;
+ * hits_group_wave_kernel, a wave per read, by option "long_search").  A group of one chunk, and every chunk at chunk_group = 1,
+ * takes the one-filter kernels (hits_kernel, hits_wave_kernel).  The bytes do not depend on the grouping.  index_mode, max_kmer and
+ * index_lanes are honoured.  info (may be NULL) as in a job; search_launches = the passes (groups x non-empty search sets),
+ * reads_scanned = the reads the passes walked (once per group pass; a read whose count has reached max_hits is not walked again),
+ * probes = 0.
+ * Not done here: profiles through the bit-sliced tables or the tiled probe, and a profile form of commet_index_many_and_search. */
 int commet_index_and_profile(commet_ctx *ctx, const commet_readset *index_rs, const uint8_t *index_select,
                              int n_search, const commet_readset *const *search_rs, const uint8_t *const *search_select,
                              int max_hits, uint8_t *const *hits_out, commet_job_info *info);
@@ -323,9 +326,10 @@ int commet_index_and_profile(commet_ctx *ctx, const commet_readset *index_rs, co
  *   part_min_kmers       auto mode: chunks with fewer k-mers take the atomic kernel
  *   index_lanes (1/2)    2 = the chunks of a group are built on two streams (default)
  *   drop_workspaces      frees the scatter workspaces (the next bucketed index build allocates them again)
- *   chunk_group (1..8)   chunk filters searched per pass over a set (1 = the reference's order; 5..8 only
+ *   chunk_group (1..8)   chunk filters searched per pass over a set (1 = the reference's order; in a job 5..8 only
  *                        for read sets with at most 255 first-hit windows per read — reads of up to 318 bases at k = 32, t = 2 — and for
- *                        sets that take long_search, else 4)
+ *                        sets that take long_search, else 4).  It governs commet_index_and_profile as well, whose kernels keep no
+ *                        masks: any set takes 5..8 there; 1 = one hits pass per chunk filter
  *   tiled_search (0/1/2) large search sets against 1 or 2 chunk filters (25 <= k <= 34): lane-a gathers served from L2 slice
  *                        by slice from the set's cached query list; 0 = sets of 2^20 reads or more whose list fits 4 GiB,
  *                        1 = never, 2 = whenever possible

@@ -6,7 +6,11 @@ The T tag vectors of (a) and (b) are byte-compared.  Every figure comes from a f
 (b) alternating over `--rounds`; a child warms up once, times `--reps` calls with a host clock around the whole call (it ends in a
 stream synchronise and the copy back) and then runs once more with option kernel_timing for the per-kernel split.
   --jobs-lib PATH   the library (b) runs on (a build of the commit before the profile existed); default: the one in the tree
-  --many-chunks     also one profile job of a few hundred chunks (configs[4]'s k = 21, 150 bp, scaled down): one filter per pass
+  --many-chunks     also one profile job of a few hundred chunks (configs[4]'s k = 21, 150 bp, scaled down)
+  --groups          ONLY the chunk_group leg: per shape (configs[1]'s; with --many-chunks the many-chunk one as well) the profile at
+                    chunk_group = 1, at the default and, with --jobs-lib, on that library (the parent commit's build), in fresh child
+                    processes alternating over `--rounds`; the hit bytes of the three are compared, medians and spreads reported,
+                    and one job at t = 5 of the many-chunk shape gives the break-even T
   python tools/hits_bench.py [--reads 10000000] [--read-len 100] [-k 32] [--max-t 8] [--rounds 2] [--reps 3] [--out FILE]"""
 import argparse
 import json
@@ -31,12 +35,17 @@ def _kernels(ctx):
 
 
 def child_profile(a):
+    if a.jobs_lib:                                                               # (the groups leg: the profile on another build)
+        from commet_amd import lib
+        lib.LIB_PATH = a.jobs_lib
     import commet_amd
     (b0, o0), (b1, o1) = _sets(a.work, a.tag)
     out = {}
     with commet_amd.Context(k=a.k, t=2) as ctx:
         if a.max_kmer:
             ctx.set_option("max_kmer", a.max_kmer)
+        if a.chunk_group:
+            ctx.set_option("chunk_group", a.chunk_group)
         irs = commet_amd.ReadSet.from_files(ctx, [(b0, o0)])
         qrs = commet_amd.ReadSet.from_files(ctx, [(b1, o1)])
         ctx.index_and_profile(irs, [qrs], max_hits=a.max_t)                      # warm-up
@@ -52,11 +61,14 @@ def child_profile(a):
         out["index_ms"] = [round(i["index_ms"], 3) for i in calls]
         out["search_ms"] = [round(i["search_ms"], 3) for i in calls]
         out["chunks"], out["reads_walked"] = int(calls[-1]["n_chunks"]), int(calls[-1]["reads_scanned"])
+        out["search_launches"] = int(calls[-1]["search_launches"])
         out["windows"] = int(qrs.kmer_counts().astype(np.uint64).sum())          # complete windows of the search set: one plane-A request each at most
         out["histogram"] = np.bincount(hits[0], minlength=a.max_t + 1).tolist()
         if a.ceiling:
             acc = 1 << 30
             out["gather_ceiling_per_s"] = acc / (ctx.membench(0, (4 << a.k) // 8, acc) * 1e-3)
+        if a.hits_name:
+            np.save(os.path.join(a.work, a.hits_name), hits[0])
         np.save(os.path.join(a.work, f"{a.tag}_profile_tags.npy"), np.stack([commet_amd.tags_at(hits[0], t) for t in range(1, a.max_t + 1)]))
     print("RESULT " + json.dumps(out), flush=True)
 
@@ -105,6 +117,26 @@ def med(x):
     return float(np.median(x))
 
 
+def groups_leg(a, tag, lib_args):
+    """the profile of one shape on the parent's library (if given), at chunk_group = 1 and at the default: fresh processes, alternated"""
+    legs = ([("parent", lib_args)] if lib_args else []) + [("group1", ["--chunk-group", "1"]), ("default", [])]
+    runs = {name: [] for name, _ in legs}
+    equal = []
+    for r in range(a.rounds):
+        for name, extra in legs:
+            runs[name].append(run_child(a, "profile", tag, a.limit, extra + ["--hits-name", f"{tag}_{name}.npy"] + (["--ceiling"] if r == 0 and name == "default" else [])))
+        h = [np.load(os.path.join(a.work, f"{tag}_{name}.npy")) for name, _ in legs]
+        equal.append(all(np.array_equal(h[0], x) for x in h[1:]))
+    out = {"hits_equal": all(equal), "runs": runs}
+    for name, _ in legs:
+        per = {f: [med(c[f]) for c in runs[name]] for f in ("total_ms", "index_ms", "search_ms")}
+        out[name] = {f: round(med(v), 3) for f, v in per.items()}
+        out[name]["total_ms_spread"] = round((max(per["total_ms"]) - min(per["total_ms"])) / med(per["total_ms"]), 4)
+        out[name].update(reads_walked=runs[name][0]["reads_walked"], search_launches=runs[name][0].get("search_launches"), chunks=runs[name][0]["chunks"],
+                         kernels_ms=runs[name][0]["kernels_ms"])
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--reads", type=int, default=10_000_000)
@@ -115,6 +147,9 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--jobs-lib", default=None)
     ap.add_argument("--many-chunks", action="store_true")
+    ap.add_argument("--groups", action="store_true")
+    ap.add_argument("--chunk-group", type=int, default=0, help=argparse.SUPPRESS)
+    ap.add_argument("--hits-name", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--many-reads", type=int, default=600_000)
     ap.add_argument("--limit", type=int, default=240, help="seconds a child may take")
     ap.add_argument("--out", default=None)
@@ -139,6 +174,28 @@ def main():
             np.save(os.path.join(a.work, f"c1{i}_b.npy"), b), np.save(os.path.join(a.work, f"c1{i}_o.npy"), o)
         res = {"workload": f"2 x {a.reads} x {a.read_len} bp, k={a.k}, t=1..{a.max_t}", "profile": [], "jobs": []}
         lib_args = ["--jobs-lib", a.jobs_lib] if a.jobs_lib else []
+        if a.groups:
+            res = {"workload": res["workload"], "groups": groups_leg(a, "c1", lib_args)}
+            if a.many_chunks:
+                n, L = a.many_reads, 150
+                for i in (0, 1):
+                    b, o = synth.synth_set(i, n, L, base_set=0)
+                    np.save(os.path.join(a.work, f"c4{i}_b.npy"), b), np.save(os.path.join(a.work, f"c4{i}_o.npy"), o)
+                res["many_chunks"] = {"workload": f"2 x {n} x {L} bp, k=21", "groups": groups_leg(a, "c4", lib_args),
+                                      "job_t5": run_child(a, "jobs", "c4", a.limit, lib_args + ["--ts", "5"])}
+            text = json.dumps(res)
+            if a.out:
+                os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+                open(a.out, "w").write(text + "\n")
+            for shape in (res, res.get("many_chunks")):
+                if shape:
+                    g = shape["groups"]
+                    print(json.dumps({"workload": shape["workload"], "hits_equal": g["hits_equal"],
+                                      **{name: {f: g[name][f] for f in ("total_ms", "index_ms", "search_ms", "total_ms_spread", "search_launches", "reads_walked")}
+                                         for name in ("parent", "group1", "default") if name in g}}))
+            if "many_chunks" in res:
+                print(json.dumps({"job_t5_ms": res["many_chunks"]["job_t5"]["per_t"]["5"]["total_ms"]}))
+            return
         for r in range(a.rounds):                                                # (a) and (b) alternate
             res["profile"].append(run_child(a, "profile", "c1", a.limit, ["--ceiling"] if r == 0 else []))
             res["jobs"].append(run_child(a, "jobs", "c1", a.limit, lib_args))
