@@ -209,7 +209,11 @@ class Context:
         per read of search set i, min(max_hits, the read's greedy non-overlapping full hits on its better strand, in its best chunk);
         tags_at(hits[i], t) is the BooleanVector index_and_search gives on a context of this k and that t, for every t in 1..max_hits.
         The chunk filters are searched in groups of up to set_option("chunk_group", 1..8) per pass over a search set (default 8; 1: one
-        filter per pass); the bytes do not depend on it, info["search_launches"] counts the passes."""
+        filter per pass); the bytes do not depend on it, info["search_launches"] counts the passes.
+        set_option("profile_wide", 2) takes the wide bit-sliced rows instead where 12 <= k <= 24 (jobs of many small chunks: every chunk
+        filter of a pass side by side in one table set, one hits_wide_kernel launch per search set and pass; "slice_wide_words" caps the
+        rows); 1 = never; 0 = auto: jobs of more than 256 chunk filters whose search sets hold no read of more than 300 bases (the shape it
+        was measured faster at).  The bytes do not depend on it either."""
         ns = len(search_sets)
         isel = _as_bits(index_select, index_rs.num_reads, "index_select")
         ssel = [None] * ns

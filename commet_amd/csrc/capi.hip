@@ -12,6 +12,7 @@
 #include "long_search.hpp"
 #include "hit_profile.hpp"
 #include "hit_profile_group.hpp"
+#include "hit_profile_wide.hpp"
 #include "read_filter.hpp"
 #include "read_iter.hpp"
 #include "host/fasta_source.hpp"

@@ -80,6 +80,11 @@ int commet_set_option(commet_ctx *c, const char *name, int64_t value)
         c->wide_cap_words = (uint32_t) value;
         return 0;
     }
+    if (!strcmp(name, "profile_wide")) {      // commet_index_and_profile through the wide rows: 0 auto (more than 256 chunks, no search read of more than 300 bases), 1 never, 2 whenever 12 <= k <= 24 and the job has a chunk
+        if (value < 0 || value > 2) return fail("profile_wide must be 0, 1 or 2");
+        c->profile_wide = (int) value;
+        return 0;
+    }
     if (!strcmp(name, "max_kmer")) {          // chunk size in k-mers (0 = the reference's constant); changes the chunking
         if (value < 0) return fail("max_kmer must be >= 0");
         c->max_kmer_test = (uint64_t) value;

@@ -13,7 +13,13 @@
 // cap = option "chunk_group" (default 8); 1 when k < 2 or the job has one chunk, and down the ladder 8 -> 4 -> 1 when the slots do
 // not fit.  A group of one chunk takes the one-filter kernels (hit_profile.hpp); chunk_group = 1 is the one-filter-per-pass form,
 // launch for launch.  No group8_ok condition: these kernels keep no masks.
-// Not done here: profiles through the bit-sliced tables or the tiled probe, and a profile form of commet_index_many_and_search.
+//
+// Many small chunks (12 <= k <= 24): option "profile_wide" = 2 takes the wide bit-sliced rows instead (run_profile_wide below;
+// hit_profile_wide.hpp): every chunk filter of a pass side by side in one table set, built 256 chunks at a time as run_sliced (job.hpp)
+// builds them, and ONE hits_wide_kernel launch per search set and pass; several passes when the rows are capped ("slice_wide_words")
+// or the table budget is small, folded by the byte array's max.  No room for the tables: the slot loop.  0 = auto (profile_wide_ok
+// below: more than 256 chunks and short reads, as measured); 1 = never.
+// Not done here: profiles through the narrow bit-sliced tables or the tiled probe, and a profile form of commet_index_many_and_search.
 #pragma once
 
 namespace {
@@ -142,6 +148,86 @@ int hits_pass(JobRun &j, int s, int g, int gs, int max_hits, uint8_t *d_hits, un
     return 0;
 }
 
+// does the call take the wide rows?  Option "profile_wide": 1 never, 2 whenever k allows it and the job has a chunk, 0 auto: jobs of
+// more than 256 chunks (the wide search's own threshold) whose search sets hold short reads only — measured 5.6x (313 chunks) and 7.2x
+// (1 043 chunks) faster than the slot loop on 150-base reads (MEASUREMENTS.md, "Hit profile").  The block counters bound a strand at two
+// hits, so a read of many windows has a chance hit in three blocks of most chunk filters and every such chunk is replayed: sets with a
+// read of more than PROFILE_WIDE_MAX_LEN bases (twice the measured length) keep the slot loop until somebody measures them
+constexpr uint32_t PROFILE_WIDE_MAX_LEN = 300;
+bool profile_wide_ok(const commet_ctx *c, uint64_t n_chunks, int n_search, const commet_readset *const *search_rs)
+{
+    if (c->profile_wide == 1 || c->k < SLICE_MIN_K || c->k > SLICE_MAX_K || n_chunks == 0) return false;
+    if (c->profile_wide == 2) return true;
+    if (n_chunks <= 256) return false;
+    for (int s = 0; s < n_search; ++s)
+        if (search_rs[s]->max_len > PROFILE_WIDE_MAX_LEN) return false;
+    return true;
+}
+
+// one pass of rs over the g chunk filters in the wide rows
+int launch_hits_wide(commet_ctx *c, const commet_readset *rs, const WidePlan &w, int g, int max_hits, const uint64_t *d_sel, uint8_t *d_hits,
+                     unsigned long long *d_walked)
+{
+    if (rs->n_reads == 0) return 0;
+    const uint64_t reads_per_block = 4ull * (64 / w.lpr);
+    const uint64_t blocks = (rs->n_reads + reads_per_block - 1) / reads_per_block;
+    if (blocks >= (1ull << 31)) return fail("search launch too large");
+    const dim3 grid((unsigned) blocks), block(256);
+    KScope ks(c, "hits_wide_kernel", c->stream);
+    auto launch = [&](auto LPR, auto NP) {
+        COMMET_LAUNCH((hits_wide_kernel<LPR, NP>), grid, block, 0, c->stream, rs->view(), c->wide_tables, c->k, max_hits, g, w.nw, w.rw, d_sel, d_hits,
+                      d_walked);
+    };
+    if (w.np == 2) launch(std::integral_constant<int, 64>{}, std::integral_constant<int, 2>{});
+    else with_value<64, 32, 16, 8>(w.lpr, [&](auto LPR) { launch(LPR, std::integral_constant<int, 1>{}); });
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+// the profile through the wide rows: the chunk filters of a pass (all of them when the tables fit) built 256 at a time into their
+// columns, then every search set scanned once.  at[s] = where set s's bytes start in c->d_hits.  *taken = false: no room for the
+// tables, nothing was launched and the caller takes the slot loop
+int run_profile_wide(JobRun &j, int max_hits, const std::vector<uint64_t> &at, unsigned long long *d_walked, bool want_times, bool *taken)
+{
+    commet_ctx *c = j.c;
+    const uint64_t n_chunks = j.n_chunks();
+    *taken = false;
+    const WidePlan wide = wide_rows(c, n_chunks);
+    if (!wide.nw || ensure_wide_tables(c, wide) || ensure_slice_buffers(c, (int) WIDE_GROUP_WORDS, n_chunks)) {
+        (void) hipGetLastError();
+        return 0;
+    }
+    *taken = true;
+    std::vector<SliceChunk> hc(n_chunks);
+    for (uint64_t i = 0; i < n_chunks; ++i) {
+        const Chunk &ch = j.plan.chunks[i];
+        hc[i].first = ch.first;
+        hc[i].count = ch.n_reads ? ch.last - ch.first + 1 : 0;
+    }
+    if (hipMemcpy(c->d_slice_chunks, hc.data(), n_chunks * sizeof(SliceChunk), hipMemcpyHostToDevice) != hipSuccess)
+        return fail("chunk descriptor upload failed");
+    const uint64_t per_pass = wide.chunks_per_pass;
+    j.tm.timed = want_times && ((n_chunks + per_pass - 1) / per_pass) * (uint64_t) (j.n_search + 2) <= 16384;
+    for (uint64_t c0 = 0; c0 < n_chunks; c0 += per_pass) {
+        const uint64_t c1 = std::min<uint64_t>(n_chunks, c0 + per_pass);
+        if (j.tm.begin_index()) return 1;
+        for (uint64_t ci = c0; ci < c1; ci += 256) {
+            if (launch_slice_build(c, j.index_rs, j.index_sel(), ci, (int) std::min<uint64_t>(256, c1 - ci), (int) WIDE_GROUP_WORDS, c->wide_tables, wide.rw,
+                                   (uint32_t) ((ci - c0) / 256 * WIDE_GROUP_WORDS)))
+                return 1;
+            j.n_index_launches += 2;
+        }
+        if (j.tm.end_index()) return 1;
+        for (int s = 0; s < j.n_search; ++s) {
+            const commet_readset *rs = j.search_rs[s];
+            if (launch_hits_wide(c, rs, wide, (int) (c1 - c0), max_hits, j.sel_of(s), c->d_hits + at[(size_t) s], d_walked)) return 1;
+            if (rs->n_reads) ++j.n_search_launches;
+            if (j.tm.end_set(s)) return 1;
+        }
+    }
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -170,9 +256,11 @@ int commet_index_and_profile(commet_ctx *c, const commet_readset *index_rs, cons
     const uint64_t n_chunks = j.n_chunks();
     j.tm.timed = info != nullptr && n_chunks * (uint64_t) (n_search + 4) <= 16384;
     int rc = 0;
+    bool wide = false;
+    if (profile_wide_ok(c, n_chunks, n_search, search_rs)) rc = run_profile_wide(j, max_hits, at, d_walked, info != nullptr, &wide);
     // the chunks in groups, as run_slots forms them (no group8_ok condition: the hits kernels keep no masks)
     int group_cap = (c->k >= 2 && n_chunks >= 2) ? std::max(1, std::min(8, c->chunk_group)) : 1;
-    for (uint64_t ci = 0; ci < n_chunks && !rc;) {
+    for (uint64_t ci = 0; ci < n_chunks && !rc && !wide;) {
         int g = (int) std::min<uint64_t>((uint64_t) group_cap, n_chunks - ci);
         const int gs = g <= 2 ? 2 : g <= 4 ? 4 : 8;
         if (g > 1 && ensure_slots(c, g, gs)) {   // not enough memory for the group

@@ -635,11 +635,11 @@ struct WidePlan {
     int lpr = 0, np = 0;          // lanes per read, 16-byte pieces per lane
 };
 
-WidePlan wide_plan(const commet_ctx *c, uint64_t n_chunks, int slice_gw)
+// the rows that hold n_chunks chunk filters under the table budget and option "slice_wide_words" (nw = 0: no room for a row of one group)
+WidePlan wide_rows(const commet_ctx *c, uint64_t n_chunks)
 {
     WidePlan w;
-    if (!slice_gw || c->slice_wide == 1) return w;
-    if (c->slice_wide == 0 && n_chunks <= 256) return w;             // one table of the narrow kind holds them all
+    if (n_chunks == 0) return w;
     const uint64_t groups = (n_chunks + 255) / 256;
     // four tables of 2^k rows: 16 bytes per row word and key; at most a third of what is free now, and 48 GiB
     size_t free_b = 0, total_b = 0;
@@ -659,6 +659,14 @@ WidePlan wide_plan(const commet_ctx *c, uint64_t n_chunks, int slice_gw)
     w.lpr = pieces <= 8 ? 8 : pieces <= 16 ? 16 : pieces <= 32 ? 32 : 64;
     w.np = pieces <= 64 ? 1 : 2;
     return w;
+}
+
+// a job's wide rows: none where option "slice_wide" or the chunk count says so
+WidePlan wide_plan(const commet_ctx *c, uint64_t n_chunks, int slice_gw)
+{
+    if (!slice_gw || c->slice_wide == 1) return WidePlan();
+    if (c->slice_wide == 0 && n_chunks <= 256) return WidePlan();    // one table of the narrow kind holds them all
+    return wide_rows(c, n_chunks);
 }
 
 int ensure_wide_tables(commet_ctx *c, const WidePlan &w)

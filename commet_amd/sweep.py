@@ -1,6 +1,6 @@
 """Threshold sweep: the `.bv` vectors of `index_and_search -t t` for every t in 1..T from ONE profile job.
 
-    python -m commet_amd.sweep -i index.txt -s search.txt -k K --max-t T -o OUT [--chunk-group N]
+    python -m commet_amd.sweep -i index.txt -s search.txt -k K --max-t T -o OUT [--chunk-group N] [--profile-wide {0,1,2}]
 
 -i / -s take the reference's set-config grammar (`name:file[,bv];file[,bv]...`, one set per line; the index file holds exactly one
 set).  The sets are parsed and packed by the library's own ingest (ReadSet.from_fasta), one Context.index_and_profile(max_hits=T) gives a hit count per read, and
@@ -10,7 +10,9 @@ set).  The sets are parsed and packed by the library's own ingest (ReadSet.from_
 
 The filters, which do not depend on t, are built once instead of T times, and every search set is walked once per GROUP of up to
 --chunk-group chunk filters (1..8, the library's option "chunk_group"; default: the library's, 8); the closing line reports the
-passes that took.  No .log files are written: the reference's `searched`
+passes that took.  --profile-wide (the library's option "profile_wide") 2 takes the wide bit-sliced rows at 12 <= k <= 24 instead:
+all chunk filters side by side, one pass per search set unless the rows are capped; 1 never, 0 the library's choice (default).
+No .log files are written: the reference's `searched`
 figure is the read count of the LAST chunk pass, which depends on t through the tags of the earlier chunks, and one pass over the
 chunks does not reproduce it."""
 import argparse
@@ -73,6 +75,8 @@ def parser():
     p.add_argument("--max-t", dest="max_t", type=int, required=True, help="largest threshold T (1..255); OUT/t1 .. OUT/tT are written")
     p.add_argument("-o", dest="out", required=True, help="output directory")
     p.add_argument("--chunk-group", dest="chunk_group", type=int, default=None, help="chunk filters per search pass (1..8; default: the library's)")
+    p.add_argument("--profile-wide", dest="profile_wide", type=int, default=None, choices=(0, 1, 2),
+                   help="the profile through the wide bit-sliced rows (12 <= k <= 24): 0 the library's choice, 1 never, 2 always")
     p.add_argument("--device", type=int, default=0)
     return p
 
@@ -99,6 +103,8 @@ def main(argv=None):
         loaded = [(tag, entries) + _load(api, ctx, entries) for tag, entries in search_sets]
         if a.chunk_group is not None:
             ctx.set_option("chunk_group", a.chunk_group)
+        if a.profile_wide is not None:
+            ctx.set_option("profile_wide", a.profile_wide)
         hits, info = ctx.index_and_profile(irs, [l[2] for l in loaded], isel, [l[4] for l in loaded], max_hits=a.max_t)
         rows = []
         for t in range(1, a.max_t + 1):

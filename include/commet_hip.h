@@ -309,7 +309,13 @@ int commet_index_many_and_search(commet_ctx *ctx, int n_jobs, const commet_reads
  * index_lanes are honoured.  info (may be NULL) as in a job; search_launches = the passes (groups x non-empty search sets),
  * reads_scanned = the reads the passes walked (once per group pass; a read whose count has reached max_hits is not walked again),
  * probes = 0.
- * Not done here: profiles through the bit-sliced tables or the tiled probe, and a profile form of commet_index_many_and_search. */
+ * Many small chunks (12 <= k <= 24), by option "profile_wide": every chunk filter of a pass side by side in the wide bit-sliced rows
+ * (as option "slice_wide" of a job), ONE hits_wide_kernel launch per search set and pass: a row pass over every window bounds each
+ * chunk's count by the blocks of k window ends that hold a hit, and a chunk is replayed exactly only while its bound exceeds the
+ * read's best count so far.  Several passes when "slice_wide_words" caps the rows or the table budget is small, folded by the bytes'
+ * max; no room for the tables: the loop above.  search_launches = passes x non-empty search sets; reads_scanned = the reads a pass
+ * walked (a read of fewer than k bases, or one already at min(max_hits, len / k), is not walked).  The bytes do not depend on it.
+ * Not done here: profiles through the narrow bit-sliced tables or the tiled probe, and a profile form of commet_index_many_and_search. */
 int commet_index_and_profile(commet_ctx *ctx, const commet_readset *index_rs, const uint8_t *index_select,
                              int n_search, const commet_readset *const *search_rs, const uint8_t *const *search_select,
                              int max_hits, uint8_t *const *hits_out, commet_job_info *info);
@@ -341,6 +347,9 @@ int commet_index_and_profile(commet_ctx *ctx, const commet_readset *index_rs, co
  *                        first 64 chunk filters on a sample of the reads (few reads found early: wide rows; most: the narrow
  *                        tables, whose later passes skip the reads already found), 1 = never, 2 = always
  *   slice_wide_words     cap on the words per wide row (a multiple of 8, 32 chunk filters per word; 0 = by the memory free)
+ *   profile_wide (0/1/2) commet_index_and_profile through the wide rows (hits_wide_kernel): 0 = jobs of more than 256 chunks whose
+ *                        search sets hold no read of more than 300 bases (measured on 150-base reads), 1 = never (the slot loop,
+ *                        launch for launch), 2 = whenever 12 <= k <= 24 and the job has a chunk; slice_wide_words caps its rows too
  *   query_list_budget_mb HBM the cached query lists of the context's read sets may hold (see commet_readset_cache_bytes)
  *   query_list_max_mb    auto mode of tiled_search: largest list (estimated) a set may get, default 4096 (sets of up to ~15 M reads;
  *                        larger lists — a 50 M-read set's is 11 GB — pay in long-lived contexts only: allocating them costs

@@ -11,6 +11,10 @@ stream synchronise and the copy back) and then runs once more with option kernel
                     chunk_group = 1, at the default and, with --jobs-lib, on that library (the parent commit's build), in fresh child
                     processes alternating over `--rounds`; the hit bytes of the three are compared, medians and spreads reported,
                     and one job at t = 5 of the many-chunk shape gives the break-even T
+  --wide            ONLY the profile_wide leg (needs --many-chunks): on the many-chunk shape (2 x 600 000 x 150 bp, k = 21, 313 chunks) and,
+                    when --many-reads is given more than once, on every further read count (2 000 000 reads cross 1 024 chunks), the
+                    profile on --jobs-lib (the parent commit's build), at profile_wide = 1 and at profile_wide = 2, fresh child processes
+                    alternating over `--rounds`, the three hit arrays byte-compared; one job at t = 5 gives the break-even T
   python tools/hits_bench.py [--reads 10000000] [--read-len 100] [-k 32] [--max-t 8] [--rounds 2] [--reps 3] [--out FILE]"""
 import argparse
 import json
@@ -46,6 +50,8 @@ def child_profile(a):
             ctx.set_option("max_kmer", a.max_kmer)
         if a.chunk_group:
             ctx.set_option("chunk_group", a.chunk_group)
+        if a.profile_wide:
+            ctx.set_option("profile_wide", a.profile_wide)
         irs = commet_amd.ReadSet.from_files(ctx, [(b0, o0)])
         qrs = commet_amd.ReadSet.from_files(ctx, [(b1, o1)])
         ctx.index_and_profile(irs, [qrs], max_hits=a.max_t)                      # warm-up
@@ -117,9 +123,11 @@ def med(x):
     return float(np.median(x))
 
 
-def groups_leg(a, tag, lib_args):
-    """the profile of one shape on the parent's library (if given), at chunk_group = 1 and at the default: fresh processes, alternated"""
-    legs = ([("parent", lib_args)] if lib_args else []) + [("group1", ["--chunk-group", "1"]), ("default", [])]
+def groups_leg(a, tag, lib_args, legs=None):
+    """the profile of one shape on the parent's library (if given), at chunk_group = 1 and at the default (or the given legs): fresh
+    processes, alternated"""
+    if legs is None:
+        legs = ([("parent", lib_args)] if lib_args else []) + [("group1", ["--chunk-group", "1"]), ("default", [])]
     runs = {name: [] for name, _ in legs}
     equal = []
     for r in range(a.rounds):
@@ -150,7 +158,9 @@ def main():
     ap.add_argument("--groups", action="store_true")
     ap.add_argument("--chunk-group", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--hits-name", default=None, help=argparse.SUPPRESS)
-    ap.add_argument("--many-reads", type=int, default=600_000)
+    ap.add_argument("--wide", action="store_true")
+    ap.add_argument("--profile-wide", type=int, default=0, help=argparse.SUPPRESS)
+    ap.add_argument("--many-reads", type=int, nargs="+", default=[600_000])
     ap.add_argument("--limit", type=int, default=240, help="seconds a child may take")
     ap.add_argument("--out", default=None)
     ap.add_argument("--child", default=None, help=argparse.SUPPRESS)
@@ -169,11 +179,33 @@ def main():
     from commet_amd import synth
     a.work = tempfile.mkdtemp(prefix="hits_bench_")
     try:
-        for i in (0, 1):
+        for i in (0, 1) if not a.wide else ():                                   # (the wide leg has shapes of its own)
             b, o = synth.synth_set(i, a.reads, a.read_len, base_set=0)
             np.save(os.path.join(a.work, f"c1{i}_b.npy"), b), np.save(os.path.join(a.work, f"c1{i}_o.npy"), o)
         res = {"workload": f"2 x {a.reads} x {a.read_len} bp, k={a.k}, t=1..{a.max_t}", "profile": [], "jobs": []}
         lib_args = ["--jobs-lib", a.jobs_lib] if a.jobs_lib else []
+        if a.wide:
+            if not a.many_chunks:
+                raise SystemExit("--wide measures the many-chunk shapes: give --many-chunks")
+            legs = ([("parent", lib_args)] if lib_args else []) + [("wide1", ["--profile-wide", "1"]), ("wide2", ["--profile-wide", "2"])]
+            res = {"shapes": []}
+            for n in a.many_reads:
+                L = 150
+                for i in (0, 1):
+                    b, o = synth.synth_set(i, n, L, base_set=0)
+                    np.save(os.path.join(a.work, f"c4{i}_b.npy"), b), np.save(os.path.join(a.work, f"c4{i}_o.npy"), o)
+                shape = {"workload": f"2 x {n} x {L} bp, k=21, T={a.max_t}", "wide": groups_leg(a, "c4", lib_args, legs),
+                         "job_t5": run_child(a, "jobs", "c4", a.limit, lib_args + ["--ts", "5"])}
+                res["shapes"].append(shape)
+                w = shape["wide"]
+                print(json.dumps({"workload": shape["workload"], "hits_equal": w["hits_equal"], "job_t5_ms": shape["job_t5"]["per_t"]["5"]["total_ms"],
+                                  **{name: {f: w[name][f] for f in ("total_ms", "index_ms", "search_ms", "total_ms_spread", "search_launches", "reads_walked", "chunks")}
+                                     for name, _ in legs}}), flush=True)
+            if a.out:
+                os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+                open(a.out, "w").write(json.dumps(res) + "\n")
+            return
+        a.many_reads = a.many_reads[0]
         if a.groups:
             res = {"workload": res["workload"], "groups": groups_leg(a, "c1", lib_args)}
             if a.many_chunks:

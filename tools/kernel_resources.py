@@ -12,6 +12,7 @@ p = subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-sha
                     "-o", "/tmp/_kr.so", os.path.join(ROOT, "commet_amd", "csrc", "capi.hip"), "-lz"] + extra, capture_output=True, text=True)
 OCC = r"Occupancy \[waves/SIMD\]"
 LDS = r"LDS Size \[bytes/block\]"
+SCRATCH = r"ScratchSize \[bytes/lane\]"
 for b in re.split(r"remark: Function Name: ", p.stderr)[1:]:
     name = b.split(" ")[0].split("\n")[0]
     g = lambda k: int((re.search(k + r": (\d+)", b) or [0, 0])[1])
@@ -19,4 +20,4 @@ for b in re.split(r"remark: Function Name: ", p.stderr)[1:]:
     d = re.sub(r"^void commet::", "", re.sub(r"\(.*", "", d))
     sg = g("TotalSGPRs")
     adm = min(8, 800 // (-(-sg // 16) * 16 + 16))
-    print(f"{d[:72]:72s} sgpr {sg:4d} (wg/CU by sgpr {adm}) vgpr {g('VGPRs'):4d} occ {g(OCC)} sspill {g('SGPRs Spill'):3d} vspill {g('VGPRs Spill'):3d} lds {g(LDS)}")
+    print(f"{d[:72]:72s} sgpr {sg:4d} (wg/CU by sgpr {adm}) vgpr {g('VGPRs'):4d} occ {g(OCC)} sspill {g('SGPRs Spill'):3d} vspill {g('VGPRs Spill'):3d} scratch {g(SCRATCH)} lds {g(LDS)}")
