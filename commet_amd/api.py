@@ -228,7 +228,13 @@ class Context:
                                                        C.byref(info)))
         return hits, {f: getattr(info, f) for f, _ in _l.JobInfo._fields_}
 
-    def export_filter_reference(self):
+    def poison(self, byte):
+        """test hook: every bit array of the context (filter slots, interleaved A planes, bit-sliced planes and tables) filled with `byte`"""
+        self.set_option("poison", byte)
+
+    def export_filter_reference(self, slot=0):
+        """the filter of `slot` in the reference's byte layout (a job leaves the chunk filters of its last groups in slots 0 .. g - 1)"""
+        self.set_option("export_slot", slot)
         nbytes = int(2 ** (self.k - 1))
         out = np.zeros(max(nbytes, 1), dtype=np.uint8)
         self._check(self._lib.commet_filter_export_reference(self._h, _ptr(out), out.size))

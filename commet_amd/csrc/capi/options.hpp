@@ -105,6 +105,27 @@ int commet_set_option(commet_ctx *c, const char *name, int64_t value)
         }
         return 0;
     }
+    if (!strcmp(name, "export_slot")) {       // the filter slot commet_filter_export_reference copies (kept apart from cur_slot, which every job resets)
+        if (value < 0 || value > 7) return fail("export_slot must be 0..7");
+        c->export_slot = (int) value;                          // (against the slots the context has: when the export is asked for)
+        return 0;
+    }
+    if (!strcmp(name, "poison")) {            // fills the context's BIT ARRAYS with the byte: a build that counts on what its buffers held before shows
+        if (value < 0 || value > 255) return fail("poison must be a byte, 0..255");
+        // only buffers in which every byte value is legal content (filter slots, interleaved A planes, bit-sliced planes and tables): no
+        // key, offset, list or counter buffer — a stale one of those misread would be an address, a wrong bit here is only a wrong bit
+        HIP_OK(hipSetDevice(c->device));
+        HIP_OK(hipStreamSynchronize(c->stream));
+        HIP_OK(hipStreamSynchronize(c->aux_stream));
+        const int b = (int) value;
+        if (c->filter) HIP_OK(hipMemsetAsync(c->filter, b, (size_t) c->n_slots * c->filter_bytes, c->stream));
+        if (c->il_a) HIP_OK(hipMemsetAsync(c->il_a, b, (size_t) c->il_words * sizeof(uint32_t), c->stream));
+        if (c->slice_stage) HIP_OK(hipMemsetAsync(c->slice_stage, b, (size_t) c->slice_stage_words * sizeof(uint32_t), c->stream));
+        if (c->slice_tables) HIP_OK(hipMemsetAsync(c->slice_tables, b, (size_t) c->slice_table_words * sizeof(uint32_t), c->stream));
+        if (c->wide_tables) HIP_OK(hipMemsetAsync(c->wide_tables, b, (size_t) c->wide_table_words * sizeof(uint32_t), c->stream));
+        HIP_OK(hipStreamSynchronize(c->stream));
+        return 0;
+    }
     if (!strcmp(name, "part_packed")) {
         c->part_packed = value != 0;
         return 0;
@@ -140,12 +161,14 @@ int commet_filter_export_reference(commet_ctx *c, uint8_t *out, uint64_t out_byt
 {
     const uint64_t nbytes = (uint64_t) pow(2, c->k - 1);   // bloom_filter.h:73
     if (out_bytes < nbytes) return fail("export buffer too small");
+    if (c->export_slot < 0 || c->export_slot >= c->n_slots)
+        return fail("filter export: slot %d asked for (option export_slot), the context has %d", c->export_slot, c->n_slots);
     if (nbytes == 0) return 0;
     HIP_OK(hipSetDevice(c->device));
     uint8_t *d_out = nullptr;
     HIP_OK(dm_malloc((void **) &d_out, nbytes));
     const uint64_t blocks = std::min<uint64_t>((nbytes + 255) / 256, 1u << 20);   // grid-stride beyond
-    COMMET_LAUNCH(export_reference_kernel, dim3((unsigned) blocks), dim3(256), 0, c->stream, c->view(), c->k, nbytes, d_out);
+    COMMET_LAUNCH(export_reference_kernel, dim3((unsigned) blocks), dim3(256), 0, c->stream, c->view_of(c->export_slot), c->k, nbytes, d_out);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, nbytes, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);

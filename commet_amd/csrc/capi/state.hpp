@@ -480,6 +480,7 @@ struct commet_ctx {
 
     int n_slots = 1;                  // filter slots allocated behind `filter` (chunk groups, kernels.hpp)
     int cur_slot = 0;                 // slot the index / search launch helpers work on
+    int export_slot = 0;              // option "export_slot" (tests): the slot commet_filter_export_reference copies
     uint32_t *il_a = nullptr;         // interleaved A planes of a chunk group
     uint64_t il_words = 0;            // ... as allocated: stride x plane_words
     // option "kernel_timing": a hipEvent pair around every kernel launch of commet_index_and_search, on the stream the
@@ -596,9 +597,10 @@ struct commet_ctx {
     uint64_t ql_max_list = 4ull << 30;                // auto mode: sets whose list (8 bytes per first-hit window, estimated) is larger keep the gather kernels
 
     uint32_t *slot_ptr(int i) const { return filter + (uint64_t) i * 4 * plane_words; }
-    FilterView view() const
+    FilterView view() const { return view_of(cur_slot); }
+    FilterView view_of(int slot) const
     {
-        uint32_t *base = slot_ptr(cur_slot);
+        uint32_t *base = slot_ptr(slot);
         FilterView f;
         f.a = base;
         f.b = base + plane_words;

@@ -377,11 +377,19 @@ int commet_index_and_profile(commet_ctx *ctx, const commet_readset *index_rs, co
  *                        chunk; the words of the coming round's items prefetched as on fixed-length sets), 1 = the round planner
  *   kernel_timing (0/1)  time every kernel launch of commet_index_and_search (commet_kernel_times)
  *   max_kmer             TEST HOOK: k-mers per index chunk instead of the reference's constant (0 = reference; the
- *                        results are then those of a reference built with that constant, index_and_search.cpp:73) */
+ *                        results are then those of a reference built with that constant, index_and_search.cpp:73)
+ *   export_slot (0..7)   TEST HOOK: the filter slot commet_filter_export_reference copies (default 0; a job builds the chunk filters
+ *                        of a group into slots 0 .. g - 1 and leaves them there); the export fails when the context has no such slot
+ *   poison (0..255)      TEST HOOK, an action: waits for the context's two job streams, fills every device buffer of the context that
+ *                        is a BIT ARRAY with the byte — all filter slots, the interleaved A planes, the staging planes and the tables
+ *                        of the bit-sliced regimes — and waits again.  A job must give the same bits afterwards: the bucketed build
+ *                        zeroes no slot, it defines every tile itself.  No other buffer is touched (keys, offsets, lists, counters:
+ *                        a stale one of those misread would be an address) */
 int commet_set_option(commet_ctx *ctx, const char *name, int64_t value);
 /* Copies the filter to the host in the REFERENCE byte layout (byte key/2,
  * even keys 0x80/40/20/10, odd keys 0x08/04/02/01 for a/b/c/d,
- * bloom_filter.h:63-70,114-117); out has 2^(k-1) bytes.  For parity tests. */
+ * bloom_filter.h:63-70,114-117); out has 2^(k-1) bytes.  For parity tests.
+ * The slot of option "export_slot" (default 0). */
 int commet_filter_export_reference(commet_ctx *ctx, uint8_t *out, uint64_t out_bytes);
 /* Device time in ms of the most recent index / search kernel launch on this
  * ctx, measured with hipEvents on the ctx's stream (synchronises). */
