@@ -284,10 +284,9 @@ int probe_wide_or_narrow(JobRun &j, bool *narrow)
     return 0;
 }
 
-// the many-small-chunks regime: the chunk filters of a group live bit-sliced in one set of tables (slice_search.hpp)
-int run_sliced(JobRun &j)
+// where each chunk's reads lie in the index set, for slice_build_kernel: c->d_slice_chunks (ensure_slice_buffers has sized it)
+int upload_chunk_descriptors(JobRun &j)
 {
-    commet_ctx *c = j.c;
     const uint64_t n_chunks = j.n_chunks();
     std::vector<SliceChunk> hc(n_chunks);
     for (uint64_t i = 0; i < n_chunks; ++i) {
@@ -295,35 +294,67 @@ int run_sliced(JobRun &j)
         hc[i].first = ch.first;
         hc[i].count = ch.n_reads ? ch.last - ch.first + 1 : 0;
     }
-    WidePlan wide = wide_plan(c, n_chunks, j.slice_gw);
-    if (wide.nw && ensure_wide_tables(c, wide)) wide = WidePlan();   // no room for the wide tables: groups of 256 chunks as before
-    if (ensure_slice_buffers(c, wide.nw ? 8 : j.slice_gw, n_chunks)) return 1;   // (sized by the caller already; a wide plan that fell back may need less)
-    if (hipMemcpy(c->d_slice_chunks, hc.data(), n_chunks * sizeof(SliceChunk), hipMemcpyHostToDevice) != hipSuccess)
+    if (hipMemcpy(j.c->d_slice_chunks, hc.data(), n_chunks * sizeof(SliceChunk), hipMemcpyHostToDevice) != hipSuccess)
         return fail("chunk descriptor upload failed");
-    if (wide.nw && c->slice_wide == 0) {
-        bool narrow = false;
-        if (probe_wide_or_narrow(j, &narrow)) return 1;
-        if (narrow) wide = WidePlan();
-    }
-    // wide rows: the filters of a pass's chunks (all of them when the tables fit) are built 256 at a time into their columns of the
-    // rows; narrow tables: a pass is one group of 32 x slice_gw chunks.  Either way every search set is scanned ONCE per pass
-    const uint64_t per_pass = wide.nw ? wide.chunks_per_pass : 32ull * j.slice_gw;
-    for (uint64_t c0 = 0; c0 < n_chunks; c0 += per_pass) {
-        const uint64_t c1 = std::min<uint64_t>(n_chunks, c0 + per_pass);
+    return 0;
+}
+
+// The passes of jobs and profiles through the wide rows (c->wide_tables, made for w; the descriptors uploaded): the filters of a
+// pass's chunks (all of them when the tables fit) are built 256 at a time into their columns of the rows, then every search set is
+// scanned ONCE: launch(s, c0, c1) scans set s against chunks c0 .. c1 - 1 and returns non-zero on failure, as this does at the first
+template <typename SetLaunch>
+int run_wide_passes(JobRun &j, const WidePlan &w, SetLaunch launch)
+{
+    commet_ctx *c = j.c;
+    const uint64_t n_chunks = j.n_chunks();
+    for (uint64_t c0 = 0; c0 < n_chunks; c0 += w.chunks_per_pass) {
+        const uint64_t c1 = std::min<uint64_t>(n_chunks, c0 + w.chunks_per_pass);
         if (j.tm.begin_index()) return 1;
-        for (uint64_t ci = c0; ci < c1; ci += wide.nw ? 256 : per_pass) {
-            if (wide.nw ? launch_slice_build(c, j.index_rs, j.index_sel(), ci, (int) std::min<uint64_t>(256, c1 - ci), 8, c->wide_tables, wide.rw,
-                                             (uint32_t) ((ci - c0) / 256 * WIDE_GROUP_WORDS))
-                        : launch_slice_build(c, j.index_rs, j.index_sel(), ci, (int) (c1 - ci), j.slice_gw))
+        for (uint64_t ci = c0; ci < c1; ci += 256) {
+            if (launch_slice_build(c, j.index_rs, j.index_sel(), ci, (int) std::min<uint64_t>(256, c1 - ci), (int) WIDE_GROUP_WORDS, c->wide_tables, w.rw,
+                                   (uint32_t) ((ci - c0) / 256 * WIDE_GROUP_WORDS)))
                 return 1;
             j.n_index_launches += 2;
         }
         if (j.tm.end_index()) return 1;
         for (int s = 0; s < j.n_search; ++s) {
+            if (launch(s, c0, c1)) return 1;
+            if (j.search_rs[s]->n_reads) ++j.n_search_launches;
+            if (j.tm.end_set(s)) return 1;
+        }
+    }
+    return 0;
+}
+
+// the many-small-chunks regime: the chunk filters of a group live bit-sliced in one set of tables (slice_search.hpp)
+int run_sliced(JobRun &j)
+{
+    commet_ctx *c = j.c;
+    const uint64_t n_chunks = j.n_chunks();
+    WidePlan wide = wide_plan(c, n_chunks, j.slice_gw);
+    if (wide.nw && ensure_wide_tables(c, wide)) wide = WidePlan();   // no room for the wide tables: groups of 256 chunks as before
+    if (ensure_slice_buffers(c, wide.nw ? 8 : j.slice_gw, n_chunks)) return 1;   // (sized by the caller already; a wide plan that fell back may need less)
+    if (upload_chunk_descriptors(j)) return 1;
+    if (wide.nw && c->slice_wide == 0) {
+        bool narrow = false;
+        if (probe_wide_or_narrow(j, &narrow)) return 1;
+        if (narrow) wide = WidePlan();
+    }
+    if (wide.nw)
+        return run_wide_passes(j, wide, [&](int s, uint64_t c0, uint64_t c1) {
             const commet_readset *rs = j.search_rs[s];
-            if (wide.nw ? launch_search_wide(c, rs, wide, (int) (c1 - c0), j.sel_of(s), rs->d_tags, j.cnt_at(c0, s), j.cstride())
-                        : launch_search_sliced(c, rs, (int) (c1 - c0), j.slice_gw, j.sel_of(s), rs->d_tags, j.cnt_at(c0, s), j.cstride()))
-                return 1;
+            return launch_search_wide(c, rs, wide, (int) (c1 - c0), j.sel_of(s), rs->d_tags, j.cnt_at(c0, s), j.cstride());
+        });
+    // narrow tables: a pass is one group of 32 x slice_gw chunks, and every search set is scanned ONCE per pass
+    const uint64_t per_pass = 32ull * j.slice_gw;
+    for (uint64_t c0 = 0; c0 < n_chunks; c0 += per_pass) {
+        const uint64_t c1 = std::min<uint64_t>(n_chunks, c0 + per_pass);
+        if (j.tm.begin_index() || launch_slice_build(c, j.index_rs, j.index_sel(), c0, (int) (c1 - c0), j.slice_gw)) return 1;
+        j.n_index_launches += 2;
+        if (j.tm.end_index()) return 1;
+        for (int s = 0; s < j.n_search; ++s) {
+            const commet_readset *rs = j.search_rs[s];
+            if (launch_search_sliced(c, rs, (int) (c1 - c0), j.slice_gw, j.sel_of(s), rs->d_tags, j.cnt_at(c0, s), j.cstride())) return 1;
             if (rs->n_reads) ++j.n_search_launches;
             if (j.tm.end_set(s)) return 1;
         }
@@ -365,19 +396,15 @@ int build_group(JobRun &j, uint64_t ci, int g, int gs)
     return g > 1 ? launch_interleave(c, g, gs) : 0;
 }
 
-// chunks are taken in groups of up to `chunk_group`: their filters are built into separate slots and every
-// search set is scanned ONCE per group (search_group_kernel) instead of once per chunk
-int run_slots(JobRun &j)
+// The slot loop of jobs and profiles: the chunks in groups of g = min(group_cap, chunks left), their filters built into slots
+// 0 .. g - 1 with the A planes interleaved at stride gs = 2 / 4 / 8, down the ladder 8 -> 4 -> 1 when the slots do not fit; every
+// search set takes ONE pass per group: pass(j, s, ci, g, gs), non-zero on failure, as this returns at the first.  (The current slot
+// is put back after every group: search_pass moves it; hits_pass, profile.hpp, sets it itself and does not care)
+template <typename Pass>
+int run_slot_groups(JobRun &j, int group_cap, Pass pass)
 {
     commet_ctx *c = j.c;
     const uint64_t n_chunks = j.n_chunks();
-    int group_cap = (c->k >= 2) ? std::max(1, std::min(8, c->chunk_group)) : 1;
-    if (n_chunks < 2) group_cap = 1;
-    if (group_cap > 4) {   // more than four filters per pass: every search set must qualify for the register-mask kernel
-        bool ok8 = n_chunks > 4;
-        for (int s = 0; s < j.n_search && ok8; ++s) ok8 = group8_ok(c, j.search_rs[s]) || long_ok(c, j.search_rs[s]);   // (search_long_kernel keeps no masks)
-        if (!ok8) group_cap = 4;
-    }
     for (uint64_t ci = 0; ci < n_chunks;) {
         int g = (int) std::min<uint64_t>((uint64_t) group_cap, n_chunks - ci);
         const int gs = g <= 2 ? 2 : g <= 4 ? 4 : 8;
@@ -392,11 +419,27 @@ int run_slots(JobRun &j)
         }
         if (j.tm.begin_index() || build_group(j, ci, g, gs) || j.tm.end_index()) return 1;
         for (int s = 0; s < j.n_search; ++s)
-            if (search_pass(j, s, ci, g, gs) || j.tm.end_set(s)) return 1;
+            if (pass(j, s, ci, g, gs) || j.tm.end_set(s)) return 1;
         c->cur_slot = 0;
         ci += (uint64_t) g;
     }
     return 0;
+}
+
+// a job's chunks in groups of up to `chunk_group`: every search set is scanned ONCE per group (search_group_kernel) instead of
+// once per chunk
+int run_slots(JobRun &j)
+{
+    commet_ctx *c = j.c;
+    const uint64_t n_chunks = j.n_chunks();
+    int group_cap = (c->k >= 2) ? std::max(1, std::min(8, c->chunk_group)) : 1;
+    if (n_chunks < 2) group_cap = 1;
+    if (group_cap > 4) {   // more than four filters per pass: every search set must qualify for the register-mask kernel
+        bool ok8 = n_chunks > 4;
+        for (int s = 0; s < j.n_search && ok8; ++s) ok8 = group8_ok(c, j.search_rs[s]) || long_ok(c, j.search_rs[s]);   // (search_long_kernel keeps no masks)
+        if (!ok8) group_cap = 4;
+    }
+    return run_slot_groups(j, group_cap, search_pass);
 }
 
 // the job's counters on the device, then its chunks through the regime that takes them

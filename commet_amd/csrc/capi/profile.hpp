@@ -7,131 +7,69 @@
 // hits of the whole forward / reverse-complement strand; across chunks the tags are ORed, and skipping tagged reads never changes
 // which other reads are visited (read_iter.hpp, SetIterator::next).  Hence hits(r) = min(T, max over chunks of max(F, R)).
 //
-// Up to eight chunk filters per pass: the chunks are taken in groups as run_slots (job.hpp) forms them — g = min(cap, chunks left)
-// filters built into slots 0 .. g - 1, their A planes interleaved with stride gs = 2 / 4 / 8 — and every search set takes ONE hits
-// pass per group (hit_profile_group.hpp: one walk of the read, one plane-A request per window for all g filters and both strands).
-// cap = option "chunk_group" (default 8); 1 when k < 2 or the job has one chunk, and down the ladder 8 -> 4 -> 1 when the slots do
-// not fit.  A group of one chunk takes the one-filter kernels (hit_profile.hpp); chunk_group = 1 is the one-filter-per-pass form,
-// launch for launch.  No group8_ok condition: these kernels keep no masks.
+// Up to eight chunk filters per pass: the chunks go through run_slot_groups (job.hpp), the job's own slot loop — the same groups in
+// the same slots, down the same ladder 8 -> 4 -> 1 when the slots do not fit — and every search set takes ONE hits pass per group
+// (hit_profile_group.hpp: one walk of the read, one plane-A request per window for all g filters and both strands).  cap = option
+// "chunk_group" (default 8); 1 when k < 2 or the job has one chunk.  A group of one chunk takes the one-filter kernels
+// (hit_profile.hpp); chunk_group = 1 is the one-filter-per-pass form, launch for launch.  No group8_ok condition: these kernels
+// keep no masks.
 //
 // Many small chunks (12 <= k <= 24): option "profile_wide" = 2 takes the wide bit-sliced rows instead (run_profile_wide below;
-// hit_profile_wide.hpp): every chunk filter of a pass side by side in one table set, built 256 chunks at a time as run_sliced (job.hpp)
-// builds them, and ONE hits_wide_kernel launch per search set and pass; several passes when the rows are capped ("slice_wide_words")
+// hit_profile_wide.hpp): every chunk filter of a pass side by side in one table set, built by run_wide_passes (job.hpp) as a job's
+// are, and ONE hits_wide_kernel launch per search set and pass; several passes when the rows are capped ("slice_wide_words")
 // or the table budget is small, folded by the byte array's max.  No room for the tables: the slot loop.  0 = auto (profile_wide_ok
 // below: more than 256 chunks and short reads, as measured); 1 = never.
-// Not done here: profiles through the narrow bit-sliced tables or the tiled probe, and a profile form of commet_index_many_and_search.
+// Not done here: profiles through the narrow bit-sliced tables or the tiled probe, and a profile form of commet_index_many_and_search
+// (each a pass function for one of the two shared loops).
 #pragma once
 
 namespace {
 
-// which hits kernel a set takes: option "long_search" as in long_ok (search_dispatch.hpp) — 0: sets whose longest read has
-// LONG_MIN_MAX_LEN bases (such a read has more than MASK_MAX_WIN windows whatever t), 1 never, 2 whenever the set has a read.
-// The context's t plays no part
+// which hits kernel a set takes: option "long_search" as long_mode (search_dispatch.hpp) reads it; auto: sets whose longest read
+// has LONG_MIN_MAX_LEN bases (such a read has more than MASK_MAX_WIN windows whatever t).  The context's t plays no part
 bool hits_wave_ok(const commet_ctx *c, const commet_readset *rs)
 {
-    if (c->long_search == 1 || c->k < 2 || rs->n_reads == 0) return false;
-    if (c->long_search == 2) return true;
-    return rs->max_len >= LONG_MIN_MAX_LEN;
+    const LongMode m = long_mode(c, rs);
+    return m == LongMode::always || (m == LongMode::automatic && rs->max_len >= LONG_MIN_MAX_LEN);
 }
 
-// persistent grid of hits_wave_kernel<W>: the workgroups the device holds at once, four reads each
-template <typename W>
-uint64_t hits_wave_blocks(const commet_ctx *c, uint64_t items)
-{
-    static std::atomic<int> resident{0};
-    int wgs = resident.load(std::memory_order_relaxed);
-    if (!wgs) {
-        int per_cu = 0, cus = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, hits_wave_kernel<W>, LONG_WG, 0) != hipSuccess ||
-            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess || per_cu < 1 || cus < 1) {
-            (void) hipGetLastError();
-            per_cu = 4, cus = 256;
-        }
-        wgs = per_cu * cus;
-        resident.store(wgs, std::memory_order_relaxed);
-    }
-    return std::min<uint64_t>((items + 3) / 4, (uint64_t) wgs);
-}
-
-// persistent grid of hits_group_wave_kernel<W, NF>, as above
-template <typename W, int NF>
-uint64_t hits_group_wave_blocks(const commet_ctx *c, uint64_t items)
-{
-    static std::atomic<int> resident{0};
-    int wgs = resident.load(std::memory_order_relaxed);
-    if (!wgs) {
-        int per_cu = 0, cus = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, hits_group_wave_kernel<W, NF>, LONG_WG, 0) != hipSuccess ||
-            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess || per_cu < 1 || cus < 1) {
-            (void) hipGetLastError();
-            per_cu = 4, cus = 256;
-        }
-        wgs = per_cu * cus;
-        resident.store(wgs, std::memory_order_relaxed);
-    }
-    return std::min<uint64_t>((items + 3) / 4, (uint64_t) wgs);
-}
-
-// one pass of rs over the g filters in slots 0 .. g - 1 (g >= 2, their A planes interleaved with stride gs); al as in launch_hits below
-int launch_hits_group(commet_ctx *c, const commet_readset *rs, int g, int gs, int max_hits, const uint64_t *d_sel, uint8_t *d_hits,
-                      unsigned long long *d_walked, ActiveList al, uint64_t n_launch)
+// one pass of rs over the g filters in slots 0 .. g - 1: g == 1: the filter in slot 0, the one-filter kernels; g >= 2: the group
+// kernels, the A planes interleaved with stride gs.  al.ids != nullptr: over the n_launch (at most) listed reads
+int launch_hits(commet_ctx *c, const commet_readset *rs, int g, int gs, int max_hits, const uint64_t *d_sel, uint8_t *d_hits,
+                unsigned long long *d_walked, ActiveList al, uint64_t n_launch)
 {
     if (rs->n_reads == 0) return 0;
     if (al.ids && n_launch == 0) return 0;
     const uint64_t items = al.ids ? n_launch : rs->n_reads;
-    const FilterGroupView fg = filter_group(c, g, 0, true);
-    if (hits_wave_ok(c, rs)) {
-        KScope ks(c, "hits_group_wave_kernel", c->stream);
-        with_key(c->k, [&](auto key) {
-            using W = decltype(key);
-            with_value<2, 4, 8>(gs, [&](auto NF) {
-                COMMET_LAUNCH((hits_group_wave_kernel<W, NF>), dim3((unsigned) hits_group_wave_blocks<W, NF>(c, items)), dim3(LONG_WG), 0, c->stream,
-                              rs->view(), fg, c->k, max_hits, d_sel, d_hits, d_walked, al);
-            });
+    const bool wave = hits_wave_ok(c, rs);          // a wave per read on a persistent grid, else a lane per read
+    if (!wave && launch_size_ok(items)) return 1;
+    const dim3 lanes((unsigned) ((items + 255) / 256));
+    KScope ks(c, g > 1 ? (wave ? "hits_group_wave_kernel" : "hits_group_kernel") : (wave ? "hits_wave_kernel" : "hits_kernel"), c->stream);
+    with_key(c->k, [&](auto key) {
+        using W = decltype(key);
+        if (g == 1) {
+            if (wave)
+                COMMET_LAUNCH(hits_wave_kernel<W>, dim3((unsigned) resident_blocks<hits_wave_kernel<W>>(c, items)), dim3(LONG_WG), 0, c->stream, rs->view(),
+                              c->view(), c->k, max_hits, d_sel, d_hits, d_walked, al);
+            else
+                COMMET_LAUNCH(hits_kernel<W>, lanes, dim3(256), 0, c->stream, rs->view(), c->view(), c->k, max_hits, d_sel, d_hits, d_walked, al);
+            return;
+        }
+        const FilterGroupView fg = filter_group(c, g, 0, true);
+        with_value<2, 4, 8>(gs, [&](auto NF) {
+            if (wave)
+                COMMET_LAUNCH((hits_group_wave_kernel<W, NF>), dim3((unsigned) resident_blocks<hits_group_wave_kernel<W, NF>>(c, items)), dim3(LONG_WG), 0,
+                              c->stream, rs->view(), fg, c->k, max_hits, d_sel, d_hits, d_walked, al);
+            else
+                COMMET_LAUNCH((hits_group_kernel<W, NF>), lanes, dim3(256), 0, c->stream, rs->view(), fg, c->k, max_hits, d_sel, d_hits, d_walked, al);
         });
-    } else {
-        if (launch_size_ok(items)) return 1;
-        KScope ks(c, "hits_group_kernel", c->stream);
-        with_key(c->k, [&](auto key) {
-            using W = decltype(key);
-            with_value<2, 4, 8>(gs, [&](auto NF) {
-                COMMET_LAUNCH((hits_group_kernel<W, NF>), dim3((unsigned) ((items + 255) / 256)), dim3(256), 0, c->stream, rs->view(), fg, c->k, max_hits,
-                              d_sel, d_hits, d_walked, al);
-            });
-        });
-    }
+    });
     HIP_OK(hipGetLastError());
     return 0;
 }
 
-// one pass of rs over the filter in slot 0; al.ids != nullptr: over the n_launch (at most) listed reads
-int launch_hits(commet_ctx *c, const commet_readset *rs, int max_hits, const uint64_t *d_sel, uint8_t *d_hits, unsigned long long *d_walked,
-                ActiveList al, uint64_t n_launch)
-{
-    if (rs->n_reads == 0) return 0;
-    if (al.ids && n_launch == 0) return 0;
-    const uint64_t items = al.ids ? n_launch : rs->n_reads;
-    if (hits_wave_ok(c, rs)) {
-        KScope ks(c, "hits_wave_kernel", c->stream);
-        with_key(c->k, [&](auto key) {
-            using W = decltype(key);
-            COMMET_LAUNCH(hits_wave_kernel<W>, dim3((unsigned) hits_wave_blocks<W>(c, items)), dim3(LONG_WG), 0, c->stream, rs->view(), c->view(), c->k,
-                          max_hits, d_sel, d_hits, d_walked, al);
-        });
-    } else {
-        if (launch_size_ok(items)) return 1;
-        KScope ks(c, "hits_kernel", c->stream);
-        with_key(c->k, [&](auto key) {
-            COMMET_LAUNCH(hits_kernel<decltype(key)>, dim3((unsigned) ((items + 255) / 256)), dim3(256), 0, c->stream, rs->view(), c->view(), c->k, max_hits,
-                          d_sel, d_hits, d_walked, al);
-        });
-    }
-    HIP_OK(hipGetLastError());
-    return 0;
-}
-
-// search set s against the g chunk filters in slots 0 .. g - 1 (g == 1: the filter in slot 0, the one-filter kernels).  A pass over
-// few of the set's reads walks their list (sparse_pass; no tags: a saturated read is skipped by the kernel itself)
+// search set s against the g chunk filters in slots 0 .. g - 1.  A pass over few of the set's reads walks their list (sparse_pass;
+// no tags: a saturated read is skipped by the kernel itself)
 int hits_pass(JobRun &j, int s, int g, int gs, int max_hits, uint8_t *d_hits, unsigned long long *d_walked)
 {
     commet_ctx *c = j.c;
@@ -141,9 +79,7 @@ int hits_pass(JobRun &j, int s, int g, int gs, int max_hits, uint8_t *d_hits, un
     if (rs->n_reads && sparse_pass(c, rs, sel_s, j.visited[s]) && build_active_list(c, rs, sel_s, nullptr, j.visited[s], &al))
         al = ActiveList{nullptr, nullptr};         // (no room: the bitmap form)
     c->cur_slot = 0;
-    if (g > 1 ? launch_hits_group(c, rs, g, gs, max_hits, sel_s, d_hits, d_walked, al, j.visited[s])
-              : launch_hits(c, rs, max_hits, sel_s, d_hits, d_walked, al, j.visited[s]))
-        return 1;
+    if (launch_hits(c, rs, g, gs, max_hits, sel_s, d_hits, d_walked, al, j.visited[s])) return 1;
     if (rs->n_reads) ++j.n_search_launches;
     return 0;
 }
@@ -168,25 +104,16 @@ bool profile_wide_ok(const commet_ctx *c, uint64_t n_chunks, int n_search, const
 int launch_hits_wide(commet_ctx *c, const commet_readset *rs, const WidePlan &w, int g, int max_hits, const uint64_t *d_sel, uint8_t *d_hits,
                      unsigned long long *d_walked)
 {
-    if (rs->n_reads == 0) return 0;
-    const uint64_t reads_per_block = 4ull * (64 / w.lpr);
-    const uint64_t blocks = (rs->n_reads + reads_per_block - 1) / reads_per_block;
-    if (blocks >= (1ull << 31)) return fail("search launch too large");
-    const dim3 grid((unsigned) blocks), block(256);
-    KScope ks(c, "hits_wide_kernel", c->stream);
-    auto launch = [&](auto LPR, auto NP) {
-        COMMET_LAUNCH((hits_wide_kernel<LPR, NP>), grid, block, 0, c->stream, rs->view(), c->wide_tables, c->k, max_hits, g, w.nw, w.rw, d_sel, d_hits,
-                      d_walked);
-    };
-    if (w.np == 2) launch(std::integral_constant<int, 64>{}, std::integral_constant<int, 2>{});
-    else with_value<64, 32, 16, 8>(w.lpr, [&](auto LPR) { launch(LPR, std::integral_constant<int, 1>{}); });
-    HIP_OK(hipGetLastError());
-    return 0;
+    return launch_wide(rs->n_reads, w, [&](dim3 grid, auto LPR, auto NP) {
+        KScope ks(c, "hits_wide_kernel", c->stream);
+        COMMET_LAUNCH((hits_wide_kernel<LPR, NP>), grid, dim3(256), 0, c->stream, rs->view(), c->wide_tables, c->k, max_hits, g, w.nw, w.rw, d_sel,
+                      d_hits, d_walked);
+    });
 }
 
-// the profile through the wide rows: the chunk filters of a pass (all of them when the tables fit) built 256 at a time into their
-// columns, then every search set scanned once.  at[s] = where set s's bytes start in c->d_hits.  *taken = false: no room for the
-// tables, nothing was launched and the caller takes the slot loop
+// the profile through the wide rows: the passes of run_wide_passes (job.hpp), every search set scanned once per pass by
+// hits_wide_kernel.  at[s] = where set s's bytes start in c->d_hits.  *taken = false: no room for the tables, nothing was launched
+// and the caller takes the slot loop
 int run_profile_wide(JobRun &j, int max_hits, const std::vector<uint64_t> &at, unsigned long long *d_walked, bool want_times, bool *taken)
 {
     commet_ctx *c = j.c;
@@ -198,34 +125,12 @@ int run_profile_wide(JobRun &j, int max_hits, const std::vector<uint64_t> &at, u
         return 0;
     }
     *taken = true;
-    std::vector<SliceChunk> hc(n_chunks);
-    for (uint64_t i = 0; i < n_chunks; ++i) {
-        const Chunk &ch = j.plan.chunks[i];
-        hc[i].first = ch.first;
-        hc[i].count = ch.n_reads ? ch.last - ch.first + 1 : 0;
-    }
-    if (hipMemcpy(c->d_slice_chunks, hc.data(), n_chunks * sizeof(SliceChunk), hipMemcpyHostToDevice) != hipSuccess)
-        return fail("chunk descriptor upload failed");
+    if (upload_chunk_descriptors(j)) return 1;
     const uint64_t per_pass = wide.chunks_per_pass;
     j.tm.timed = want_times && ((n_chunks + per_pass - 1) / per_pass) * (uint64_t) (j.n_search + 2) <= 16384;
-    for (uint64_t c0 = 0; c0 < n_chunks; c0 += per_pass) {
-        const uint64_t c1 = std::min<uint64_t>(n_chunks, c0 + per_pass);
-        if (j.tm.begin_index()) return 1;
-        for (uint64_t ci = c0; ci < c1; ci += 256) {
-            if (launch_slice_build(c, j.index_rs, j.index_sel(), ci, (int) std::min<uint64_t>(256, c1 - ci), (int) WIDE_GROUP_WORDS, c->wide_tables, wide.rw,
-                                   (uint32_t) ((ci - c0) / 256 * WIDE_GROUP_WORDS)))
-                return 1;
-            j.n_index_launches += 2;
-        }
-        if (j.tm.end_index()) return 1;
-        for (int s = 0; s < j.n_search; ++s) {
-            const commet_readset *rs = j.search_rs[s];
-            if (launch_hits_wide(c, rs, wide, (int) (c1 - c0), max_hits, j.sel_of(s), c->d_hits + at[(size_t) s], d_walked)) return 1;
-            if (rs->n_reads) ++j.n_search_launches;
-            if (j.tm.end_set(s)) return 1;
-        }
-    }
-    return 0;
+    return run_wide_passes(j, wide, [&](int s, uint64_t c0, uint64_t c1) {
+        return launch_hits_wide(c, j.search_rs[s], wide, (int) (c1 - c0), max_hits, j.sel_of(s), c->d_hits + at[(size_t) s], d_walked);
+    });
 }
 
 }  // namespace
@@ -258,24 +163,12 @@ int commet_index_and_profile(commet_ctx *c, const commet_readset *index_rs, cons
     int rc = 0;
     bool wide = false;
     if (profile_wide_ok(c, n_chunks, n_search, search_rs)) rc = run_profile_wide(j, max_hits, at, d_walked, info != nullptr, &wide);
-    // the chunks in groups, as run_slots forms them (no group8_ok condition: the hits kernels keep no masks)
-    int group_cap = (c->k >= 2 && n_chunks >= 2) ? std::max(1, std::min(8, c->chunk_group)) : 1;
-    for (uint64_t ci = 0; ci < n_chunks && !rc && !wide;) {
-        int g = (int) std::min<uint64_t>((uint64_t) group_cap, n_chunks - ci);
-        const int gs = g <= 2 ? 2 : g <= 4 ? 4 : 8;
-        if (g > 1 && ensure_slots(c, g, gs)) {   // not enough memory for the group
-            (void) hipGetLastError();
-            if (g > 4) {                          // eight slots do not fit: groups of four
-                group_cap = 4;
-                continue;
-            }
-            g = 1;                                // one chunk at a time
-            group_cap = 1;
-        }
-        rc = j.tm.begin_index() || build_group(j, ci, g, gs) || j.tm.end_index();
-        for (int s = 0; s < n_search && !rc; ++s) rc = hits_pass(j, s, g, gs, max_hits, c->d_hits + at[(size_t) s], d_walked) || j.tm.end_set(s);
-        ci += (uint64_t) g;
-    }
+    // the job's slot loop with a cap rule of its own (no group8_ok condition: the hits kernels keep no masks)
+    const int group_cap = (c->k >= 2 && n_chunks >= 2) ? std::max(1, std::min(8, c->chunk_group)) : 1;
+    if (!rc && !wide)
+        rc = run_slot_groups(j, group_cap, [&](JobRun &jr, int s, uint64_t, int g, int gs) {
+            return hits_pass(jr, s, g, gs, max_hits, c->d_hits + at[(size_t) s], d_walked);
+        });
     c->cur_slot = 0;
     j.clk.lap(j.ph_launch);
     if (!rc && hipMemcpyAsync(&c->h_counters[0], d_walked, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream) != hipSuccess)

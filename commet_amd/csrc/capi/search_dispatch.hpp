@@ -199,11 +199,39 @@ bool group8_ok(const commet_ctx *c, const commet_readset *rs)
 // 2000 among 100-300) and won every pair from 3000 on (1 % of 3000: 9.55 -> 7.8 ms; ragged 500-5000: 14.0 -> 10.6; one length
 // 5500: 14.1 -> 5.7; ragged 1-10 kb: 22.2 -> 8.0).  Sets of ONE length between 2500 and 5500 were not measured, hence 5000.
 constexpr uint32_t LONG_MIN_MAX_LEN = 5000;
+// option "long_search" for a set: 1 never (also k < 2 and sets without a read), 2 whenever the set has a read, 0 auto — the rule
+// of whoever asks (long_ok here, hits_wave_ok in profile.hpp)
+enum class LongMode { never, always, automatic };
+inline LongMode long_mode(const commet_ctx *c, const commet_readset *rs)
+{
+    if (c->long_search == 1 || c->k < 2 || rs->n_reads == 0) return LongMode::never;
+    return c->long_search == 2 ? LongMode::always : LongMode::automatic;
+}
 bool long_ok(const commet_ctx *c, const commet_readset *rs)
 {
-    if (c->long_search == 1 || c->k < 2 || rs->n_reads == 0) return false;
-    if (c->long_search == 2) return true;
-    return first_hit_windows(c, rs) > MASK_MAX_WIN && rs->max_len >= LONG_MIN_MAX_LEN;
+    const LongMode m = long_mode(c, rs);
+    return m == LongMode::always || (m == LongMode::automatic && first_hit_windows(c, rs) > MASK_MAX_WIN && rs->max_len >= LONG_MIN_MAX_LEN);
+}
+
+// persistent grid of a wave-per-read kernel (LONG_WG threads, four reads in flight per workgroup): the workgroups the device holds
+// at once (4-8 per CU by the instantiation's registers, tools/kernel_resources.py; asked once per instantiation), or fewer when
+// the pass has fewer reads
+template <auto Kernel>
+uint64_t resident_blocks(const commet_ctx *c, uint64_t items)
+{
+    static std::atomic<int> resident{0};
+    int wgs = resident.load(std::memory_order_relaxed);
+    if (!wgs) {
+        int per_cu = 0, cus = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, Kernel, LONG_WG, 0) != hipSuccess ||
+            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess || per_cu < 1 || cus < 1) {
+            (void) hipGetLastError();
+            per_cu = 4, cus = 256;
+        }
+        wgs = per_cu * cus;
+        resident.store(wgs, std::memory_order_relaxed);
+    }
+    return std::min<uint64_t>((items + 3) / 4, (uint64_t) wgs);
 }
 
 // one pass of rs over the g filters in slots 0..g-1: nf == 1 (g == 1): slot 0's own plane A; nf = 2, 4, 8: A planes interleaved with stride nf
@@ -222,33 +250,16 @@ int launch_search_long(commet_ctx *c, const commet_readset *rs, int g, int nf, c
     const FilterGroupView fg = filter_group(c, g, 0, nf > 1);
     const uint64_t items = al.ids ? n_launch : rs->n_reads;
     KScope ks(c, "search_long_kernel", c->stream);
-    // persistent grid: the workgroups the device holds at once (4-8 per CU by the instantiation's registers, tools/kernel_resources.py)
-    auto resident_wgs = [&](std::atomic<int> &resident, auto kernel) {
-        int wgs = resident.load(std::memory_order_relaxed);
-        if (!wgs) {
-            int per_cu = 0, cus = 0;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, LONG_WG, 0) != hipSuccess ||
-                hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess || per_cu < 1 || cus < 1) {
-                (void) hipGetLastError();
-                per_cu = 4, cus = 256;
-            }
-            wgs = per_cu * cus;
-            resident.store(wgs, std::memory_order_relaxed);
-        }
-        return std::min<uint64_t>((items + 3) / 4, (uint64_t) wgs);
-    };
     with_key(c->k, [&](auto key) {
         if (jobs) {
-            static std::atomic<int> resident{0};
-            const uint64_t blocks = resident_wgs(resident, search_long_kernel<decltype(key), 8, false, true>);
+            const uint64_t blocks = resident_blocks<search_long_kernel<decltype(key), 8, false, true>>(c, items);
             COMMET_LAUNCH((search_long_kernel<decltype(key), 8, false, true>), dim3((unsigned) blocks), dim3(LONG_WG), 0, c->stream, rs->view(), fg,
                           c->k, t_eff(c, rs), d_tags, d_counters, cstride, job_mask, job_tag_words);
             return;
         }
         with_value<1, 2, 4, 8>(nf, [&](auto NF) {
             with_value<false, true>(d_probes != nullptr, [&](auto count) {
-                static std::atomic<int> resident{0};
-                const uint64_t blocks = resident_wgs(resident, search_long_kernel<decltype(key), NF, count>);
+                const uint64_t blocks = resident_blocks<search_long_kernel<decltype(key), NF, count>>(c, items);
                 COMMET_LAUNCH((search_long_kernel<decltype(key), NF, count>), dim3((unsigned) blocks), dim3(LONG_WG), 0, c->stream, rs->view(), fg,
                               c->k, t_eff(c, rs), d_sel, d_tags, d_counters, cstride, d_probes, al);
             });
@@ -675,24 +686,30 @@ int ensure_wide_tables(commet_ctx *c, const WidePlan &w)
     return grow_kept(c, c->wide_tables, c->wide_table_words, words, words);   // 1: the caller falls back to the narrow tables
 }
 
+// a launch of 256 threads over n_reads reads in the wide rows (none: nothing to launch): f(grid, LPR, NP) with the plan's lanes per
+// read and 16-byte pieces per lane as constants — the kernels of a call site exist as <64, 2> and <64 | 32 | 16 | 8, 1>
+template <typename F>
+int launch_wide(uint64_t n_reads, const WidePlan &w, F f)
+{
+    if (n_reads == 0) return 0;
+    const uint64_t reads_per_block = 4ull * (64 / w.lpr);
+    const uint64_t blocks = (n_reads + reads_per_block - 1) / reads_per_block;
+    if (blocks >= (1ull << 31)) return fail("search launch too large");
+    const dim3 grid((unsigned) blocks);
+    if (w.np == 2) f(grid, std::integral_constant<int, 64>{}, std::integral_constant<int, 2>{});
+    else with_value<64, 32, 16, 8>(w.lpr, [&](auto LPR) { f(grid, LPR, std::integral_constant<int, 1>{}); });
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
 int launch_search_wide(commet_ctx *c, const commet_readset *rs, const WidePlan &w, int g, const uint64_t *d_sel, uint64_t *d_tags,
                        unsigned long long *d_counters, uint32_t cstride)
 {
-    if (rs->n_reads == 0) return 0;
-    const uint64_t reads_per_block = 4ull * (64 / w.lpr);
-    const uint64_t blocks = (rs->n_reads + reads_per_block - 1) / reads_per_block;
-    if (blocks >= (1ull << 31)) return fail("search launch too large");
-    const dim3 grid((unsigned) blocks), block(256);
-    const int t = t_eff(c, rs);
-    KScope ks(c, "search_wide_kernel", c->stream);
-    auto launch = [&](auto LPR, auto NP) {
-        COMMET_LAUNCH((search_wide_kernel<LPR, NP>), grid, block, 0, c->stream, rs->view(), c->wide_tables, c->k, t, g, w.nw, w.rw, d_sel, d_tags,
-                      d_counters, cstride);
-    };
-    if (w.np == 2) launch(std::integral_constant<int, 64>{}, std::integral_constant<int, 2>{});
-    else with_value<64, 32, 16, 8>(w.lpr, [&](auto LPR) { launch(LPR, std::integral_constant<int, 1>{}); });
-    HIP_OK(hipGetLastError());
-    return 0;
+    return launch_wide(rs->n_reads, w, [&](dim3 grid, auto LPR, auto NP) {
+        KScope ks(c, "search_wide_kernel", c->stream);
+        COMMET_LAUNCH((search_wide_kernel<LPR, NP>), grid, dim3(256), 0, c->stream, rs->view(), c->wide_tables, c->k, t_eff(c, rs), g, w.nw, w.rw, d_sel,
+                      d_tags, d_counters, cstride);
+    });
 }
 
 }  // namespace

@@ -258,7 +258,60 @@ def test_random_scenarios_match_checker(tmp_path, seed):
             assert pos == h.size
 
 
-# ---- 8. the sweep command ---------------------------------------------------------------------------------------------------------------
+# ---- 8. a job and a profile build the same groups --------------------------------------------------------------------------------------
+def test_job_and_profile_build_the_same_groups():
+    """both go through run_slot_groups and run_wide_passes (capi/job.hpp): on one context the job and the profile build the same
+    groups of chunk filters — equal build and interleave launches — and scan every non-empty set once per group or pass"""
+    import commet_amd as commet
+    import hit_profile_wide_sets as ws
+
+    def both(ctx, irs, srs):
+        ctx.set_option("kernel_timing", 1)                    # (the totals start again)
+        _, _, jinfo = ctx.index_and_search(irs, srs)
+        jtimes = ctx.kernel_times()
+        ctx.set_option("kernel_timing", 1)
+        _, pinfo = ctx.index_and_profile(irs, srs, max_hits=4)
+        return jinfo, jtimes, pinfo, ctx.kernel_times()
+
+    # the slot loop: 11 chunks in groups of 1 | 2 + a single chunk | 4, 4, 3 | 8, 3; the second search set is empty
+    k, n_chunks = 25, 11
+    index, search, max_kmer = gs.group_set(k, n_chunks)
+    with commet.Context(k=k, t=2) as ctx:
+        irs = commet.ReadSet.from_files(ctx, [util.to_batch(index)])
+        srs = [commet.ReadSet.from_files(ctx, [util.to_batch(s)]) for s in (search, [], search[:70])]
+        for name, value in (("max_kmer", max_kmer), ("tiled_search", 1), ("slice_mode", 1), ("long_search", 1)):
+            ctx.set_option(name, value)
+        for chunk_group in (1, 2, 4, 8):
+            ctx.set_option("chunk_group", chunk_group)
+            jinfo, jtimes, pinfo, ptimes = both(ctx, irs, srs)
+            groups = gs.groups_of(n_chunks, chunk_group)[0]
+            grouped = n_chunks // chunk_group + (n_chunks % chunk_group >= 2) if chunk_group > 1 else 0   # groups of two chunks or more
+            print(chunk_group, jinfo["index_launches"], jinfo["search_launches"], jtimes.get("interleave_a_kernel"), ptimes.get("interleave_a_kernel"))
+            assert jinfo["n_chunks"] == pinfo["n_chunks"] == n_chunks
+            assert jinfo["index_launches"] == pinfo["index_launches"] == n_chunks
+            assert jtimes.get("interleave_a_kernel", (0, 0))[0] == ptimes.get("interleave_a_kernel", (0, 0))[0] == grouped
+            assert jinfo["search_launches"] == pinfo["search_launches"] == groups * 2, chunk_group
+
+    # the wide rows: 300 chunks, rows capped at one group of 256: two passes
+    k, L, n_chunks, _, _ = ws.ROWS[0]
+    index, queries = ws.row_set(k, L, n_chunks)
+    with commet.Context(k=k, t=2) as ctx:
+        irs = commet.ReadSet.from_files(ctx, [util.to_batch(index)])
+        srs = [commet.ReadSet.from_files(ctx, [util.to_batch(s)]) for s in (queries, queries[:70])]
+        for name, value in (("max_kmer", 1), ("slice_wide", 2), ("profile_wide", 2), ("slice_wide_words", 8)):
+            ctx.set_option(name, value)
+        jinfo, jtimes, pinfo, ptimes = both(ctx, irs, srs)
+        passes = ws.passes_of(jinfo["n_chunks"], 8)[0]
+        print(jinfo["n_chunks"], passes, jtimes["slice_build_kernel"][0], ptimes["slice_build_kernel"][0])
+        assert passes == 2 and jinfo["n_chunks"] == pinfo["n_chunks"]
+        assert "search_wide_kernel" in jtimes and "hits_wide_kernel" in ptimes
+        for name in ("slice_build_kernel", "slice_transpose_kernel"):
+            assert jtimes[name][0] == ptimes[name][0] == passes, name
+        assert jinfo["index_launches"] == pinfo["index_launches"] == 2 * passes
+        assert jinfo["search_launches"] == pinfo["search_launches"] == passes * 2
+
+
+# ---- 9. the sweep command ---------------------------------------------------------------------------------------------------------------
 def test_sweep_chunk_group_writes_the_same_vectors(tmp_path):
     d = tmp_path
     os.makedirs(d / "ABCDE_bench")
