@@ -75,6 +75,38 @@ def device_alloc_stats(device=-1):
     return {"wait_ms": float(ms.value), "fresh_bytes": int(by.value), "calls": int(n.value)}
 
 
+def device_alloc_refuse(at_least=0, nth=0):
+    """commet_device_alloc_refuse (test hook): from now on the library's device allocations of `at_least` bytes or more are refused,
+    and the `nth` one from now on once, as by a full device; restarts the numbers of device_alloc_requests.  (0, 0) disarms"""
+    _l.load().commet_device_alloc_refuse(int(at_least), int(nth))
+
+
+def device_alloc_requests():
+    """commet_device_alloc_requests: {"requests", "refused", "last_refused_bytes"} since the last device_alloc_refuse call"""
+    n, r, b = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+    _l.load().commet_device_alloc_requests(C.byref(n), C.byref(r), C.byref(b))
+    return {"requests": int(n.value), "refused": int(r.value), "last_refused_bytes": int(b.value)}
+
+
+class refusing_device_allocs:
+    """with refusing_device_allocs(at_least=..., nth=...) as r: ... — armed inside, always disarmed on exit; r.requests() reads the
+    numbers while armed, r.seen holds them as they were at exit"""
+
+    def __init__(self, at_least=0, nth=0):
+        self.at_least, self.nth, self.seen = int(at_least), int(nth), None
+
+    def requests(self):
+        return device_alloc_requests()
+
+    def __enter__(self):
+        device_alloc_refuse(self.at_least, self.nth)
+        return self
+
+    def __exit__(self, *a):
+        self.seen = device_alloc_requests()
+        device_alloc_refuse(0, 0)
+
+
 def files_packed_bytes(paths):
     """commet_files_packed_bytes: (reads, bases, packed_bytes) of the set ReadSet.from_fasta would make of these files, counted on the
     host — what a residency planner needs before any set is parsed"""

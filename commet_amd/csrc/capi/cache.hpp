@@ -145,6 +145,20 @@ int commet_device_alloc_stats(int device, double *wait_ms, uint64_t *fresh_bytes
     return 0;
 }
 
+void commet_device_alloc_refuse(uint64_t at_least_bytes, uint64_t nth)
+{
+    g_devmem.refuse_at_least = 0, g_devmem.refuse_nth = 0;       // (nothing is refused while the numbers restart)
+    g_devmem.requests = 0, g_devmem.refused = 0, g_devmem.last_refused_bytes = 0;
+    g_devmem.refuse_at_least = at_least_bytes, g_devmem.refuse_nth = nth;
+}
+
+void commet_device_alloc_requests(uint64_t *requests, uint64_t *refused, uint64_t *last_refused_bytes)
+{
+    if (requests) *requests = g_devmem.requests.load();
+    if (refused) *refused = g_devmem.refused.load();
+    if (last_refused_bytes) *last_refused_bytes = g_devmem.last_refused_bytes.load();
+}
+
 int commet_cache_stats(commet_ctx *c, uint64_t *bytes, uint64_t *budget_bytes, uint64_t *evictions)
 {
     std::lock_guard<std::mutex> lk(c->ql_mu);

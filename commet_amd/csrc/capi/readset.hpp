@@ -101,11 +101,12 @@ int commet_readset_stage_acquire(commet_readset *rs, uint8_t **bases, uint64_t *
     if (rs->acquired) return fail("staging buffer already acquired");
     HIP_OK(hipSetDevice(rs->ctx->device));
     commet_readset::Stage &s = rs->st[rs->cur];
-    if (!s.h_bases) {   // staging buffers are created on first use (commet_readset_from_fasta has its own)
-        HIP_OK(hipHostMalloc((void **) &s.h_bases, rs->stage_bases));
-        HIP_OK(hipHostMalloc((void **) &s.h_offs, (rs->stage_reads + 1) * sizeof(uint64_t)));
-        HIP_OK(dm_malloc((void **) &s.d_bases, rs->stage_bases));
-        HIP_OK(dm_malloc((void **) &s.d_offs, (rs->stage_reads + 1) * sizeof(uint64_t)));
+    if (!s.done) {   // staging buffers are created on first use (commet_readset_from_fasta has its own); the event last: a call that
+                     // found no room for one of them leaves the rest to the next call, which never meets a half-made stage
+        if (!s.h_bases) HIP_OK(hipHostMalloc((void **) &s.h_bases, rs->stage_bases));
+        if (!s.h_offs) HIP_OK(hipHostMalloc((void **) &s.h_offs, (rs->stage_reads + 1) * sizeof(uint64_t)));
+        if (!s.d_bases) HIP_OK(dm_malloc((void **) &s.d_bases, rs->stage_bases));
+        if (!s.d_offs) HIP_OK(dm_malloc((void **) &s.d_offs, (rs->stage_reads + 1) * sizeof(uint64_t)));
         HIP_OK(hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
     }
     if (s.inflight) {

@@ -94,6 +94,10 @@ struct DevMemCache {
     // hipMallocAsync, bytes and calls — a box that charges for a process's first use of device memory shows here, not in kernel time
     std::atomic<uint64_t> drv_ns[16], drv_bytes[16], drv_calls[16];
     std::atomic<uint64_t> trims{0};                                // times filed blocks went back to the driver (dm_trim): what was set aside before is gone
+    // test hook (commet_device_alloc_refuse; off = 0, 0): dm_malloc refuses a request of refuse_at_least bytes or more, and the
+    // refuse_nth request since arming (once), as the driver does when it is out of memory; what dm_malloc saw since arming
+    std::atomic<uint64_t> refuse_at_least{0}, refuse_nth{0};
+    std::atomic<uint64_t> requests{0}, refused{0}, last_refused_bytes{0};
     DevMemCache()
     {
         for (int d = 0; d < 16; ++d) drv_ns[d] = 0, drv_bytes[d] = 0, drv_calls[d] = 0;
@@ -243,6 +247,15 @@ inline size_t dm_size_class(size_t bytes)
 hipError_t dm_malloc(void **p, size_t bytes, bool shareable = false)
 {
     *p = nullptr;
+    {   // the refusal hook: the caller's byte count, before anything else; a refusal touches nothing but the hook's own numbers
+        const uint64_t n = g_devmem.requests.fetch_add(1, std::memory_order_relaxed) + 1;
+        const uint64_t at_least = g_devmem.refuse_at_least.load(std::memory_order_relaxed), nth = g_devmem.refuse_nth.load(std::memory_order_relaxed);
+        if ((at_least && bytes >= at_least) || (nth && n == nth)) {
+            g_devmem.refused.fetch_add(1, std::memory_order_relaxed);
+            g_devmem.last_refused_bytes.store(bytes, std::memory_order_relaxed);
+            return hipErrorOutOfMemory;
+        }
+    }
     if (g_devmem.enabled()) bytes = dm_size_class(bytes);
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return hipMalloc(p, bytes);

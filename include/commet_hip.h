@@ -211,6 +211,15 @@ uint64_t        commet_device_pooled_bytes(int device);
  * HERE and not in any kernel's time; the N x N driver reports the difference over a matrix leg as alloc_wait_ms / fresh_device_bytes.
  * Nothing in the reference corresponds to it. */
 int             commet_device_alloc_stats(int device, double *wait_ms, uint64_t *fresh_bytes, uint64_t *calls);
+/* Test hooks, off by default: the library's device allocations refused on request, as the driver refuses them when the device is
+ * full (hipErrorOutOfMemory, before the device cache or the driver is asked), so that every no-room fallback can be run on small
+ * shapes.  Process-wide.  at_least_bytes: every request of that many bytes or more is refused while armed (0 = off); nth: the nth
+ * request from this call on is refused, once (1 = the next one, 0 = off) — the retry that follows it is request nth + 1 and goes
+ * through.  Arming restarts the numbers that commet_device_alloc_requests reports: requests seen, requests refused, the byte count
+ * of the last one refused (each may be NULL).  (0, 0) disarms.  Pinned host memory and blocks set aside ahead of time
+ * (commet_readset_reserve_cache) are not refused. */
+void            commet_device_alloc_refuse(uint64_t at_least_bytes, uint64_t nth);
+void            commet_device_alloc_requests(uint64_t *requests, uint64_t *refused, uint64_t *last_refused_bytes);
 
 /* ---- the two kernels ------------------------------------------------------ */
 /* Replaces `new BloomFilter` per chunk (index_and_search.cpp:256-262,
