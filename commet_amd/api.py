@@ -245,7 +245,12 @@ class Context:
         set_option("profile_wide", 2) takes the wide bit-sliced rows instead where 12 <= k <= 24 (jobs of many small chunks: every chunk
         filter of a pass side by side in one table set, one hits_wide_kernel launch per search set and pass; "slice_wide_words" caps the
         rows); 1 = never; 0 = auto: jobs of more than 256 chunk filters whose search sets hold no read of more than 300 bases (the shape it
-        was measured faster at).  The bytes do not depend on it either."""
+        was measured faster at).  The bytes do not depend on it either.
+        set_option("profile_tiled", 2) sends every pass of one or two chunk filters over a set with 25 <= k <= 34 and at most 255 windows per
+        read through the tiled probe (tq_probe_kernel, then tq_hits_replay_kernel) on the set's query list of (k, t = 1), which is cached with
+        the set (ReadSet.cache_bytes counts it; the search's own list on a context of t = 1); 1 = never; 0 = auto: sets of 2^20 reads or more whose list (8 bytes per k-mer, estimated)
+        stays within "query_list_max_mb".
+        Independent of "tiled_search"; the bytes do not depend on it."""
         ns = len(search_sets)
         isel = _as_bits(index_select, index_rs.num_reads, "index_select")
         ssel = [None] * ns
@@ -385,7 +390,7 @@ class ReadSet:
 
     @property
     def cache_bytes(self):
-        """HBM held by data derived from the set and cached with it (the tiled search's query list)"""
+        """HBM held by data derived from the set and cached with it (the tiled search's query list and, beside it, the tiled hit profile's)"""
         return int(self._lib.commet_readset_cache_bytes(self._h))
 
     def drop_cache(self):

@@ -3,28 +3,38 @@
 #pragma once
 
 namespace {
-// drops one set's query list (caller holds ql_mu); hipFree waits for the kernels that read it
-void drop_query_list(commet_ctx *c, const commet_readset *rs)
+// drops one query list of a set (caller holds ql_mu); hipFree waits for the kernels that read it
+void drop_query_list(commet_ctx *c, commet_readset::QueryList &ql)
 {
-    if (!rs->ql.built && !rs->ql.bytes) return;
-    c->ql_bytes -= std::min(c->ql_bytes, rs->ql.bytes);
-    rs->ql.release();
+    if (!ql.built && !ql.bytes) return;
+    c->ql_bytes -= std::min(c->ql_bytes, ql.bytes);
+    ql.release();
     ++c->ql_evictions;
 }
+// both lists of a set: the search's (ql) and the profile's (pl)
+void drop_query_list(commet_ctx *c, const commet_readset *rs)
+{
+    drop_query_list(c, rs->ql);
+    drop_query_list(c, rs->pl);
+}
 
-// gives cached query lists back until at most `target` bytes of them are left: least recently used first, never a list
+// gives cached query lists back until at most `target` bytes of them are left: least recently used first — judged list by
+// list, a set's search list and its profile list apart —, never a list
 // of the running job unless `even_in_job` (the job thread itself is out of memory and holds no list between build and
 // launch).  Returns the bytes released.  Caller holds ql_mu.
 uint64_t shrink_query_lists(commet_ctx *c, uint64_t target, bool even_in_job)
 {
     uint64_t freed = 0;
     while (c->ql_bytes > target) {
-        const commet_readset *victim = nullptr;
-        for (const commet_readset *rs : c->sets)
-            if (rs->ql.built && (even_in_job || !rs->in_job) && (!victim || rs->ql.last_use < victim->ql.last_use)) victim = rs;
+        commet_readset::QueryList *victim = nullptr;
+        for (const commet_readset *rs : c->sets) {
+            if (!even_in_job && rs->in_job) continue;
+            for (commet_readset::QueryList *l : {&rs->ql, &rs->pl})
+                if (l->built && (!victim || l->last_use < victim->last_use)) victim = l;
+        }
         if (!victim) break;
-        freed += victim->ql.bytes;
-        drop_query_list(c, victim);
+        freed += victim->bytes;
+        drop_query_list(c, *victim);
     }
     return freed;
 }
@@ -104,7 +114,7 @@ extern "C" {
 uint64_t commet_readset_cache_bytes(const commet_readset *rs)
 {
     std::lock_guard<std::mutex> lk(rs->ctx->ql_mu);
-    return rs->ql.built ? rs->ql.bytes : 0;
+    return (rs->ql.built ? rs->ql.bytes : 0) + (rs->pl.built ? rs->pl.bytes : 0);
 }
 
 void commet_readset_drop_cache(commet_readset *rs)
@@ -114,7 +124,7 @@ void commet_readset_drop_cache(commet_readset *rs)
     std::lock_guard<std::mutex> lk(c->ql_mu);
     if (rs->in_job) return;                              // (never under a running job)
     drop_query_list(c, rs);
-    rs->ql.failed = false;                               // a list that did not fit once may fit now
+    rs->ql.failed = rs->pl.failed = false;               // a list that did not fit once may fit now
 }
 
 uint64_t commet_device_cache_trim(int device)

@@ -142,7 +142,7 @@ int try_tiled(commet_ctx *c, const commet_readset *rs, int g, int slot0, const u
               uint32_t cstride, uint64_t job_tag_words = 0)
 {
     std::lock_guard<std::mutex> qlk(c->ql_mu);
-    if (!tiled_ok(c, rs, g) || build_query_list(c, rs) != 0 || ensure_query_results(c, rs) != 0) return 1;
+    if (!tiled_ok(c, rs, g) || build_query_list(c, rs, t_eff(c, rs), rs->ql) != 0 || ensure_query_results(c, rs->ql) != 0) return 1;
     return launch_search_tiled(c, rs, g, slot0, d_sel, d_tags, d_counters, cstride, job_tag_words) ? 2 : 0;
 }
 

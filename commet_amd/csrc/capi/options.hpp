@@ -45,6 +45,11 @@ int commet_set_option(commet_ctx *c, const char *name, int64_t value)
         c->tiled_mode = (int) value;
         return 0;
     }
+    if (!strcmp(name, "profile_tiled")) {     // commet_index_and_profile through the tiled probe: 0 auto (sets of 2^20 reads and more whose list stays within query_list_max_mb), 1 never, 2 whenever the set's geometry allows it (25 <= k <= 34, at most 255 windows per read; capi/profile.hpp)
+        if (value < 0 || value > 2) return fail("profile_tiled must be 0, 1 or 2");
+        c->profile_tiled = (int) value;
+        return 0;
+    }
     if (!strcmp(name, "multi_job")) {         // 0 = commet_index_many_and_search puts the chunk filters of several jobs into one pass where it can, 1 = job by job, 2 = as 0, and search sets of long reads share passes too (capi/multi.hpp)
         if (value < 0 || value > 2) return fail("multi_job must be 0, 1 or 2");
         c->multi_job = (int) value;

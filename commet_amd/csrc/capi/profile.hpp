@@ -19,8 +19,15 @@
 // are, and ONE hits_wide_kernel launch per search set and pass; several passes when the rows are capped ("slice_wide_words")
 // or the table budget is small, folded by the byte array's max.  No room for the tables: the slot loop.  0 = auto (profile_wide_ok
 // below: more than 256 chunks and short reads, as measured); 1 = never.
-// Not done here: profiles through the narrow bit-sliced tables or the tiled probe, and a profile form of commet_index_many_and_search
-// (each a pass function for one of the two shared loops).
+//
+// Large sets at 25 <= k <= 34: option "profile_tiled" = 2 sends a pass of one or two filters through the tiled probe (try_hits_tiled
+// below; hit_profile_tiled.hpp): tq_probe_kernel over the set's query list of (k, t = 1) — every complete window of every read; the
+// set's own list when the context's t is 1, else a second list kept with the set (commet_readset::pl) — then tq_hits_replay_kernel,
+// which counts where tq_replay_kernel stops.  Sparse passes, wave-per-read sets, groups of three filters and more, and sets with no
+// room for the list or the result bytes run what they ran before.  0 = auto: sets of 2^20 reads and more whose list stays within
+// query_list_max_mb (profile_tiled_ok below; MEASUREMENTS.md, "Tiled probe"); 1 = never.
+// Not done here: profiles through the narrow bit-sliced tables, and a profile form of commet_index_many_and_search (each a pass
+// function for one of the two shared loops).
 #pragma once
 
 namespace {
@@ -68,17 +75,120 @@ int launch_hits(commet_ctx *c, const commet_readset *rs, int g, int gs, int max_
     return 0;
 }
 
-// search set s against the g chunk filters in slots 0 .. g - 1.  A pass over few of the set's reads walks their list (sparse_pass;
-// no tags: a saturated read is skipped by the kernel itself)
+// ---- the tiled profile (hit_profile_tiled.hpp) ------------------------------------------------------------------------------------
+// windows of the set's longest read (< 1: the set has no k-mer)
+inline int64_t profile_windows(const commet_ctx *c, const commet_readset *rs) { return (int64_t) rs->max_len - c->k + 1; }
+
+// an upper bound on the records of the set's (k, 1) list — exactly its complete k-mers: every window of every read, and no more
+// windows than bases
+inline uint64_t profile_records_bound(const commet_ctx *c, const commet_readset *rs)
+{
+    const int64_t w = profile_windows(c, rs);
+    if (w < 1 || !rs->n_reads) return 0;
+    const uint64_t by_reads = rs->n_reads * (uint64_t) w;
+    return rs->uniform_len ? by_reads : std::min<uint64_t>(by_reads, rs->n_bases);
+}
+
+// what tq_hits_replay_kernel and the (k, 1) list can take: tiled_geometry_ok (search_dispatch.hpp) with t = 1
+bool profile_geometry_ok(const commet_ctx *c, const commet_readset *rs)
+{
+    if (c->k <= TQ_SLICE_BITS || c->k > TQ_MAX_K) return false;
+    const int64_t w = profile_windows(c, rs);
+    if (w < 1 || w > TQ_MAX_WIN) return false;
+    if (rs->max_len >= TQ_MAX_LEN) return false;
+    if (rs->n_reads >= (1ull << 32)) return false;
+    return profile_records_bound(c, rs) < (1ull << 32);  // record numbers are 32 bits (build_query_list checks the exact count again)
+}
+
+// the list a profile scans: every complete window, t = 1 — the search's own list when that is built for t = 1
+inline commet_readset::QueryList &profile_list(const commet_ctx *c, const commet_readset *rs) { return t_eff(c, rs) == 1 ? rs->ql : rs->pl; }
+
+// mask words of the replay, by the thresholds of mask_words (search_dispatch.hpp)
+inline int profile_mask_words(const commet_ctx *c, const commet_readset *rs)
+{
+    const int64_t w = profile_windows(c, rs);
+    return w <= 64 ? 2 : w <= 96 ? 3 : w <= 128 ? 4 : w <= 192 ? 6 : 8;
+}
+
+// does a pass of g filters over rs take the tiled profile?  Option "profile_tiled": 1 never; 2 whenever the geometry allows; 0 auto: by
+// tiled_ok's auto bounds (search_dispatch.hpp) — sets of 2^20 reads and more whose (k, 1) list, estimated at 8 bytes per record,
+// stays within query_list_max_mb.  Measured at 2 x 5 M x 100 bp, k = 32, one filter (MEASUREMENTS.md, "Tiled probe"): 10.8 against
+// 14.2 ms per call with the list cached, rounds within 1.5 %; the call that builds the list takes 2.6 ms longer, so the second call
+// has repaid it.  configs[1]'s sets (10 M reads: 5.5 GB estimated) lie above the default cap and keep the slot loop in auto, though
+// forced they gain as much (23.9 against 30.6 ms): raise query_list_max_mb for them.
+bool profile_tiled_ok(const commet_ctx *c, const commet_readset *rs, int g, bool sparse)
+{
+    if (c->profile_tiled == 1 || c->count_probes || sparse) return false;
+    if (g < 1 || g > 2 || hits_wave_ok(c, rs) || !profile_geometry_ok(c, rs)) return false;
+    if (profile_list(c, rs).failed) return false;
+    if (c->profile_tiled == 2) return true;              // (forced: sets below auto's 2^20 reads too)
+    return rs->n_reads >= (1ull << 20) && profile_records_bound(c, rs) * 8 <= c->ql_max_list;
+}
+
+// probe and counting replay of rs over the g <= 2 filters in slots 0 .. g - 1 (g == 2: interleaved A planes), its list and result bytes in place
+int launch_hits_tiled(commet_ctx *c, const commet_readset *rs, const commet_readset::QueryList &q, int g, int max_hits, const uint64_t *d_sel,
+                      uint8_t *d_hits, unsigned long long *d_walked)
+{
+    if (rs->n_reads == 0) return 0;
+    if (c->qres_cap < q.n_records) return fail("internal error: tiled profile without its result buffer");
+    QueryListView v;
+    v.tile_off = q.d_tile_off, v.qaddr = q.d_qaddr, v.qwho = q.d_qwho, v.tstart = q.d_tstart, v.tlen = q.d_tlen;
+    v.n_slices = q.n_slices, v.n_pieces = q.n_pieces, v.sbits = q.sbits;
+    const FilterGroupView fg = filter_group(c, g, 0, g > 1);
+    {
+        KScope ks(c, "tq_probe_kernel", c->stream);
+        with_value<1, 2>(g, [&](auto GS) {
+            COMMET_LAUNCH(tq_probe_kernel<GS>, dim3(8 * TQ_PROBE_WGS_PER_XCD), dim3(256), 0, c->stream, v, fg.il_a, c->d_qres, 0u, q.n_pieces);
+        });
+    }
+    HIP_OK(hipGetLastError());
+    {
+        KScope ks(c, "tq_hits_replay_kernel", c->stream);
+        const uint32_t hit_cap = (uint32_t) std::min<int>(c->tq_hit_cap, TQ_HIT_CAP);
+        const int mw = profile_mask_words(c, rs);
+        with_key(c->k, [&](auto key) {
+            with_value<1, 2>(g, [&](auto GS) {
+                with_mask_words(mw, [&](auto MW) {
+                    COMMET_LAUNCH((tq_hits_replay_kernel<decltype(key), GS, MW>), dim3(q.n_pieces), dim3(TQ_PIECE), 0, c->stream, rs->view(), v, c->d_qres,
+                                  fg, c->k, max_hits, d_sel, d_hits, d_walked, hit_cap);
+                });
+            });
+        });
+    }
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+// 0 = launched, 1 = not for this set / group (or no room: the caller's kernels), 2 = error.  List, result bytes and launches under
+// ql_mu, as try_tiled (job_parts.hpp): no other thread gives the list back in between
+int try_hits_tiled(commet_ctx *c, const commet_readset *rs, int g, bool sparse, int max_hits, const uint64_t *d_sel, uint8_t *d_hits,
+                   unsigned long long *d_walked)
+{
+    std::lock_guard<std::mutex> qlk(c->ql_mu);
+    if (!profile_tiled_ok(c, rs, g, sparse)) return 1;
+    commet_readset::QueryList &l = profile_list(c, rs);
+    if (build_query_list(c, rs, 1, l) != 0 || ensure_query_results(c, l) != 0) return 1;
+    return launch_hits_tiled(c, rs, l, g, max_hits, d_sel, d_hits, d_walked) ? 2 : 0;
+}
+
+// search set s against the g chunk filters in slots 0 .. g - 1: the tiled profile where it applies; else the gather kernels, a pass
+// over few of the set's reads walking their list (sparse_pass; no tags: a saturated read is skipped by the kernel itself)
 int hits_pass(JobRun &j, int s, int g, int gs, int max_hits, uint8_t *d_hits, unsigned long long *d_walked)
 {
     commet_ctx *c = j.c;
     const commet_readset *rs = j.search_rs[s];
     const uint64_t *sel_s = j.sel_of(s);
-    ActiveList al{nullptr, nullptr};
-    if (rs->n_reads && sparse_pass(c, rs, sel_s, j.visited[s]) && build_active_list(c, rs, sel_s, nullptr, j.visited[s], &al))
-        al = ActiveList{nullptr, nullptr};         // (no room: the bitmap form)
+    const bool sparse = rs->n_reads && sparse_pass(c, rs, sel_s, j.visited[s]);
     c->cur_slot = 0;
+    const int tiled = try_hits_tiled(c, rs, g, sparse, max_hits, sel_s, d_hits, d_walked);
+    if (tiled == 2) return 1;
+    if (tiled == 0) {
+        if (rs->n_reads) ++j.n_search_launches;
+        return 0;
+    }
+    ActiveList al{nullptr, nullptr};
+    if (sparse && build_active_list(c, rs, sel_s, nullptr, j.visited[s], &al))
+        al = ActiveList{nullptr, nullptr};         // (no room: the bitmap form)
     if (launch_hits(c, rs, g, gs, max_hits, sel_s, d_hits, d_walked, al, j.visited[s])) return 1;
     if (rs->n_reads) ++j.n_search_launches;
     return 0;

@@ -62,6 +62,7 @@ void commet_readset_destroy(commet_readset *rs)
         commet_ctx *c = rs->ctx;
         std::lock_guard<std::mutex> lk(c->ql_mu);
         c->ql_bytes -= std::min(c->ql_bytes, rs->ql.bytes);
+        c->ql_bytes -= std::min(c->ql_bytes, rs->pl.bytes);
         c->sets.erase(std::remove(c->sets.begin(), c->sets.end(), rs), c->sets.end());
     }
     (void) dm_free(rs->d_planes);
@@ -73,6 +74,7 @@ void commet_readset_destroy(commet_readset *rs)
     (void) dm_free(rs->d_found);
     (void) dm_free(rs->d_filter_ws);
     rs->ql.release();
+    rs->pl.release();
     (void) dm_free(rs->d_len_order);
     free(rs->h_away);
     for (int i = 0; i < 2; ++i) {

@@ -129,7 +129,7 @@ int commet_readset_offload(commet_readset *rs)
     if (!rs) return fail("null read set");
     commet_ctx *c = rs->ctx;
     if (!rs->finalized) return fail("read set not finalized");
-    commet_readset::QueryList list;                        // what is derived from the set leaves with it (freed outside the mutex)
+    commet_readset::QueryList list, plist;                 // what is derived from the set leaves with it (freed outside the mutex)
     uint32_t *len_order = nullptr;
     {
         // the check and the change in one critical section: a job that enters later (SetUse) finds the set offloaded
@@ -143,7 +143,12 @@ int commet_readset_offload(commet_readset *rs)
             list = rs->ql;
             rs->ql = commet_readset::QueryList();
         }
-        rs->ql.failed = false;
+        if (rs->pl.built || rs->pl.bytes) {
+            c->ql_bytes -= std::min(c->ql_bytes, rs->pl.bytes);
+            plist = rs->pl;
+            rs->pl = commet_readset::QueryList();
+        }
+        rs->ql.failed = rs->pl.failed = false;
         len_order = rs->d_len_order;
         rs->d_len_order = nullptr, rs->len_order_failed = false, rs->n_len_seg = 0;
         rs->ql_reserved.store(false);
@@ -154,6 +159,7 @@ int commet_readset_offload(commet_readset *rs)
     };
     hipError_t e = hipSetDevice(c->device);
     list.release();
+    plist.release();
     (void) dm_free(len_order);
     (void) dm_free(rs->d_filter_ws);
     rs->d_filter_ws = nullptr, rs->filter_ws_bytes = 0;

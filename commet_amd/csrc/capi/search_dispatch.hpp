@@ -416,10 +416,10 @@ bool tiled_ok(const commet_ctx *c, const commet_readset *rs, int g)
     return true;
 }
 
-// the set's query list for this context's (k, t): counted, scanned, filled; kept with the set
-int build_query_list(commet_ctx *c, const commet_readset *rs)
+// a query list of the set for (the context's k, t): counted, scanned, filled; kept with the set in `ql` — rs->ql for the search
+// (t = t_eff), rs->pl for the tiled hit profile (t = 1; rs->ql itself where t_eff is 1: profile_list, capi/profile.hpp)
+int build_query_list(commet_ctx *c, const commet_readset *rs, int t, commet_readset::QueryList &ql)
 {
-    commet_readset::QueryList &ql = rs->ql;
     if (ql.built) {
         ql.last_use = ++c->ql_clock;
         return 0;
@@ -441,7 +441,6 @@ int build_query_list(commet_ctx *c, const commet_readset *rs)
     if (e == hipSuccess && grow_kept(c, c->d_ql_totals, c->ql_totals_cap, (uint64_t) nb + 1, (uint64_t) nb + 1, true)) e = hipErrorOutOfMemory;
     unsigned long long *const d_totals = c->d_ql_totals;
     if (e == hipSuccess) {
-        const int t = t_eff(c, rs);
         const size_t lds = (size_t) ql.n_slices * 4;
         {
             KScope ks(c, "tq_count_kernel", ls);
@@ -474,7 +473,7 @@ int build_query_list(commet_ctx *c, const commet_readset *rs)
         }
         if (e == hipSuccess) {
             // reads sorted per round in LDS: as many as keep rpr * (first-hit windows per read) within TQ_FILL_CAP records
-            const int64_t fhw = std::max<int64_t>(1, first_hit_windows(c, rs));
+            const int64_t fhw = std::max<int64_t>(1, (int64_t) rs->max_len - (int64_t) t * c->k + 1);
             // (even rounds: e.g. 256 reads x 87 windows = 22 272 records are three rounds of 86 reads)
             const uint32_t rounds = (uint32_t) (((uint64_t) TQ_PIECE * (uint64_t) fhw + TQ_FILL_CAP - 1) / TQ_FILL_CAP);
             uint32_t rpr = (TQ_PIECE + rounds - 1) / rounds;
@@ -506,13 +505,13 @@ int build_query_list(commet_ctx *c, const commet_readset *rs)
     return 0;
 }
 
-// the scan's result bytes (one per record of the set's query list); no room = this set keeps the gather kernels
-int ensure_query_results(commet_ctx *c, const commet_readset *rs)
+// the scan's result bytes (one per record of the list that is scanned); no room = this set keeps the gather kernels
+int ensure_query_results(commet_ctx *c, commet_readset::QueryList &ql)
 {
-    const uint64_t need = std::max<uint64_t>(rs->ql.n_records, 1);
+    const uint64_t need = std::max<uint64_t>(ql.n_records, 1);
     // (the caller holds ql_mu: the lists of sets outside this job are given back and the allocation tried once more)
     if (grow_kept(c, c->d_qres, c->qres_cap, need, need, true)) {
-        rs->ql.failed = true;
+        ql.failed = true;
         return 1;
     }
     return 0;

@@ -571,6 +571,7 @@ struct commet_ctx {
     unsigned long long *d_lo_cnt = nullptr;   // scratch of that list's counting sort (class-major block counts), kept
     uint64_t lo_cnt_cap = 0;
     int tiled_mode = 0;               // option "tiled_search": 0 auto (large sets, groups of 1 or 2 chunks), 1 never, 2 whenever possible
+    int profile_tiled = 0;            // option "profile_tiled": commet_index_and_profile through the tiled probe (hit_profile_tiled.hpp): 0 auto (sets of 2^20 reads and more whose list stays within query_list_max_mb), 1 never, 2 whenever the set's geometry allows it (capi/profile.hpp)
     // environment knobs, read ONCE in commet_create (nothing on the launch path calls getenv)
     bool job_verbose = false;         // COMMET_JOB_VERBOSE: host-side phase times of every commet_index_and_search call on stderr
     bool ingest_verbose = false;      // COMMET_INGEST_VERBOSE
@@ -670,6 +671,9 @@ struct commet_readset {
         }
     };
     mutable QueryList ql;
+    // ... and the list of the tiled hit profile (hit_profile_tiled.hpp), built with t = 1: every complete window of every read.  When the
+    // context's t_eff is 1 the profile uses `ql` itself; under the same rules as `ql` (accounted, evicted, dropped, offloaded)
+    mutable QueryList pl;
     // the set's reads in order of their first-hit window counts (tile_search.hpp, lo_*_kernel): ragged sets only, made on the first pass
     // of a gather kernel that visits the whole set; ids[n_reads] = n_reads closes the list
     mutable uint32_t *d_len_order = nullptr;

@@ -324,7 +324,12 @@ int commet_index_many_and_search(commet_ctx *ctx, int n_jobs, const commet_reads
  * read's best count so far.  Several passes when "slice_wide_words" caps the rows or the table budget is small, folded by the bytes'
  * max; no room for the tables: the loop above.  search_launches = passes x non-empty search sets; reads_scanned = the reads a pass
  * walked (a read of fewer than k bases, or one already at min(max_hits, len / k), is not walked).  The bytes do not depend on it.
- * Not done here: profiles through the narrow bit-sliced tables or the tiled probe, and a profile form of commet_index_many_and_search. */
+ * Large sets at 25 <= k <= 34, by option "profile_tiled": a pass of one or two chunk filters goes through the tiled probe — tq_probe_kernel
+ * over the set's query list of (k, t = 1), which holds every complete window of every read (the search's own list on a context of
+ * t = 1, else a second list cached with the set under the same rules: commet_readset_cache_bytes counts both), then
+ * tq_hits_replay_kernel, which counts the full hits greedily per filter and strand.  Sparse passes, sets that take long_search, groups
+ * of three filters and more, count_probes, and sets without room for the list run the kernels above.  The bytes do not depend on it.
+ * Not done here: profiles through the narrow bit-sliced tables, and a profile form of commet_index_many_and_search. */
 int commet_index_and_profile(commet_ctx *ctx, const commet_readset *index_rs, const uint8_t *index_select,
                              int n_search, const commet_readset *const *search_rs, const uint8_t *const *search_select,
                              int max_hits, uint8_t *const *hits_out, commet_job_info *info);
@@ -359,6 +364,10 @@ int commet_index_and_profile(commet_ctx *ctx, const commet_readset *index_rs, co
  *   profile_wide (0/1/2) commet_index_and_profile through the wide rows (hits_wide_kernel): 0 = jobs of more than 256 chunks whose
  *                        search sets hold no read of more than 300 bases (measured on 150-base reads), 1 = never (the slot loop,
  *                        launch for launch), 2 = whenever 12 <= k <= 24 and the job has a chunk; slice_wide_words caps its rows too
+ *   profile_tiled (0/1/2) commet_index_and_profile through the tiled probe (tq_hits_replay_kernel): 0 = auto: sets of 2^20 reads or more whose
+ *                        list, estimated at 8 bytes per k-mer, stays within query_list_max_mb (the bounds of tiled_search), 1 = never, 2 = every pass of one or two chunk filters over a set
+ *                        with 25 <= k <= 34, 1..255 windows per read and fewer than 2^32 k-mers (tests; sets below 2^20 reads too);
+ *                        independent of tiled_search; tq_hit_cap applies
  *   query_list_budget_mb HBM the cached query lists of the context's read sets may hold (see commet_readset_cache_bytes)
  *   query_list_max_mb    auto mode of tiled_search: largest list (estimated) a set may get, default 4096 (sets of up to ~15 M reads;
  *                        larger lists — a 50 M-read set's is 11 GB — pay in long-lived contexts only: allocating them costs

@@ -15,6 +15,11 @@ stream synchronise and the copy back) and then runs once more with option kernel
                     when --many-reads is given more than once, on every further read count (2 000 000 reads cross 1 024 chunks), the
                     profile on --jobs-lib (the parent commit's build), at profile_wide = 1 and at profile_wide = 2, fresh child processes
                     alternating over `--rounds`, the three hit arrays byte-compared; one job at t = 5 gives the break-even T
+  --tiled           ONLY the profile_tiled leg, on the configs[1] shape (--reads, --read-len, -k): the profile on --jobs-lib (the parent
+                    commit's build), at profile_tiled = 1 (the slot loop), at profile_tiled = 2 (tq_probe_kernel + tq_hits_replay_kernel) and at the
+                    default (auto),
+                    fresh child processes alternating over `--rounds`, the hit arrays byte-compared; the timed calls find the (k, 1) query
+                    list cached, `first_call` is the warm-up call that builds it (tq_count / tq_fill and the allocation)
   python tools/hits_bench.py [--reads 10000000] [--read-len 100] [-k 32] [--max-t 8] [--rounds 2] [--reps 3] [--out FILE]"""
 import argparse
 import json
@@ -52,9 +57,13 @@ def child_profile(a):
             ctx.set_option("chunk_group", a.chunk_group)
         if a.profile_wide:
             ctx.set_option("profile_wide", a.profile_wide)
+        if a.profile_tiled:
+            ctx.set_option("profile_tiled", a.profile_tiled)
         irs = commet_amd.ReadSet.from_files(ctx, [(b0, o0)])
         qrs = commet_amd.ReadSet.from_files(ctx, [(b1, o1)])
-        ctx.index_and_profile(irs, [qrs], max_hits=a.max_t)                      # warm-up
+        _, first = ctx.index_and_profile(irs, [qrs], max_hits=a.max_t)           # warm-up (workspaces; the tiled leg's query list)
+        out["first_call"] = {f: round(first[f], 3) for f in ("total_ms", "index_ms", "search_ms")}
+        out["cache_bytes"] = int(qrs.cache_bytes)
         calls = []
         for _ in range(a.reps):
             hits, info = ctx.index_and_profile(irs, [qrs], max_hits=a.max_t)
@@ -140,6 +149,8 @@ def groups_leg(a, tag, lib_args, legs=None):
         per = {f: [med(c[f]) for c in runs[name]] for f in ("total_ms", "index_ms", "search_ms")}
         out[name] = {f: round(med(v), 3) for f, v in per.items()}
         out[name]["total_ms_spread"] = round((max(per["total_ms"]) - min(per["total_ms"])) / med(per["total_ms"]), 4)
+        out[name]["first_call_total_ms"] = round(med([c["first_call"]["total_ms"] for c in runs[name]]), 3)
+        out[name]["cache_bytes"] = runs[name][0].get("cache_bytes")
         out[name].update(reads_walked=runs[name][0]["reads_walked"], search_launches=runs[name][0].get("search_launches"), chunks=runs[name][0]["chunks"],
                          kernels_ms=runs[name][0]["kernels_ms"])
     return out
@@ -160,6 +171,8 @@ def main():
     ap.add_argument("--hits-name", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--wide", action="store_true")
     ap.add_argument("--profile-wide", type=int, default=0, help=argparse.SUPPRESS)
+    ap.add_argument("--tiled", action="store_true")
+    ap.add_argument("--profile-tiled", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--many-reads", type=int, nargs="+", default=[600_000])
     ap.add_argument("--limit", type=int, default=240, help="seconds a child may take")
     ap.add_argument("--out", default=None)
@@ -206,6 +219,17 @@ def main():
                 open(a.out, "w").write(json.dumps(res) + "\n")
             return
         a.many_reads = a.many_reads[0]
+        if a.tiled:
+            legs = ([("parent", lib_args)] if lib_args else []) + [("tiled1", ["--profile-tiled", "1"]), ("tiled2", ["--profile-tiled", "2"]), ("auto", [])]
+            t = groups_leg(a, "c1", lib_args, legs)
+            res = {"workload": res["workload"], "tiled": t}
+            if a.out:
+                os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+                open(a.out, "w").write(json.dumps(res) + "\n")
+            print(json.dumps({"workload": res["workload"], "hits_equal": t["hits_equal"],
+                              **{name: {f: t[name][f] for f in ("total_ms", "index_ms", "search_ms", "total_ms_spread", "first_call_total_ms", "cache_bytes",
+                                                                "search_launches", "reads_walked", "kernels_ms")} for name, _ in legs}}), flush=True)
+            return
         if a.groups:
             res = {"workload": res["workload"], "groups": groups_leg(a, "c1", lib_args)}
             if a.many_chunks:
