@@ -89,26 +89,14 @@ inline uint64_t profile_records_bound(const commet_ctx *c, const commet_readset 
     return rs->uniform_len ? by_reads : std::min<uint64_t>(by_reads, rs->n_bases);
 }
 
-// what tq_hits_replay_kernel and the (k, 1) list can take: tiled_geometry_ok (search_dispatch.hpp) with t = 1
+// what tq_hits_replay_kernel and the (k, 1) list can take
 bool profile_geometry_ok(const commet_ctx *c, const commet_readset *rs)
 {
-    if (c->k <= TQ_SLICE_BITS || c->k > TQ_MAX_K) return false;
-    const int64_t w = profile_windows(c, rs);
-    if (w < 1 || w > TQ_MAX_WIN) return false;
-    if (rs->max_len >= TQ_MAX_LEN) return false;
-    if (rs->n_reads >= (1ull << 32)) return false;
-    return profile_records_bound(c, rs) < (1ull << 32);  // record numbers are 32 bits (build_query_list checks the exact count again)
+    return tq_geometry_ok(c, rs, profile_windows(c, rs), profile_records_bound(c, rs));
 }
 
 // the list a profile scans: every complete window, t = 1 — the search's own list when that is built for t = 1
 inline commet_readset::QueryList &profile_list(const commet_ctx *c, const commet_readset *rs) { return t_eff(c, rs) == 1 ? rs->ql : rs->pl; }
-
-// mask words of the replay, by the thresholds of mask_words (search_dispatch.hpp)
-inline int profile_mask_words(const commet_ctx *c, const commet_readset *rs)
-{
-    const int64_t w = profile_windows(c, rs);
-    return w <= 64 ? 2 : w <= 96 ? 3 : w <= 128 ? 4 : w <= 192 ? 6 : 8;
-}
 
 // does a pass of g filters over rs take the tiled profile?  Option "profile_tiled": 1 never; 2 whenever the geometry allows; 0 auto: by
 // tiled_ok's auto bounds (search_dispatch.hpp) — sets of 2^20 reads and more whose (k, 1) list, estimated at 8 bytes per record,
@@ -131,32 +119,14 @@ int launch_hits_tiled(commet_ctx *c, const commet_readset *rs, const commet_read
 {
     if (rs->n_reads == 0) return 0;
     if (c->qres_cap < q.n_records) return fail("internal error: tiled profile without its result buffer");
-    QueryListView v;
-    v.tile_off = q.d_tile_off, v.qaddr = q.d_qaddr, v.qwho = q.d_qwho, v.tstart = q.d_tstart, v.tlen = q.d_tlen;
-    v.n_slices = q.n_slices, v.n_pieces = q.n_pieces, v.sbits = q.sbits;
+    const QueryListView v = query_list_view(q);
     const FilterGroupView fg = filter_group(c, g, 0, g > 1);
-    {
-        KScope ks(c, "tq_probe_kernel", c->stream);
-        with_value<1, 2>(g, [&](auto GS) {
-            COMMET_LAUNCH(tq_probe_kernel<GS>, dim3(8 * TQ_PROBE_WGS_PER_XCD), dim3(256), 0, c->stream, v, fg.il_a, c->d_qres, 0u, q.n_pieces);
-        });
-    }
-    HIP_OK(hipGetLastError());
-    {
-        KScope ks(c, "tq_hits_replay_kernel", c->stream);
-        const uint32_t hit_cap = (uint32_t) std::min<int>(c->tq_hit_cap, TQ_HIT_CAP);
-        const int mw = profile_mask_words(c, rs);
-        with_key(c->k, [&](auto key) {
-            with_value<1, 2>(g, [&](auto GS) {
-                with_mask_words(mw, [&](auto MW) {
-                    COMMET_LAUNCH((tq_hits_replay_kernel<decltype(key), GS, MW>), dim3(q.n_pieces), dim3(TQ_PIECE), 0, c->stream, rs->view(), v, c->d_qres,
-                                  fg, c->k, max_hits, d_sel, d_hits, d_walked, hit_cap);
-                });
-            });
-        });
-    }
-    HIP_OK(hipGetLastError());
-    return 0;
+    if (launch_tq_probe(c, v, fg, g)) return 1;
+    // (mask words: by every window of the set's longest read, not its first-hit windows)
+    return launch_tq_replay(c, "tq_hits_replay_kernel", g, mask_words_of(profile_windows(c, rs)), [&](auto key, auto GS, auto MW, uint32_t hit_cap) {
+        COMMET_LAUNCH((tq_hits_replay_kernel<decltype(key), GS, MW>), dim3(q.n_pieces), dim3(TQ_PIECE), 0, c->stream, rs->view(), v, c->d_qres, fg,
+                      c->k, max_hits, d_sel, d_hits, d_walked, hit_cap);
+    });
 }
 
 // 0 = launched, 1 = not for this set / group (or no room: the caller's kernels), 2 = error.  List, result bytes and launches under

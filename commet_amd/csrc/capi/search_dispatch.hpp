@@ -120,11 +120,9 @@ int launch_search_group_t(commet_ctx *c, const commet_readset *rs, const FilterG
 // mask words (32 first-hit windows each) a read of the set needs per strand and filter in the register-mask kernels
 // (search_group8_kernel, tq_replay_kernel): 2, 3, 4, 6 or 8 — reads of up to 318 bases at k = 32, t = 2 (round 6; 96 windows before)
 constexpr int MASK_MAX_WIN = 255;      // (= TQ_MAX_WIN)
-inline int mask_words(const commet_ctx *c, const commet_readset *rs)
-{
-    const int64_t fhw = first_hit_windows(c, rs);
-    return fhw <= 64 ? 2 : fhw <= 96 ? 3 : fhw <= 128 ? 4 : fhw <= 192 ? 6 : 8;
-}
+// the one table of it: mask words for reads of up to `windows` windows (the tiled hit profile asks with every window of the read)
+inline int mask_words_of(int64_t windows) { return windows <= 64 ? 2 : windows <= 96 ? 3 : windows <= 128 ? 4 : windows <= 192 ? 6 : 8; }
+inline int mask_words(const commet_ctx *c, const commet_readset *rs) { return mask_words_of(first_hit_windows(c, rs)); }
 template <typename F>
 decltype(auto) with_mask_words(int mw, F &&f)
 {
@@ -384,18 +382,20 @@ constexpr int TQ_SLICE_BITS = 24;     // slice = 2^24 bits of plane A's address 
 
 constexpr int TQ_MAX_K = 34;          // 64-bit keys from k = 33 (the reference's default k, index_and_search.cpp:71): 2^(k - 24) <= 1024 slices
 
-// what the tiled search's kernels and the query list's layout can take, whatever the mode and the group: the one statement of it for
-// tiled_ok and query_list_blocks
-bool tiled_geometry_ok(const commet_ctx *c, const commet_readset *rs)
+// what the probe, the replay kernels and the query list's layout can take, whatever the mode and the group: the one statement of it.
+// windows: of the list's longest read (< 1: the list is empty); records: an upper bound on the list's records
+bool tq_geometry_ok(const commet_ctx *c, const commet_readset *rs, int64_t windows, uint64_t records)
 {
     if (c->k <= TQ_SLICE_BITS || c->k > TQ_MAX_K) return false;
-    const int64_t fhw = first_hit_windows(c, rs);
-    if (fhw < 1 || fhw > TQ_MAX_WIN) return false;
+    if (windows < 1 || windows > TQ_MAX_WIN) return false;
     if (rs->max_len >= TQ_MAX_LEN) return false;        // (the replay keeps a piece's read extents in 16 + 16 bits; such reads pass the line above only with t in the hundreds)
     if (rs->n_reads >= (1ull << 32)) return false;
-    // (rs->fhw_total: the set's first-hit windows summed over its reads — n x first_hit_windows for reads of one length, less for ragged sets)
-    return rs->fhw_total < (1ull << 32);                // record numbers are 32 bits (forced mode, too)
+    return records < (1ull << 32);                      // record numbers are 32 bits (forced mode, too; build_query_list checks the exact count again)
 }
+
+// the search's list, (k, t_eff): for tiled_ok and query_list_blocks
+// (rs->fhw_total: the set's first-hit windows summed over its reads — n x first_hit_windows for reads of one length, less for ragged sets)
+bool tiled_geometry_ok(const commet_ctx *c, const commet_readset *rs) { return tq_geometry_ok(c, rs, first_hit_windows(c, rs), rs->fhw_total); }
 
 bool tiled_ok(const commet_ctx *c, const commet_readset *rs, int g)
 {
@@ -534,6 +534,47 @@ bool query_list_blocks(const commet_ctx *c, const commet_readset *rs, uint64_t o
 constexpr unsigned TQ_PROBE_WGS_PER_XCD = 64;   // probe workgroups per XCD (a multiple of the 32 CUs of an XCD keeps the sweep even;
                                                 // measured: 32 or 64 (1 or 2 per CU) 2.3-2.6 ms, 128: 3.7, 256: 4.8)
 
+// ---- what the tiled search and the tiled hit profile (capi/profile.hpp) launch alike: the probe over a list, then a replay kernel
+inline QueryListView query_list_view(const commet_readset::QueryList &q)
+{
+    QueryListView v;
+    v.tile_off = q.d_tile_off, v.qaddr = q.d_qaddr, v.qwho = q.d_qwho, v.tstart = q.d_tstart, v.tlen = q.d_tlen;
+    v.n_slices = q.n_slices, v.n_pieces = q.n_pieces, v.sbits = q.sbits;
+    return v;
+}
+
+// the result bytes of the whole list over fg's g <= 2 filters into c->d_qres.
+// The probe is bound by L2 gathers, the replay by L2-MISSING requests and bookkeeping: different walls, but run beside each
+// other (the set cut into runs of pieces, the replay of one beside the probe of the next on a second stream) they contend for
+// the same memory system: measured on configs[1] 19.76 ms per step in one part, 21.8 / 23.2 / 24.6 / 25.3 in 2 / 3 / 4 / 6
+// (r03_parts_*.json).  So the whole set's probe, then its replay, on the job's stream.
+int launch_tq_probe(commet_ctx *c, const QueryListView &v, const FilterGroupView &fg, int g)
+{
+    {
+        KScope ks(c, "tq_probe_kernel", c->stream);
+        with_value<1, 2>(g, [&](auto GS) {
+            COMMET_LAUNCH(tq_probe_kernel<GS>, dim3(8 * TQ_PROBE_WGS_PER_XCD), dim3(256), 0, c->stream, v, fg.il_a, c->d_qres, 0u, v.n_pieces);
+        });
+    }
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+// a replay kernel's build for (k, g filters, mw mask words): launch(key, GS, MW, hit_cap), timed under `name`
+template <typename F>
+int launch_tq_replay(commet_ctx *c, const char *name, int g, int mw, F &&launch)
+{
+    {
+        KScope ks(c, name, c->stream);
+        const uint32_t hit_cap = (uint32_t) std::min<int>(c->tq_hit_cap, TQ_HIT_CAP);
+        with_key(c->k, [&](auto key) {
+            with_value<1, 2>(g, [&](auto GS) { with_mask_words(mw, [&](auto MW) { launch(key, GS, MW, hit_cap); }); });
+        });
+    }
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
 // one pass of rs over the g <= 2 chunk filters in slots slot0 .. slot0 + g - 1 (g == 2: slots 0, 1 with interleaved A planes)
 // job_tag_words != 0 (g == 2): the two filters belong to two jobs; job j's found flags go to d_tags + j * job_tag_words (zeroed by the caller)
 int launch_search_tiled(commet_ctx *c, const commet_readset *rs, int g, int slot0, const uint64_t *d_sel, uint64_t *d_tags,
@@ -542,37 +583,14 @@ int launch_search_tiled(commet_ctx *c, const commet_readset *rs, int g, int slot
     if (rs->n_reads == 0) return 0;
     const commet_readset::QueryList &q = rs->ql;
     if (c->qres_cap < q.n_records) return fail("internal error: tiled search without its result buffer");
-    QueryListView v;
-    v.tile_off = q.d_tile_off, v.qaddr = q.d_qaddr, v.qwho = q.d_qwho, v.tstart = q.d_tstart, v.tlen = q.d_tlen;
-    v.n_slices = q.n_slices, v.n_pieces = q.n_pieces, v.sbits = q.sbits;
+    const QueryListView v = query_list_view(q);
     const FilterGroupView fg = filter_group(c, g, slot0, g > 1);   // one filter: its own plane A (stride 1)
-    // The probe is bound by L2 gathers, the replay by L2-MISSING requests and bookkeeping: different walls, but run beside each
-    // other (the set cut into runs of pieces, the replay of one beside the probe of the next on a second stream) they contend for
-    // the same memory system: measured on configs[1] 19.76 ms per step in one part, 21.8 / 23.2 / 24.6 / 25.3 in 2 / 3 / 4 / 6
-    // (r03_parts_*.json).  So the whole set's probe, then its replay, on the job's stream.
-    const int mw = mask_words(c, rs);
     const int t = t_eff(c, rs);
-    {
-        KScope ks(c, "tq_probe_kernel", c->stream);
-        with_value<1, 2>(g, [&](auto GS) {
-            COMMET_LAUNCH(tq_probe_kernel<GS>, dim3(8 * TQ_PROBE_WGS_PER_XCD), dim3(256), 0, c->stream, v, fg.il_a, c->d_qres, 0u, q.n_pieces);
-        });
-    }
-    HIP_OK(hipGetLastError());
-    {
-        KScope ks(c, "tq_replay_kernel", c->stream);
-        const uint32_t hit_cap = (uint32_t) std::min<int>(c->tq_hit_cap, TQ_HIT_CAP);
-        with_key(c->k, [&](auto key) {
-            with_value<1, 2>(g, [&](auto GS) {
-                with_mask_words(mw, [&](auto MW) {
-                    COMMET_LAUNCH((tq_replay_kernel<decltype(key), GS, MW>), dim3(q.n_pieces), dim3(TQ_PIECE), 0, c->stream, rs->view(), v, c->d_qres,
-                                  fg, c->k, t, d_sel, d_tags, d_counters, cstride, 0u, hit_cap, job_tag_words);
-                });
-            });
-        });
-    }
-    HIP_OK(hipGetLastError());
-    return 0;
+    if (launch_tq_probe(c, v, fg, g)) return 1;
+    return launch_tq_replay(c, "tq_replay_kernel", g, mask_words(c, rs), [&](auto key, auto GS, auto MW, uint32_t hit_cap) {
+        COMMET_LAUNCH((tq_replay_kernel<decltype(key), GS, MW>), dim3(q.n_pieces), dim3(TQ_PIECE), 0, c->stream, rs->view(), v, c->d_qres, fg, c->k, t,
+                      d_sel, d_tags, d_counters, cstride, 0u, hit_cap, job_tag_words);
+    });
 }
 
 // words per bit-sliced entry (32 chunk filters per word) for a job of n_chunks chunks; 0 = the job takes the slot path

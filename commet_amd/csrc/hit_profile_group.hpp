@@ -112,14 +112,10 @@ __global__ __launch_bounds__(256) COMMET_SGPRS void hits_group_kernel(ReadsView 
         if (h > before) hits[r] = (uint8_t) h;
     }
     if (walked) {
-        // one add per workgroup (see add_chunk_counters)
         __shared__ unsigned int wg_walked;
         if (threadIdx.x == 0) wg_walked = 0;
         __syncthreads();
-        const uint64_t wb = __ballot(walk);
-        if ((threadIdx.x & 63) == 0 && wb) atomicAdd(&wg_walked, (unsigned int) __popcll(wb));
-        __syncthreads();
-        if (threadIdx.x == 0 && wg_walked) atomicAdd(walked, (unsigned long long) wg_walked);
+        add_walked(walked, walk, wg_walked);
     }
 }
 

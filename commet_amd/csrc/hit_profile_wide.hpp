@@ -203,14 +203,10 @@ __global__ __launch_bounds__(256) void hits_wide_kernel(ReadsView rv, const uint
     const bool mine = walk && sl == 0;
     if (mine && best > (int) hits[r]) hits[r] = (uint8_t) best;
     if (walked) {
-        // one add per workgroup (see add_chunk_counters)
         __shared__ unsigned int wg_walked;
         if (threadIdx.x == 0) wg_walked = 0;
         __syncthreads();
-        const uint64_t wb = __ballot(mine);
-        if (lane == 0 && wb) atomicAdd(&wg_walked, (unsigned int) __popcll(wb));
-        __syncthreads();
-        if (threadIdx.x == 0 && wg_walked) atomicAdd(walked, (unsigned long long) wg_walked);
+        add_walked(walked, mine, wg_walked);
     }
 }
 

@@ -114,6 +114,17 @@ __device__ __forceinline__ void add_chunk_counters(unsigned long long *__restric
         atomicAdd(&counters[(uint64_t) (threadIdx.x >> 1) * cstride + (threadIdx.x & 1u)], (unsigned long long) wg_cnt[threadIdx.x]);
 }
 
+// The walked-reads counter of a hit-profile pass, for the same reason in the same form: a ballot, one LDS add per wave, one global
+// add per workgroup.  Every thread of the workgroup calls it (it holds a barrier); wg_walked: a word of LDS that the caller has
+// zeroed in front of a barrier (tq_hits_replay_kernel zeroes it early, before barriers it has anyway).
+__device__ __forceinline__ void add_walked(unsigned long long *__restrict__ walked, bool mine, unsigned int &wg_walked)
+{
+    const uint64_t wb = __ballot(mine);
+    if ((threadIdx.x & 63) == 0 && wb) atomicAdd(&wg_walked, (unsigned int) __popcll(wb));
+    __syncthreads();
+    if (threadIdx.x == 0 && wg_walked) atomicAdd(walked, (unsigned long long) wg_walked);
+}
+
 // ---------------------------------------------------------------------------
 // Which read a search thread works on.  Usually thread i of the launch takes read i and the bitmaps decide (sel: reads to
 // search, tags: reads found by an earlier chunk).  A pass over FEW of a set's reads — Commet.py's third job searches a set

@@ -383,171 +383,173 @@ __global__ __launch_bounds__(256) void tq_probe_kernel(QueryListView ql, const u
     }
 }
 
-// replay: one workgroup per piece, one thread per read.
-// (scalar registers capped, COMMET_SGPRS in kernels.hpp: eight workgroups per CU instead of six — the LDS (10.3-18.3 KiB) and the 49-62
-// vector registers of the builds with up to three mask words for two filters, six for one, allow eight, and the kernel is a chain of
-// dependent round trips that lives on workgroups in flight; the larger builds take 106 scalar registers and 22-38 KiB: four to six)
-template <typename W, int GS, int MW>
-__global__ __launch_bounds__(TQ_PIECE) COMMET_SGPRS void tq_replay_kernel(ReadsView rv, QueryListView ql, const uint8_t *__restrict__ qres,
-                                                             FilterGroupView fg, int k, int t, const uint64_t *__restrict__ sel,
-                                                             uint64_t *__restrict__ tags, unsigned long long *__restrict__ counters,
-                                                             uint32_t cstride, uint32_t piece0, uint32_t hit_cap, uint64_t job_tag_words)
+// ---------------------------------------------------------------------------
+// replay: one workgroup per piece, one thread per read, in three steps.  Steps (1) and (2) are the same for every consumer of the
+// probe's result bytes — tq_replay_kernel below (the search: stops at t hits, walks tails) and tq_hits_replay_kernel
+// (hit_profile_tiled.hpp: counts) — and stand here once; step (3) is the kernel's own.
+//   masks[chunk][strand][word][read]: GS * 2 * MW * TQ_PIECE words of LDS, bit = window of the list (32 per word)
+// ---------------------------------------------------------------------------
+
+// (1) collect: the piece's results into `masks` (zeroed here; barriers on either side).  Wave w takes slices w, w + 16, ... in
+// batches of 64 tiles: every lane fetches the bounds of one tile, the batch's records then form one flat list that the wave walks
+// 64 at a time (tile of a record: by counting the tile ends at or below it) — independent loads, no chain of small dependent ones.
+template <int GS, int MW>
+__device__ __forceinline__ void tq_collect(const QueryListView &ql, const uint8_t *__restrict__ qres, uint32_t piece, uint32_t *masks)
 {
-    // job_tag_words != 0 (GS == 2 only; round 6): the two chunk filters belong to TWO jobs that search this set (two J2 jobs of a reference
-    // set, two J3 jobs of a target whose index selections make one chunk each, commet_index_many_and_search): the probe's one gather per
-    // record serves both; here job 1 starts afresh at chunk 1 — no read is skipped for what job 0 found — and job j's found flags go to
-    // tags + j * job_tag_words (zeroed by the host), its counters to its own chunk's slots.  `tags` is not read then.
-    const bool multi = GS == 2 && job_tag_words != 0;
-    // hit_cap <= TQ_HIT_CAP: full hits of light scans a piece may post (tests set it to 0: every piece with a hit overflows)
-    const uint32_t piece = blockIdx.x + piece0;          // (the launch covers pieces piece0 .. piece0 + gridDim.x - 1)
-    __shared__ uint32_t masks[GS * 2 * MW * TQ_PIECE];   // [chunk][strand][word][read]
     auto mask_at = [&](int c, int strand, int h, uint32_t rd) -> uint32_t & { return masks[(((c * 2 + strand) * MW) + h) * TQ_PIECE + rd]; };
     for (uint32_t i = threadIdx.x; i < GS * 2 * MW * TQ_PIECE; i += TQ_PIECE) masks[i] = 0;
     __syncthreads();
-    // (1) the piece's results.  Wave w takes slices w, w + 16, ... in batches of 64 tiles: every lane fetches the bounds of
-    // one tile, the batch's records then form one flat list that the wave walks 64 at a time (tile of a record: by
-    // counting the tile ends at or below it) — independent loads, no chain of small dependent ones.
-    {
-        const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-        constexpr uint32_t NWAVE = TQ_PIECE / 64;
-        for (uint32_t s0 = wave; s0 < ql.n_slices; s0 += 64 * NWAVE) {
-            const uint32_t sl = s0 + lane * NWAVE;                       // this lane's tile of the batch
-            unsigned long long ta = 0, te = 0;
-            if (sl < ql.n_slices) {
-                ta = ql.tstart[(uint64_t) piece * ql.n_slices + sl];           // piece-major: a piece's bounds are contiguous
-                te = ta + ql.tlen[(uint64_t) piece * ql.n_slices + sl];
-            }
-            const uint32_t len = (uint32_t) (te - ta);
-            uint32_t inc = len;                                           // inclusive prefix of the tile lengths over the lanes
-            for (int o = 1; o < 64; o <<= 1) {
-                const uint32_t x = __shfl_up(inc, o, 64);
-                if ((int) lane >= o) inc += x;
-            }
-            const uint32_t total = __shfl(inc, 63, 64);
-            // TQ_COLLECT_U flat records per lane and round: their result bytes and owner words are independent loads, all issued
-            // before the first is looked at — one round trip per round instead of two per record (the loop used to wait for a
-            // record's result byte, then, for the one in four that is not zero, for its owner word).  The owner words of the
-            // zero results cost no memory traffic: their sectors are fetched for their neighbours anyway.
-            for (uint32_t f0 = 0; f0 < total; f0 += 64 * TQ_COLLECT_U) {              // (uniform trip count: every lane takes part in the shuffles)
-                unsigned long long ri[TQ_COLLECT_U];
-                bool ok[TQ_COLLECT_U];
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    constexpr uint32_t NWAVE = TQ_PIECE / 64;
+    for (uint32_t s0 = wave; s0 < ql.n_slices; s0 += 64 * NWAVE) {
+        const uint32_t sl = s0 + lane * NWAVE;                       // this lane's tile of the batch
+        unsigned long long ta = 0, te = 0;
+        if (sl < ql.n_slices) {
+            ta = ql.tstart[(uint64_t) piece * ql.n_slices + sl];           // piece-major: a piece's bounds are contiguous
+            te = ta + ql.tlen[(uint64_t) piece * ql.n_slices + sl];
+        }
+        const uint32_t len = (uint32_t) (te - ta);
+        uint32_t inc = len;                                           // inclusive prefix of the tile lengths over the lanes
+        for (int o = 1; o < 64; o <<= 1) {
+            const uint32_t x = __shfl_up(inc, o, 64);
+            if ((int) lane >= o) inc += x;
+        }
+        const uint32_t total = __shfl(inc, 63, 64);
+        // TQ_COLLECT_U flat records per lane and round: their result bytes and owner words are independent loads, all issued
+        // before the first is looked at — one round trip per round instead of two per record (the loop used to wait for a
+        // record's result byte, then, for the one in four that is not zero, for its owner word).  The owner words of the
+        // zero results cost no memory traffic: their sectors are fetched for their neighbours anyway.
+        for (uint32_t f0 = 0; f0 < total; f0 += 64 * TQ_COLLECT_U) {              // (uniform trip count: every lane takes part in the shuffles)
+            unsigned long long ri[TQ_COLLECT_U];
+            bool ok[TQ_COLLECT_U];
 #pragma unroll
-                for (int u = 0; u < TQ_COLLECT_U; ++u) {
-                    const uint32_t f = f0 + 64u * (uint32_t) u + lane;
-                    // tile of flat record f = number of lanes whose inclusive prefix is <= f (binary search over the 64 prefixes)
-                    uint32_t lo = 0, hi = 64;
+            for (int u = 0; u < TQ_COLLECT_U; ++u) {
+                const uint32_t f = f0 + 64u * (uint32_t) u + lane;
+                // tile of flat record f = number of lanes whose inclusive prefix is <= f (binary search over the 64 prefixes)
+                uint32_t lo = 0, hi = 64;
 #pragma unroll
-                    for (int step = 0; step < 7; ++step) {
-                        const uint32_t mid = min((lo + hi) >> 1, 63u);
-                        const uint32_t pm = __shfl(inc, (int) mid, 64);
-                        if (lo < hi) {
-                            if (pm <= f) lo = mid + 1;
-                            else hi = mid;
-                        }
+                for (int step = 0; step < 7; ++step) {
+                    const uint32_t mid = min((lo + hi) >> 1, 63u);
+                    const uint32_t pm = __shfl(inc, (int) mid, 64);
+                    if (lo < hi) {
+                        if (pm <= f) lo = mid + 1;
+                        else hi = mid;
                     }
-                    const uint32_t src = min(lo, 63u);
-                    const uint32_t before_raw = __shfl(inc, (int) (src ? src - 1 : 0), 64);
-                    const unsigned long long tbase = __shfl((unsigned long long) ta, (int) src, 64);
-                    ok[u] = f < total;
-                    ri[u] = ok[u] ? tbase + (f - (src ? before_raw : 0u)) : 0ull;     // (record 0 exists whenever the batch has one)
                 }
-                uint32_t res[TQ_COLLECT_U], who[TQ_COLLECT_U];
+                const uint32_t src = min(lo, 63u);
+                const uint32_t before_raw = __shfl(inc, (int) (src ? src - 1 : 0), 64);
+                const unsigned long long tbase = __shfl((unsigned long long) ta, (int) src, 64);
+                ok[u] = f < total;
+                ri[u] = ok[u] ? tbase + (f - (src ? before_raw : 0u)) : 0ull;     // (record 0 exists whenever the batch has one)
+            }
+            uint32_t res[TQ_COLLECT_U], who[TQ_COLLECT_U];
 #pragma unroll
-                for (int u = 0; u < TQ_COLLECT_U; ++u) {
-                    res[u] = __builtin_nontemporal_load(qres + ri[u]);
-                    who[u] = __builtin_nontemporal_load(ql.qwho + ri[u]);
-                }
+            for (int u = 0; u < TQ_COLLECT_U; ++u) {
+                res[u] = __builtin_nontemporal_load(qres + ri[u]);
+                who[u] = __builtin_nontemporal_load(ql.qwho + ri[u]);
+            }
 #pragma unroll
-                for (int u = 0; u < TQ_COLLECT_U; ++u) {
-                    if (!ok[u] || !res[u]) continue;
-                    const uint32_t rd = who[u] & 255u, win = who[u] >> 8;
+            for (int u = 0; u < TQ_COLLECT_U; ++u) {
+                if (!ok[u] || !res[u]) continue;
+                const uint32_t rd = who[u] & 255u, win = who[u] >> 8;
+                if ((win >> 5) >= (uint32_t) MW) continue;            // (the host sizes MW by the list's longest read, mask_words_of: never taken; it keeps a wrong choice inside LDS)
 #pragma unroll
-                    for (int c = 0; c < GS; ++c) {
-                        if ((res[u] >> c) & 1u) atomicOr(&mask_at(c, 0, (int) (win >> 5), rd), 1u << (win & 31u));
-                        if ((res[u] >> (GS + c)) & 1u) atomicOr(&mask_at(c, 1, (int) (win >> 5), rd), 1u << (win & 31u));
-                    }
+                for (int c = 0; c < GS; ++c) {
+                    if ((res[u] >> c) & 1u) atomicOr(&mask_at(c, 0, (int) (win >> 5), rd), 1u << (win & 31u));
+                    if ((res[u] >> (GS + c)) & 1u) atomicOr(&mask_at(c, 1, (int) (win >> 5), rd), 1u << (win & 31u));
                 }
             }
         }
     }
     __syncthreads();
-    // (2) planes B, C, D for the lane-a candidates, balanced over the workgroup.  A read has ~11 candidates on average but
-    // the count varies from lane to lane, and every probe is a dependent HBM round trip; walking them per read leaves
-    // most lanes idle in most of ~150 serialised loads per wave.  So the candidates of the whole piece are numbered
-    // (prefix sums of the masks' popcounts) and thread f takes candidates f, f + 1024, ...: one plane-B probe per lane and
-    // round, all lanes busy.  Survivors (A & B) are collected in a second mask array and go through planes C and D the same
-    // way; what is left are the full four-lane hits.
-    // The full hits (A & B & C & D) of the light scans are found by whichever thread the sweep hands the candidate to, and are few (chance
-    // hits; reads that share sequence are heavy scans and walk their own candidates).  They are posted as a list of
-    // TQ_HIT_CAP words and, behind the sweep, ORed into the masks array itself, which nobody reads any more by then — the second
-    // mask array (12 KiB with three mask words: five workgroups per CU instead of eight, 6.4 against 4.5 ms per configs[1]-sized
-    // step on 50-150-bp reads) is gone.  A piece with more hits than the list holds lets every scan walk its own candidates, as
-    // heavy scans do: exact, only slower.
-    __shared__ uint32_t hits[TQ_HIT_CAP];
+}
+
+// what step (2) leaves for the kernel's step (3), beside the full hits of the light scans in `masks`
+template <int GS, int MW> struct TqSwept {
+    uint32_t am[2 * GS][MW];          // this thread's lane-a candidates as collected (scan index = chunk * 2 + strand): what a heavy scan walks
+    uint32_t hv;                      // bit i: scan i is heavy
+    bool all_self;                    // the hit list overflowed: every scan of the piece walks its own candidates, as heavy scans do
+    uint64_t t0;                      // this thread's read: its first triple and its length (0, 0 behind the set's last read)
+    uint32_t len;
+    const uint32_t *piece_planes;     // the words of the piece's first read; read `owner` of the piece starts 3 * (rd_ext[owner] & 0xFFFF) words on
+};
+
+// (2) sweep: planes B, C, D for the lane-a candidates in `masks`, balanced over the workgroup; on return `masks` holds the FULL hits
+// (A & B & C & D) of the light scans of the active reads and nothing else.  Every thread of the workgroup calls it (barriers); the
+// kernel zeroes its own workgroup counters in front of the call, the barriers in here order them.
+//   active       the kernel's rule (searched / walked); the candidates of the other reads are dropped
+//   hits         TQ_HIT_CAP words, dead on return: the search's tails take them over
+//   rd_ext       where every read of the piece lies and how long it is: (first triple - the piece's first triple) | length << 16.  A
+//                candidate is probed by whichever thread the sweep hands it to, a tail window by whichever thread its number falls on,
+//                and on a set of many read lengths the owner's extent is two more loads (goff) in front of every such probe's chain;
+//                the piece's 256 extents fit 1 KiB (reads of a set that takes the tiled search have fewer than 2^13 bases: TQ_MAX_LEN)
+// Why balanced: a read has ~11 candidates on average but the count varies from lane to lane, and every probe is a dependent HBM
+// round trip; walking them per read leaves most lanes idle in most of ~150 serialised loads per wave.  So the candidates of the
+// whole piece are numbered (prefix sums of the masks' popcounts) and thread f takes candidates f, f + 256, ..., TQ_SWEEP_U of them
+// per round: one plane-B probe per candidate, all lanes busy.  The one in nine that passes B goes through planes C and D at once
+// (two independent loads): a second balanced sweep for C / D (1.2 K survivors per piece) cost more in prefix sums and barriers
+// than the divergence it avoided.
+// Why heavy scans: a read that shares sequence with the index set has a lane-a bit on (nearly) every window of one strand; the
+// reference leaves it after t hits, i.e. after ~4 t probes.  Such scans (more than TQ_HEAVY candidates) keep their candidates in
+// registers (am) and their thread walks them itself in step (3), where t hits or saturation end the walk; probing all their
+// windows in the sweep would multiply their probes by ten.  The read's other scans (the other strand, the other chunk: a handful
+// of chance candidates) stay in the sweep like anybody's.
+// Why a hit list: the full hits of the light scans are found by whichever thread the sweep hands the candidate to, and are few
+// (chance hits).  They are posted as a list of hit_cap <= TQ_HIT_CAP words and, behind the sweep, ORed into the masks array itself,
+// which nobody reads any more by then — a second mask array (12 KiB with three mask words: five workgroups per CU instead of
+// eight, 6.4 against 4.5 ms per configs[1]-sized step on 50-150-bp reads) is gone.  A piece with more hits than the list holds
+// lets every scan walk its own candidates: exact, only slower (tests set hit_cap to 0: every piece with a hit overflows).
+// The group holds exactly GS filters (fg.g == GS: the hosts instantiate by g) and a slot is four planes (filter_group): fg.g and
+// fg.slot_words are not read in here — with them live, builds of two filters kept scalar values in vector lanes under the
+// 80-register cap.
+constexpr uint32_t TQ_HEAVY = 20;   // 4 / 12 / 18 / 24 / 32 / 40 -> 8.2 / 6.9 / 6.3 / 6.3 / 6.6 / 8.9 ms on configs[1]
+template <typename W, int GS, int MW>
+__device__ __forceinline__ void tq_sweep(const ReadsView &rv, const FilterGroupView &fg, const KeyCtx<W> &kc, int k, uint64_t r, bool active,
+                                         uint32_t hit_cap, uint32_t *masks, uint32_t *hits, uint32_t *rd_ext, TqSwept<GS, MW> &out)
+{
+    static_assert(TQ_PIECE == 256 && 2 * GS <= 16 && MW <= 16, "a hit packs the read in 8 bits, the scan and the mask word in 4 each");
     __shared__ uint32_t hit_n;
-    // where every read of the piece lies and how long it is: (first triple - the piece's first triple) | length << 16.  A candidate is
-    // probed by whichever thread the sweep hands it to, a tail window by whichever thread its number falls on, and on a set of many read
-    // lengths the owner's extent is two more loads (goff) in front of every such probe's chain; the piece's 256 extents fit 1 KiB
-    // (reads of a set that takes the tiled search have fewer than 2^13 bases: TQ_MAX_WIN first-hit windows)
-    __shared__ uint32_t rd_ext[TQ_PIECE];
     __shared__ unsigned long long piece_t0;
     __shared__ uint32_t pre[TQ_PIECE];
     __shared__ uint32_t scan_ws[TQ_PIECE / 64];
-    __shared__ unsigned int wg_cnt[2 * GS];
     constexpr int NS = 2 * GS;                           // scan index = chunk * 2 + strand
-    auto word_at = [&](uint32_t *arr, int i, int h, uint32_t rd) -> uint32_t & { return arr[((i * MW) + h) * TQ_PIECE + rd]; };
-    if (threadIdx.x < 2 * GS) wg_cnt[threadIdx.x] = 0;
+    auto word_at = [&](int i, int h, uint32_t rd) -> uint32_t & { return masks[((i * MW) + h) * TQ_PIECE + rd]; };
     if (threadIdx.x == 0) hit_n = 0;
-    static_assert(TQ_PIECE == 256, "search_lane, add_chunk_counters and cooperative_tail are written for workgroups of 256 threads");
-    const ActiveList no_list{nullptr, nullptr};
-    const SearchLane me = search_lane(rv, no_list, sel, multi ? nullptr : tags, piece0);   // thread x of piece p has read 256 p + x
-    const uint64_t r = me.r;
-    const bool active = me.active;
     uint64_t my_t0 = 0;
     uint32_t my_len = 0;
     if (r < rv.n) read_extent(rv, r, my_t0, my_len);
     if (threadIdx.x == 0) piece_t0 = my_t0;                          // (the piece's first read exists: the grid covers pieces of the set only)
-    const KeyCtx<W> kc(k);
 #pragma unroll
     for (int i = 0; i < NS; ++i)
 #pragma unroll
         for (int h = 0; h < MW; ++h)
-            if (!active || (i >> 1) >= fg.g) word_at(masks, i, h, threadIdx.x) = 0;   // reads that are not searched have no candidates
+            if (!active) word_at(i, h, threadIdx.x) = 0;             // reads that are not searched have no candidates
     __syncthreads();
-    rd_ext[threadIdx.x] = (r < rv.n) ? ((uint32_t) (my_t0 - piece_t0) & 0xFFFFu) | (my_len << 16) : 0u;   // (first read before the sweep's first barrier)
-    // A read that shares sequence with the index set has a lane-a bit on (nearly) every window of one strand; the
-    // reference leaves it after t hits, i.e. after ~4 t probes.  Such "heavy" scans (more than TQ_HEAVY candidates) keep
-    // their masks in registers and their thread walks them itself in step (3), stopping at t; probing all their windows
-    // in the balanced sweep would multiply their probes by ten.  The read's other scans (the other strand, the other
-    // chunk: a handful of chance candidates) stay in the sweep like anybody's.
-    constexpr uint32_t TQ_HEAVY = 20;   // 4 / 12 / 18 / 24 / 32 / 40 -> 8.2 / 6.9 / 6.3 / 6.3 / 6.6 / 8.9 ms on configs[1]
-    uint32_t am[NS][MW];
-    uint32_t hv = 0;                    // bit i: scan i is heavy
+    rd_ext[threadIdx.x] = (r < rv.n) ? ((uint32_t) (my_t0 - piece_t0) & 0xFFFFu) | (my_len << 16) : 0u;   // (first read behind the next barrier)
+    uint32_t hv = 0;
 #pragma unroll
     for (int i = 0; i < NS; ++i) {
         uint32_t n = 0;
 #pragma unroll
-        for (int h = 0; h < MW; ++h) am[i][h] = word_at(masks, i, h, threadIdx.x), n += __popc(am[i][h]);
+        for (int h = 0; h < MW; ++h) out.am[i][h] = word_at(i, h, threadIdx.x), n += __popc(out.am[i][h]);
         if (n > TQ_HEAVY) {
             hv |= 1u << i;
 #pragma unroll
-            for (int h = 0; h < MW; ++h) word_at(masks, i, h, threadIdx.x) = 0;   // (the sweep's first barrier comes before anyone else reads them)
+            for (int h = 0; h < MW; ++h) word_at(i, h, threadIdx.x) = 0;   // (the next barrier comes before anyone else reads them)
         }
     }
-    // words of another read of the piece around window end q
     const uint32_t *const piece_planes = rv.planes + 3 * piece_t0;
-    auto keys_of = [&](uint32_t owner, int strand, int q, W &ka, W &kb) {
-        (void) kc.window_keys(piece_planes + 3u * (rd_ext[owner] & 0xFFFFu), q, strand, ka, kb);   // complete: only complete windows are in the list
-    };
-    // one balanced sweep over the set bits of `src` (heavy scans are not in it), four candidates per thread and round so that
-    // four probes are in flight per lane: word_of(owner, scan, window end) -> {filter word address, bit} of the first plane
-    // to test; on_set(owner, scan, mask word, bit, ka, kb) is called for the candidates whose bit is set
-    auto sweep = [&](uint32_t *src, auto &&word_of, auto &&on_set) {
+    // (the loop stands in a lambda of its own, called on the spot: the compiler then optimises it by itself before it inlines it, and
+    // tq_replay_kernel<u64, 1, 6> and <u64, 1, 8> keep 58 and 62 vector registers; written straight into this function they took 66 and 74
+    // and lost a wave per SIMD each — MEASUREMENTS.md, "Tiled replay: shared steps".  It rests on this compiler's order of passes: after
+    // a toolchain update, or a change in here, run tools/kernel_resources.py and hold the 40 replay rows against that section's table —
+    // vgpr / occ of those two builds first; if the lambda no longer helps, take it out)
+    [&]() {
         uint32_t cnt = 0;
 #pragma unroll
         for (int i = 0; i < NS; ++i)
 #pragma unroll
-            for (int h = 0; h < MW; ++h) cnt += __popc(word_at(src, i, h, threadIdx.x));
+            for (int h = 0; h < MW; ++h) cnt += __popc(word_at(i, h, threadIdx.x));
         uint32_t total;
         const uint32_t ex = block_scan<TQ_PIECE>(cnt, scan_ws, &total);
         pre[threadIdx.x] = ex + cnt;                      // inclusive
@@ -577,63 +579,101 @@ __global__ __launch_bounds__(TQ_PIECE) COMMET_SGPRS void tq_replay_kernel(ReadsV
 #pragma unroll
                     for (int h = 0; h < MW; ++h) {
                         if (got) continue;
-                        const uint32_t x = word_at(src, i, h, lo);
+                        const uint32_t x = word_at(i, h, lo);
                         const uint32_t c = __popc(x);
                         if (local < c) sc[u] = i, hw[u] = h, wd = x, got = true;
                         else local -= c;
                     }
                 for (uint32_t v = 0; v < local; ++v) wd &= wd - 1u;        // drop the `local` lowest set bits
                 owner[u] = lo, bitn[u] = (uint32_t) __ffs((int) wd) - 1u;
+                have[u] = got && wd != 0;                                  // (always: f < total)
             }
-            const uint32_t *wp[U];
 #pragma unroll
-            for (int u = 0; u < U; ++u) {                                  // keys: the owners' read words (L1 / L2)
+            for (int u = 0; u < U; ++u) {                                  // keys: the owners' read words (L1 / L2); only complete windows are in the list
                 ka[u] = kb[u] = 0;
-                if (have[u]) keys_of(owner[u], sc[u] & 1, (int) (32 * hw[u] + bitn[u]) + (k - 1), ka[u], kb[u]);
+                if (have[u])
+                    (void) kc.window_keys(piece_planes + 3u * (rd_ext[owner[u]] & 0xFFFFu), (int) (32 * hw[u] + bitn[u]) + (k - 1), sc[u] & 1, ka[u], kb[u]);
             }
 #pragma unroll
-            for (int u = 0; u < U; ++u) {                                  // the filter words: up to four HBM probes in flight
-                fw[u] = 0, fbit[u] = 0;
-                if (have[u]) {
-                    wp[u] = word_of(sc[u], ka[u], kb[u], fbit[u]);
-                    fw[u] = *wp[u];
+            for (int u = 0; u < U; ++u) {                                  // plane B: U probes in flight
+                fw[u] = 0, fbit[u] = (uint32_t) kb[u] & 31u;
+                if (have[u]) fw[u] = fg.slot0[(uint64_t) (sc[u] >> 1) * (4 * fg.plane_words) + fg.plane_words + (kb[u] >> 5)];
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                if (!have[u] || !((fw[u] >> fbit[u]) & 1u)) continue;
+                const uint32_t *pc = fg.slot0 + (uint64_t) (sc[u] >> 1) * (4 * fg.plane_words) + 2 * fg.plane_words, *pd = pc + fg.plane_words;
+                const W kx = ka[u] ^ kb[u], ko = ka[u] | kb[u];
+                const uint32_t vc = pc[kx >> 5], vd = pd[ko >> 5];
+                if ((vc >> ((uint32_t) kx & 31u)) & (vd >> ((uint32_t) ko & 31u)) & 1u) {
+                    const uint32_t at = atomicAdd(&hit_n, 1u);
+                    if (at < hit_cap) hits[at] = owner[u] | ((uint32_t) sc[u] << 8) | ((uint32_t) hw[u] << 12) | (bitn[u] << 16);
                 }
             }
-#pragma unroll
-            for (int u = 0; u < U; ++u)
-                if (have[u] && ((fw[u] >> fbit[u]) & 1u)) on_set(owner[u], sc[u], hw[u], bitn[u], ka[u], kb[u]);
         }
         __syncthreads();
-    };
-    // plane B of every candidate; the one in nine that passes goes through planes C and D at once (two independent
-    // loads).  A second balanced sweep for C / D (1.2 K survivors per piece) cost more in prefix sums and barriers
-    // than the divergence it avoided.
-    sweep(masks,
-          [&](int i, W, W kb, uint32_t &bit) -> const uint32_t * {
-              bit = (uint32_t) kb & 31u;
-              return fg.slot0 + (uint64_t) (i >> 1) * fg.slot_words + fg.plane_words + (kb >> 5);
-          },
-          [&](uint32_t owner, int i, int h, uint32_t b, W ka, W kb) {
-              const uint32_t *pc = fg.slot0 + (uint64_t) (i >> 1) * fg.slot_words + 2 * fg.plane_words, *pd = pc + fg.plane_words;
-              const uint32_t vc = pc[(ka ^ kb) >> 5], vd = pd[(ka | kb) >> 5];
-              if ((vc >> ((uint32_t) (ka ^ kb) & 31u)) & (vd >> ((uint32_t) (ka | kb) & 31u)) & 1u) {
-                  const uint32_t at = atomicAdd(&hit_n, 1u);
-                  if (at < hit_cap) hits[at] = owner | ((uint32_t) i << 8) | ((uint32_t) h << 12) | (b << 16);
-              }
-          });
+    }();
     // (behind the sweep's last barrier: nobody reads the masks any more) the full hits into the masks array
 #pragma unroll
     for (int i = 0; i < NS; ++i)
 #pragma unroll
-        for (int h = 0; h < MW; ++h) word_at(masks, i, h, threadIdx.x) = 0;
+        for (int h = 0; h < MW; ++h) word_at(i, h, threadIdx.x) = 0;
     __syncthreads();
     const uint32_t nh = hit_n;
-    const bool all_self = nh > hit_cap;   // the list overflowed: every scan walks its own lane-a candidates (am[])
     for (uint32_t e = threadIdx.x; e < min(nh, hit_cap); e += TQ_PIECE) {
         const uint32_t x = hits[e];
-        atomicOr(&word_at(masks, (int) ((x >> 8) & 15u), (int) ((x >> 12) & 15u), x & 255u), 1u << (x >> 16));
+        atomicOr(&word_at((int) ((x >> 8) & 15u), (int) ((x >> 12) & 15u), x & 255u), 1u << (x >> 16));
     }
     __syncthreads();
+    out.hv = hv, out.all_self = nh > hit_cap;
+    out.t0 = my_t0, out.len = my_len, out.piece_planes = piece_planes;
+}
+
+// the mask word a scan walks in step (3): the full hits of a light scan, a heavy scan's own lane-a candidates (probed by the walker)
+template <int GS, int MW>
+__device__ __forceinline__ uint32_t tq_walk_word(const uint32_t *masks, const TqSwept<GS, MW> &sw, int i, int h, bool hscan)
+{
+    uint32_t m = masks[((i * MW) + h) * TQ_PIECE + threadIdx.x];
+    if (hscan) {
+        m = 0;
+#pragma unroll
+        for (int ii = 0; ii < 2 * GS; ++ii)
+#pragma unroll
+            for (int hh = 0; hh < MW; ++hh)
+                if (ii == i && hh == h) m = sw.am[ii][hh];        // (selects, not an indexed register array)
+    }
+    return m;
+}
+
+// the search's replay.
+// (scalar registers capped, COMMET_SGPRS in kernels.hpp: eight workgroups per CU instead of six — the LDS (10.3-18.3 KiB) and the 49-62
+// vector registers of the builds with up to three mask words for two filters, six for one, allow eight, and the kernel is a chain of
+// dependent round trips that lives on workgroups in flight; the larger builds take 106 scalar registers and 22-38 KiB: four to six)
+template <typename W, int GS, int MW>
+__global__ __launch_bounds__(TQ_PIECE) COMMET_SGPRS void tq_replay_kernel(ReadsView rv, QueryListView ql, const uint8_t *__restrict__ qres,
+                                                             FilterGroupView fg, int k, int t, const uint64_t *__restrict__ sel,
+                                                             uint64_t *__restrict__ tags, unsigned long long *__restrict__ counters,
+                                                             uint32_t cstride, uint32_t piece0, uint32_t hit_cap, uint64_t job_tag_words)
+{
+    // job_tag_words != 0 (GS == 2 only; round 6): the two chunk filters belong to TWO jobs that search this set (two J2 jobs of a reference
+    // set, two J3 jobs of a target whose index selections make one chunk each, commet_index_many_and_search): the probe's one gather per
+    // record serves both; here job 1 starts afresh at chunk 1 — no read is skipped for what job 0 found — and job j's found flags go to
+    // tags + j * job_tag_words (zeroed by the host), its counters to its own chunk's slots.  `tags` is not read then.
+    const bool multi = GS == 2 && job_tag_words != 0;
+    const uint32_t piece = blockIdx.x + piece0;          // (the launch covers pieces piece0 .. piece0 + gridDim.x - 1)
+    __shared__ uint32_t masks[GS * 2 * MW * TQ_PIECE];   // [chunk][strand][word][read]
+    __shared__ uint32_t hits[TQ_HIT_CAP];
+    __shared__ uint32_t rd_ext[TQ_PIECE];
+    __shared__ unsigned int wg_cnt[2 * GS];
+    tq_collect<GS, MW>(ql, qres, piece, masks);
+    if (threadIdx.x < 2 * GS) wg_cnt[threadIdx.x] = 0;   // (before the sweep's barriers)
+    static_assert(TQ_PIECE == 256, "search_lane, add_chunk_counters and cooperative_tail are written for workgroups of 256 threads");
+    const ActiveList no_list{nullptr, nullptr};
+    const SearchLane me = search_lane(rv, no_list, sel, multi ? nullptr : tags, piece0);   // thread x of piece p has read 256 p + x
+    const bool active = me.active;
+    const KeyCtx<W> kc(k);
+    TqSwept<GS, MW> sw;
+    tq_sweep<W, GS, MW>(rv, fg, kc, k, me.r, active, hit_cap, masks, hits, rd_ext, sw);
     // (3) the reference's control flow (search_reads.h:45-83) on the full hits of this thread's read: per chunk, strand 0
     // then strand 1; greedy non-overlapping hits (StrandScan::walk); the windows behind the first-hit ones are fetched by the whole
     // workgroup, for the scans that have a hit but not yet t of them (cooperative_tail).
@@ -644,8 +684,8 @@ __global__ __launch_bounds__(TQ_PIECE) COMMET_SGPRS void tq_replay_kernel(ReadsV
     int found_chunk = -1;
     bool found_job0 = false, found_job1 = false;       // (two jobs in one scan)
     {
-        const uint32_t *p = rv.planes + 3 * my_t0;
-        const int last = (int) my_len - 1;
+        const uint32_t *p = rv.planes + 3 * sw.t0;
+        const int last = (int) sw.len - 1;
         const int pe = last - (t - 1) * k;
         const int q0 = k - 1;
         bool found = false;
@@ -660,19 +700,9 @@ __global__ __launch_bounds__(TQ_PIECE) COMMET_SGPRS void tq_replay_kernel(ReadsV
                 (void) kc.window_keys(p, q, strand, ka, kb);
                 return probe_bcd_together<W>(f, ka, kb);
             };
-            const bool hscan = ((hv >> i) & 1u) || all_self;
-            for (int h = 0; h < MW && sc.open(); ++h) {
-                uint32_t m = masks[((i * MW) + h) * TQ_PIECE + threadIdx.x];    // light scans: full hits (step 2)
-                if (hscan) {                                                     // heavy scans: lane-a candidates, probed here
-                    m = 0;
-#pragma unroll
-                    for (int ii = 0; ii < NS; ++ii)
-#pragma unroll
-                        for (int hh = 0; hh < MW; ++hh)
-                            if (ii == i && hh == h) m = am[ii][hh];
-                }
-                sc.walk(m, q0 + 32 * h, t, k, last, [&](int q) -> bool { return !hscan || probe_own(q); });
-            }
+            const bool hscan = ((sw.hv >> i) & 1u) || sw.all_self;
+            for (int h = 0; h < MW && sc.open(); ++h)
+                sc.walk(tq_walk_word(masks, sw, i, h, hscan), q0 + 32 * h, t, k, last, [&](int q) -> bool { return !hscan || probe_own(q); });
             // the tail, 32 windows per request; an owner's extent and words through rd_ext (above)
             cooperative_tail<W, 32, GS>(
                 sc, tail_req, tail_bits, tail_n, kc, strand, t, pe, last, fg.il_a, i >> 1,
@@ -680,7 +710,7 @@ __global__ __launch_bounds__(TQ_PIECE) COMMET_SGPRS void tq_replay_kernel(ReadsV
                     const uint32_t oext = rd_ext[owner];
                     if (q >= (int) (oext >> 16)) return false;
                     ItemWords<W> ot;
-                    ot.load(piece_planes + 3u * (oext & 0xFFFFu), (uint32_t) q >> 5);
+                    ot.load(sw.piece_planes + 3u * (oext & 0xFFFFu), (uint32_t) q >> 5);
                     return ot.window((uint32_t) q & 31u, k, kc.mask, wh, wl);
                 },
                 probe_own);

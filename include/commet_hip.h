@@ -327,7 +327,9 @@ int commet_index_many_and_search(commet_ctx *ctx, int n_jobs, const commet_reads
  * Large sets at 25 <= k <= 34, by option "profile_tiled": a pass of one or two chunk filters goes through the tiled probe — tq_probe_kernel
  * over the set's query list of (k, t = 1), which holds every complete window of every read (the search's own list on a context of
  * t = 1, else a second list cached with the set under the same rules: commet_readset_cache_bytes counts both), then
- * tq_hits_replay_kernel, which counts the full hits greedily per filter and strand.  Sparse passes, sets that take long_search, groups
+ * tq_hits_replay_kernel: the search's tq_replay_kernel with another last step — both collect the probe's results and sweep planes B, C, D
+ * with the same code (tq_collect, tq_sweep); the search then stops at t hits and walks the tails, the profile counts the full hits
+ * greedily per filter and strand.  Sparse passes, sets that take long_search, groups
  * of three filters and more, count_probes, and sets without room for the list run the kernels above.  The bytes do not depend on it.
  * Not done here: profiles through the narrow bit-sliced tables, and a profile form of commet_index_many_and_search. */
 int commet_index_and_profile(commet_ctx *ctx, const commet_readset *index_rs, const uint8_t *index_select,

@@ -19,7 +19,7 @@ _SWEEPS = {}
 
 
 def mask_words(n_windows):
-    """mask words of the replay for a set whose longest read has n_windows windows (mask_words, capi/search_dispatch.hpp)"""
+    """mask words of the replay for a set whose longest read has n_windows windows (mask_words_of, capi/search_dispatch.hpp)"""
     return 2 if n_windows <= 64 else 3 if n_windows <= 96 else 4 if n_windows <= 128 else 6 if n_windows <= 192 else 8
 
 

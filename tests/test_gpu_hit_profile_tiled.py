@@ -116,6 +116,69 @@ def test_hit_list_overflow(tmp_path, n_chunks):
         _sweep_case(tmp_path, ctx, 25, n_chunks, caps=(0, 3))
 
 
+# ---- 1b. the two consumers of the replay's shared steps ------------------------------------------------------------------------------------
+def _first_hit_windows(k, t, max_len):
+    """first_hit_windows of capi/search_dispatch.hpp: max_len - t_eff k + 1 with t_eff = min(t, max_len / k + 1)"""
+    return max_len - min(t, max_len // k + 1) * k + 1
+
+
+def _left_out(k, T):
+    """the (W, t) pairs, t in 1..T, at which the sweep's set of W-window reads (all of k + W - 1 bases) has no first-hit window: the
+    tiled search does not take it (tq_geometry_ok asks for 1..255), so it is not searched at that t"""
+    return [(W, t) for W in ts.WINDOWS for t in range(1, T + 1) if _first_hit_windows(k, t, k + W - 1) < 1]
+
+
+def _largest_t(k, designed):
+    """T = the largest designed count + 1, lowered until at most a quarter of the (set, t) pairs are left out — from the sets' lengths
+    alone.  k = 25: T = 4, 8 of 32 pairs left out (W = 1 from t = 2, W = 32 and 33 from t = 3, W = 65 at t = 4).  k = 33: the designed
+    T = 4 would leave out 12 of 32 and T = 3 7 of 24 (a window costs 33 bases per further hit), so T = 2: 3 of 16"""
+    T = designed + 1
+    while T > 1 and 4 * len(_left_out(k, T)) > len(ts.WINDOWS) * T:
+        T -= 1
+    return T
+
+
+@pytest.mark.parametrize("cap", [1024, 3, 0])
+@pytest.mark.parametrize("n_chunks", [1, 2])
+@pytest.mark.parametrize("k", [25, ts.WIDE_K])
+def test_search_and_profile_agree_on_the_window_sweep(k, n_chunks, cap):
+    """tq_replay_kernel and tq_hits_replay_kernel share the collect and the sweep (tq_collect, tq_sweep: tile_search.hpp): on the window
+    sweep's sets (mask widths 2, 3, 4, 6 and 8 by mask_words_of, capi/search_dispatch.hpp; hits at bits 31 / 32 and 63 / 64, either
+    strand) the tiled search's found flags at every t in 1..T are the tiled profile's hits >= t, read by read, at every hit-list cap.
+    T comes from the quarter rule (_largest_t: 4 at k = 25, 2 at k = 33).  Beyond it, up to the largest designed count + 1 (where no
+    read is found), the sets that still have a first-hit window are compared as well (k = 33: W >= 97 at t = 3, W >= 129 at t = 4);
+    those pairs stand outside the quarter count.  The profile runs once, at max_hits = the largest designed count + 1"""
+    commet = _commet()
+    index, max_kmer, sets = ts.window_sweep(k, n_chunks)
+    top = max(max(exp) for _, exp in sets.values()) + 1
+    T = _largest_t(k, top - 1)
+    left_out = _left_out(k, T)
+    assert 2 <= T <= top and 4 * len(left_out) <= len(ts.WINDOWS) * T, (k, T, left_out)
+    no_window = _left_out(k, top)
+    opts = dict(max_kmer=max_kmer, chunk_group=2, tq_hit_cap=cap)
+    with _context(k, **opts) as ctx:
+        irs, srs = _load(ctx, index), [_load(ctx, sets[W][0]) for W in ts.WINDOWS]
+        hits, info, ran = _profile(ctx, irs, srs, 2, top)
+        assert info["n_chunks"] == n_chunks and all(ran.get(n) == len(srs) for n in TILED) and "tq_replay_kernel" not in ran, ran
+    compared = 0
+    for t in range(1, top + 1):
+        took = [i for i, W in enumerate(ts.WINDOWS) if (W, t) not in no_window]
+        assert took, (k, t)
+        with _context(k, t=t, tiled_search=2, **opts) as ctx:
+            irs, srs = _load(ctx, index), [_load(ctx, sets[ts.WINDOWS[i]][0]) for i in took]
+            ctx.set_option("kernel_timing", 1)
+            tags, _, sinfo = ctx.index_and_search(irs, srs)
+            ran = {n: v[0] for n, v in ctx.kernel_times().items()}
+        assert sinfo["n_chunks"] == n_chunks and ran.get("tq_replay_kernel") == ran.get("tq_probe_kernel") == len(took), (t, ran)
+        assert "tq_hits_replay_kernel" not in ran and not any(n.startswith("search_") for n in ran), (t, ran)
+        for i, tg in zip(took, tags):
+            found = util.bools_from_bits(tg, len(hits[i]))
+            assert np.array_equal(found, hits[i] >= t), (k, n_chunks, cap, t, ts.WINDOWS[i], np.flatnonzero(found != (hits[i] >= t))[:8])
+            assert t < top or not found.any(), (k, t, ts.WINDOWS[i])
+            compared += t <= T
+    assert compared == len(ts.WINDOWS) * T - len(left_out)
+
+
 # ---- 2. filter and strand independence ------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("case", [0, 1])
 def test_filter_and_strand_independence(case):

@@ -20,6 +20,8 @@ stream synchronise and the copy back) and then runs once more with option kernel
                     default (auto),
                     fresh child processes alternating over `--rounds`, the hit arrays byte-compared; the timed calls find the (k, 1) query
                     list cached, `first_call` is the warm-up call that builds it (tq_count / tq_fill and the allocation)
+  --parent-tiled    with --tiled and --jobs-lib: one more leg, `parent_tiled2`, --jobs-lib at profile_tiled = 2 (a parent that has the
+                    option: the like-for-like partner of `tiled2` when the tiled kernels themselves changed)
   python tools/hits_bench.py [--reads 10000000] [--read-len 100] [-k 32] [--max-t 8] [--rounds 2] [--reps 3] [--out FILE]"""
 import argparse
 import json
@@ -173,6 +175,7 @@ def main():
     ap.add_argument("--profile-wide", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--tiled", action="store_true")
     ap.add_argument("--profile-tiled", type=int, default=0, help=argparse.SUPPRESS)
+    ap.add_argument("--parent-tiled", action="store_true")
     ap.add_argument("--many-reads", type=int, nargs="+", default=[600_000])
     ap.add_argument("--limit", type=int, default=240, help="seconds a child may take")
     ap.add_argument("--out", default=None)
@@ -220,7 +223,8 @@ def main():
             return
         a.many_reads = a.many_reads[0]
         if a.tiled:
-            legs = ([("parent", lib_args)] if lib_args else []) + [("tiled1", ["--profile-tiled", "1"]), ("tiled2", ["--profile-tiled", "2"]), ("auto", [])]
+            legs = ([("parent", lib_args)] if lib_args else []) + ([("parent_tiled2", lib_args + ["--profile-tiled", "2"])] if a.parent_tiled else []) + \
+                   [("tiled1", ["--profile-tiled", "1"]), ("tiled2", ["--profile-tiled", "2"]), ("auto", [])]
             t = groups_leg(a, "c1", lib_args, legs)
             res = {"workload": res["workload"], "tiled": t}
             if a.out:
