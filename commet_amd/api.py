@@ -246,6 +246,9 @@ class Context:
         filter of a pass side by side in one table set, one hits_wide_kernel launch per search set and pass; "slice_wide_words" caps the
         rows); 1 = never; 0 = auto: jobs of more than 256 chunk filters whose search sets hold no read of more than 300 bases (the shape it
         was measured faster at).  The bytes do not depend on it either.
+        set_option("profile_slice", 2) takes the narrow bit-sliced tables where the wide rows do not take the call and 12 <= k <= 24: 32 x
+        "slice_words" chunk filters (up to 256) per pass in one table set, one hits_sliced_kernel launch per search set and pass; 1 = never;
+        0 = auto, which is never for now.  The bytes do not depend on it.
         set_option("profile_tiled", 2) sends every pass of one or two chunk filters over a set with 25 <= k <= 34 and at most 255 windows per
         read through the tiled probe (tq_probe_kernel, then tq_hits_replay_kernel) on the set's query list of (k, t = 1), which is cached with
         the set (ReadSet.cache_bytes counts it; the search's own list on a context of t = 1); 1 = never; 0 = auto: sets of 2^20 reads or more whose list (8 bytes per k-mer, estimated)

@@ -13,6 +13,7 @@
 #include "hit_profile.hpp"
 #include "hit_profile_group.hpp"
 #include "hit_profile_wide.hpp"
+#include "hit_profile_sliced.hpp"
 #include "hit_profile_tiled.hpp"
 #include "read_filter.hpp"
 #include "read_iter.hpp"

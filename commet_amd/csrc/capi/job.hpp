@@ -326,6 +326,29 @@ int run_wide_passes(JobRun &j, const WidePlan &w, SetLaunch launch)
     return 0;
 }
 
+// The passes of jobs and profiles through the narrow tables (c->slice_tables and the staging planes sized for gw; the descriptors
+// uploaded): a pass is one group of 32 x gw chunks, its filters built into the one table set, then every search set is scanned ONCE:
+// launch(s, c0, c1) scans set s against chunks c0 .. c1 - 1 and returns non-zero on failure, as this does at the first
+template <typename SetLaunch>
+int run_narrow_passes(JobRun &j, int gw, SetLaunch launch)
+{
+    commet_ctx *c = j.c;
+    const uint64_t n_chunks = j.n_chunks();
+    const uint64_t per_pass = 32ull * gw;
+    for (uint64_t c0 = 0; c0 < n_chunks; c0 += per_pass) {
+        const uint64_t c1 = std::min<uint64_t>(n_chunks, c0 + per_pass);
+        if (j.tm.begin_index() || launch_slice_build(c, j.index_rs, j.index_sel(), c0, (int) (c1 - c0), gw)) return 1;
+        j.n_index_launches += 2;
+        if (j.tm.end_index()) return 1;
+        for (int s = 0; s < j.n_search; ++s) {
+            if (launch(s, c0, c1)) return 1;
+            if (j.search_rs[s]->n_reads) ++j.n_search_launches;
+            if (j.tm.end_set(s)) return 1;
+        }
+    }
+    return 0;
+}
+
 // the many-small-chunks regime: the chunk filters of a group live bit-sliced in one set of tables (slice_search.hpp)
 int run_sliced(JobRun &j)
 {
@@ -345,21 +368,10 @@ int run_sliced(JobRun &j)
             const commet_readset *rs = j.search_rs[s];
             return launch_search_wide(c, rs, wide, (int) (c1 - c0), j.sel_of(s), rs->d_tags, j.cnt_at(c0, s), j.cstride());
         });
-    // narrow tables: a pass is one group of 32 x slice_gw chunks, and every search set is scanned ONCE per pass
-    const uint64_t per_pass = 32ull * j.slice_gw;
-    for (uint64_t c0 = 0; c0 < n_chunks; c0 += per_pass) {
-        const uint64_t c1 = std::min<uint64_t>(n_chunks, c0 + per_pass);
-        if (j.tm.begin_index() || launch_slice_build(c, j.index_rs, j.index_sel(), c0, (int) (c1 - c0), j.slice_gw)) return 1;
-        j.n_index_launches += 2;
-        if (j.tm.end_index()) return 1;
-        for (int s = 0; s < j.n_search; ++s) {
-            const commet_readset *rs = j.search_rs[s];
-            if (launch_search_sliced(c, rs, (int) (c1 - c0), j.slice_gw, j.sel_of(s), rs->d_tags, j.cnt_at(c0, s), j.cstride())) return 1;
-            if (rs->n_reads) ++j.n_search_launches;
-            if (j.tm.end_set(s)) return 1;
-        }
-    }
-    return 0;
+    return run_narrow_passes(j, j.slice_gw, [&](int s, uint64_t c0, uint64_t c1) {
+        const commet_readset *rs = j.search_rs[s];
+        return launch_search_sliced(c, rs, (int) (c1 - c0), j.slice_gw, j.sel_of(s), rs->d_tags, j.cnt_at(c0, s), j.cstride());
+    });
 }
 
 // the filters of chunks ci .. ci + g - 1 into slots 0 .. g - 1, their A planes interleaved with stride gs

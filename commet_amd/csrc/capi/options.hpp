@@ -90,6 +90,11 @@ int commet_set_option(commet_ctx *c, const char *name, int64_t value)
         c->profile_wide = (int) value;
         return 0;
     }
+    if (!strcmp(name, "profile_slice")) {     // commet_index_and_profile through the narrow bit-sliced tables where the wide rows do not apply: 0 auto (never, for now), 1 never, 2 whenever 12 <= k <= 24, the job has a chunk and no probes are counted
+        if (value < 0 || value > 2) return fail("profile_slice must be 0, 1 or 2");
+        c->profile_slice = (int) value;
+        return 0;
+    }
     if (!strcmp(name, "max_kmer")) {          // chunk size in k-mers (0 = the reference's constant); changes the chunking
         if (value < 0) return fail("max_kmer must be >= 0");
         c->max_kmer_test = (uint64_t) value;

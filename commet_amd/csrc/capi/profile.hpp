@@ -26,8 +26,12 @@
 // which counts where tq_replay_kernel stops.  Sparse passes, wave-per-read sets, groups of three filters and more, and sets with no
 // room for the list or the result bytes run what they ran before.  0 = auto: sets of 2^20 reads and more whose list stays within
 // query_list_max_mb (profile_tiled_ok below; MEASUREMENTS.md, "Tiled probe"); 1 = never.
-// Not done here: profiles through the narrow bit-sliced tables, and a profile form of commet_index_many_and_search (each a pass
-// function for one of the two shared loops).
+//
+// Up to 256 chunks a pass at 12 <= k <= 24: option "profile_slice" = 2 takes the narrow bit-sliced tables where the wide rows do not take the call
+// (run_profile_sliced below; hit_profile_sliced.hpp): the chunk filters of a pass, 32 x gw of them (gw as a job's: option "slice_words",
+// the 1 GiB clamp), in one table set built by run_narrow_passes (job.hpp) as a job's are, and ONE hits_sliced_kernel launch per search
+// set and pass.  No room for the tables: the slot loop.  1 = never; 0 = auto, which is never for now (MEASUREMENTS.md, "Hit profile").
+// Not done here: a profile form of commet_index_many_and_search (a pass function for the slot loop).
 #pragma once
 
 namespace {
@@ -213,6 +217,35 @@ int run_profile_wide(JobRun &j, int max_hits, const std::vector<uint64_t> &at, u
     });
 }
 
+// does the call take the narrow tables (when the wide rows do not)?  Option "profile_slice": 2 whenever k allows it, the job has a chunk
+// and no probes are counted; 1 never; 0 auto: never, until the measurements say where (MEASUREMENTS.md, "Hit profile")
+bool profile_slice_ok(const commet_ctx *c, uint64_t n_chunks)
+{
+    return c->profile_slice == 2 && !c->count_probes && c->k >= SLICE_MIN_K && c->k <= SLICE_MAX_K && n_chunks > 0;
+}
+
+// the profile through the narrow tables: the passes of run_narrow_passes (job.hpp), 32 x gw chunks each, every search set scanned once
+// per pass by hits_sliced_kernel; gw as a job's (slice_entry_words: option "slice_words", the 1 GiB clamp).  at[s] = where set s's
+// bytes start in c->d_hits.  *taken = false: no room for the tables, nothing was launched and the caller takes the slot loop
+int run_profile_sliced(JobRun &j, int max_hits, const std::vector<uint64_t> &at, unsigned long long *d_walked, bool want_times, bool *taken)
+{
+    commet_ctx *c = j.c;
+    const uint64_t n_chunks = j.n_chunks();
+    *taken = false;
+    const int gw = slice_entry_words(c, n_chunks);
+    if (ensure_slice_buffers(c, gw, n_chunks)) {
+        (void) hipGetLastError();
+        return 0;
+    }
+    *taken = true;
+    if (upload_chunk_descriptors(j)) return 1;
+    const uint64_t per_pass = 32ull * gw;
+    j.tm.timed = want_times && ((n_chunks + per_pass - 1) / per_pass) * (uint64_t) (j.n_search + 2) <= 16384;
+    return run_narrow_passes(j, gw, [&](int s, uint64_t c0, uint64_t c1) {
+        return launch_hits_sliced(c, j.search_rs[s], (int) (c1 - c0), gw, max_hits, j.sel_of(s), c->d_hits + at[(size_t) s], d_walked);
+    });
+}
+
 }  // namespace
 
 extern "C" {
@@ -241,8 +274,9 @@ int commet_index_and_profile(commet_ctx *c, const commet_readset *index_rs, cons
     const uint64_t n_chunks = j.n_chunks();
     j.tm.timed = info != nullptr && n_chunks * (uint64_t) (n_search + 4) <= 16384;
     int rc = 0;
-    bool wide = false;
+    bool wide = false;                             // the call went through bit-sliced tables, wide or narrow
     if (profile_wide_ok(c, n_chunks, n_search, search_rs)) rc = run_profile_wide(j, max_hits, at, d_walked, info != nullptr, &wide);
+    else if (profile_slice_ok(c, n_chunks)) rc = run_profile_sliced(j, max_hits, at, d_walked, info != nullptr, &wide);
     // the job's slot loop with a cap rule of its own (no group8_ok condition: the hits kernels keep no masks)
     const int group_cap = (c->k >= 2 && n_chunks >= 2) ? std::max(1, std::min(8, c->chunk_group)) : 1;
     if (!rc && !wide)

@@ -593,15 +593,22 @@ int launch_search_tiled(commet_ctx *c, const commet_readset *rs, int g, int slot
     });
 }
 
-// words per bit-sliced entry (32 chunk filters per word) for a job of n_chunks chunks; 0 = the job takes the slot path
+// words per bit-sliced entry (32 chunk filters per word) of the narrow tables for n_chunks >= 1 chunks at SLICE_MIN_K <= k <= SLICE_MAX_K:
+// option "slice_words", else by the chunk count; clamped
+int slice_entry_words(const commet_ctx *c, uint64_t n_chunks)
+{
+    int gw = c->slice_gw ? c->slice_gw : n_chunks > 128 ? 8 : n_chunks > 64 ? 4 : n_chunks > 32 ? 2 : 1;
+    while (gw > 1 && (((uint64_t) 16 * gw) << c->k) > (1ull << 30)) gw /= 2;   // the four tables: at most 1 GiB
+    return gw;
+}
+
+// the same for a job of n_chunks chunks; 0 = the job takes the slot path
 int slice_words(const commet_ctx *c, uint64_t n_chunks)
 {
     if (c->slice_mode == 1 || c->count_probes) return 0;
     if (c->k < SLICE_MIN_K || c->k > SLICE_MAX_K || n_chunks == 0) return 0;
     if (c->slice_mode == 0 && n_chunks < 8) return 0;
-    int gw = c->slice_gw ? c->slice_gw : n_chunks > 128 ? 8 : n_chunks > 64 ? 4 : n_chunks > 32 ? 2 : 1;
-    while (gw > 1 && (((uint64_t) 16 * gw) << c->k) > (1ull << 30)) gw /= 2;   // the four tables: at most 1 GiB
-    return gw;
+    return slice_entry_words(c, n_chunks);
 }
 
 int ensure_slice_buffers(commet_ctx *c, int gw, uint64_t n_chunks)
@@ -650,6 +657,21 @@ int launch_search_sliced(commet_ctx *c, const commet_readset *rs, int g, int gw,
     with_value<1, 2, 4, 8>(gw, [&](auto GW) {
         COMMET_LAUNCH(search_sliced_kernel<GW>, grid, block, 0, c->stream, rs->view(), c->slice_tables, c->k, t_eff(c, rs), g, d_sel, d_tags,
                       d_counters, cstride, block_stride);
+    });
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+// one pass of rs over the g chunk filters in the narrow tables (hit_profile_sliced.hpp)
+int launch_hits_sliced(commet_ctx *c, const commet_readset *rs, int g, int gw, int max_hits, const uint64_t *d_sel, uint8_t *d_hits,
+                       unsigned long long *d_walked)
+{
+    if (rs->n_reads == 0) return 0;
+    if (launch_size_ok(rs->n_reads)) return 1;
+    const dim3 grid((unsigned) ((rs->n_reads + 255) / 256)), block(256);
+    KScope ks(c, "hits_sliced_kernel", c->stream);
+    with_value<1, 2, 4, 8>(gw, [&](auto GW) {
+        COMMET_LAUNCH(hits_sliced_kernel<GW>, grid, block, 0, c->stream, rs->view(), c->slice_tables, c->k, max_hits, g, d_sel, d_hits, d_walked);
     });
     HIP_OK(hipGetLastError());
     return 0;

@@ -580,6 +580,7 @@ struct commet_ctx {
     int slice_wide = 0;               // option: wide rows (all chunk filters side by side, slice_search.hpp): 0 auto (more than 256 chunks), 1 never, 2 whenever the regime applies
     uint32_t wide_cap_words = 0;      // option "slice_wide_words": at most this many words per row (tests: several passes); 0 = the budget decides
     int profile_wide = 0;             // option: commet_index_and_profile through the wide rows (hit_profile_wide.hpp): 0 auto (more than 256 chunks, no search read of more than 300 bases), 1 never, 2 whenever 12 <= k <= 24 and the job has a chunk
+    int profile_slice = 0;            // option: commet_index_and_profile through the narrow bit-sliced tables (hit_profile_sliced.hpp) where the wide rows do not apply: 0 auto (never, for now), 1 never, 2 whenever 12 <= k <= 24, the job has a chunk and no probes are counted
     uint32_t *wide_tables = nullptr;
     uint64_t wide_table_words = 0;
     uint64_t max_kmer_test = 0;       // option "max_kmer": chunk size override for tests (0 = the reference's constant)

@@ -1,6 +1,6 @@
 """Threshold sweep: the `.bv` vectors of `index_and_search -t t` for every t in 1..T from ONE profile job.
 
-    python -m commet_amd.sweep -i index.txt -s search.txt -k K --max-t T -o OUT [--chunk-group N] [--profile-wide {0,1,2}] [--profile-tiled {0,1,2}]
+    python -m commet_amd.sweep -i index.txt -s search.txt -k K --max-t T -o OUT [--chunk-group N] [--profile-wide {0,1,2}] [--profile-slice {0,1,2}] [--profile-tiled {0,1,2}]
 
 -i / -s take the reference's set-config grammar (`name:file[,bv];file[,bv]...`, one set per line; the index file holds exactly one
 set).  The sets are parsed and packed by the library's own ingest (ReadSet.from_fasta), one Context.index_and_profile(max_hits=T) gives a hit count per read, and
@@ -12,6 +12,8 @@ The filters, which do not depend on t, are built once instead of T times, and ev
 --chunk-group chunk filters (1..8, the library's option "chunk_group"; default: the library's, 8); the closing line reports the
 passes that took.  --profile-wide (the library's option "profile_wide") 2 takes the wide bit-sliced rows at 12 <= k <= 24 instead:
 all chunk filters side by side, one pass per search set unless the rows are capped; 1 never, 0 the library's choice (default).
+--profile-slice (the library's option "profile_slice") 2 takes the narrow bit-sliced tables at 12 <= k <= 24 where the wide rows do not
+take the call: up to 256 chunk filters per pass; 1 never, 0 the library's choice (default: never).
 --profile-tiled (the library's option "profile_tiled") 2 sends passes of one or two chunk filters at 25 <= k <= 34 through the tiled
 probe; 1 never, 0 the library's choice (default: sets of 2^20 reads and more whose query list fits its cap).
 No .log files are written: the reference's `searched`
@@ -79,6 +81,8 @@ def parser():
     p.add_argument("--chunk-group", dest="chunk_group", type=int, default=None, help="chunk filters per search pass (1..8; default: the library's)")
     p.add_argument("--profile-wide", dest="profile_wide", type=int, default=None, choices=(0, 1, 2),
                    help="the profile through the wide bit-sliced rows (12 <= k <= 24): 0 the library's choice, 1 never, 2 always")
+    p.add_argument("--profile-slice", dest="profile_slice", type=int, default=None, choices=(0, 1, 2),
+                   help="the profile through the narrow bit-sliced tables (12 <= k <= 24, up to 256 chunk filters a pass): 0 the library's choice, 1 never, 2 always")
     p.add_argument("--profile-tiled", dest="profile_tiled", type=int, default=None, choices=(0, 1, 2),
                    help="the profile through the tiled probe (25 <= k <= 34, passes of one or two chunk filters): 0 the library's choice, 1 never, 2 always")
     p.add_argument("--device", type=int, default=0)
@@ -109,6 +113,8 @@ def main(argv=None):
             ctx.set_option("chunk_group", a.chunk_group)
         if a.profile_wide is not None:
             ctx.set_option("profile_wide", a.profile_wide)
+        if a.profile_slice is not None:
+            ctx.set_option("profile_slice", a.profile_slice)
         if a.profile_tiled is not None:
             ctx.set_option("profile_tiled", a.profile_tiled)
         hits, info = ctx.index_and_profile(irs, [l[2] for l in loaded], isel, [l[4] for l in loaded], max_hits=a.max_t)

@@ -331,7 +331,14 @@ int commet_index_many_and_search(commet_ctx *ctx, int n_jobs, const commet_reads
  * with the same code (tq_collect, tq_sweep); the search then stops at t hits and walks the tails, the profile counts the full hits
  * greedily per filter and strand.  Sparse passes, sets that take long_search, groups
  * of three filters and more, count_probes, and sets without room for the list run the kernels above.  The bytes do not depend on it.
- * Not done here: profiles through the narrow bit-sliced tables, and a profile form of commet_index_many_and_search. */
+ * Up to 256 chunks a pass (12 <= k <= 24), by option "profile_slice" where the wide rows do not take the call: the chunk filters of a pass, 32 x
+ * slice_words of them, in the narrow bit-sliced tables (as option "slice_mode" of a job; slice_words and its 1 GiB clamp apply), ONE
+ * hits_sliced_kernel launch per search set and pass, a lane per read: a row pass over every window ANDs all four planes and counts,
+ * per chunk and strand, the blocks of k window ends that hold a full hit (1: the count is 1; 2: it is 1 or 2; three or more: at least
+ * 2), and a chunk is replayed exactly only while its upper bound exceeds the read's best count so far.  Several passes fold by the
+ * bytes' max; no room for the tables: the loop above.  search_launches, reads_scanned and index_launches (2 per pass) as for the wide
+ * rows.  The bytes do not depend on it.
+ * Not done here: a profile form of commet_index_many_and_search. */
 int commet_index_and_profile(commet_ctx *ctx, const commet_readset *index_rs, const uint8_t *index_select,
                              int n_search, const commet_readset *const *search_rs, const uint8_t *const *search_select,
                              int max_hits, uint8_t *const *hits_out, commet_job_info *info);
@@ -366,6 +373,9 @@ int commet_index_and_profile(commet_ctx *ctx, const commet_readset *index_rs, co
  *   profile_wide (0/1/2) commet_index_and_profile through the wide rows (hits_wide_kernel): 0 = jobs of more than 256 chunks whose
  *                        search sets hold no read of more than 300 bases (measured on 150-base reads), 1 = never (the slot loop,
  *                        launch for launch), 2 = whenever 12 <= k <= 24 and the job has a chunk; slice_wide_words caps its rows too
+ *   profile_slice (0/1/2) commet_index_and_profile through the narrow bit-sliced tables (hits_sliced_kernel) where profile_wide does not take
+ *                        the call: 0 = auto: never, until it is measured to pay, 1 = never, 2 = whenever 12 <= k <= 24, the job has a
+ *                        chunk and count_probes is off; slice_words sets the chunk filters per pass as in a job
  *   profile_tiled (0/1/2) commet_index_and_profile through the tiled probe (tq_hits_replay_kernel): 0 = auto: sets of 2^20 reads or more whose
  *                        list, estimated at 8 bytes per k-mer, stays within query_list_max_mb (the bounds of tiled_search), 1 = never, 2 = every pass of one or two chunk filters over a set
  *                        with 25 <= k <= 34, 1..255 windows per read and fewer than 2^32 k-mers (tests; sets below 2^20 reads too);

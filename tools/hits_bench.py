@@ -15,6 +15,10 @@ stream synchronise and the copy back) and then runs once more with option kernel
                     when --many-reads is given more than once, on every further read count (2 000 000 reads cross 1 024 chunks), the
                     profile on --jobs-lib (the parent commit's build), at profile_wide = 1 and at profile_wide = 2, fresh child processes
                     alternating over `--rounds`, the three hit arrays byte-compared; one job at t = 5 gives the break-even T
+  --sliced          ONLY the profile_slice leg (needs --many-chunks): on every read count of --many-reads (k = 21, 150 bp; 200 000 and 450 000
+                    reads cross about 107 and about 240 chunk filters, one pass of the narrow tables) the profile at profile_slice = 1 (the
+                    slot loop) and at profile_slice = 2 (hits_sliced_kernel), fresh child processes alternating over `--rounds`, the hit
+                    arrays byte-compared, the per-kernel times of both legs reported
   --tiled           ONLY the profile_tiled leg, on the configs[1] shape (--reads, --read-len, -k): the profile on --jobs-lib (the parent
                     commit's build), at profile_tiled = 1 (the slot loop), at profile_tiled = 2 (tq_probe_kernel + tq_hits_replay_kernel) and at the
                     default (auto),
@@ -61,6 +65,8 @@ def child_profile(a):
             ctx.set_option("profile_wide", a.profile_wide)
         if a.profile_tiled:
             ctx.set_option("profile_tiled", a.profile_tiled)
+        if a.profile_slice:
+            ctx.set_option("profile_slice", a.profile_slice)
         irs = commet_amd.ReadSet.from_files(ctx, [(b0, o0)])
         qrs = commet_amd.ReadSet.from_files(ctx, [(b1, o1)])
         _, first = ctx.index_and_profile(irs, [qrs], max_hits=a.max_t)           # warm-up (workspaces; the tiled leg's query list)
@@ -173,6 +179,8 @@ def main():
     ap.add_argument("--hits-name", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--wide", action="store_true")
     ap.add_argument("--profile-wide", type=int, default=0, help=argparse.SUPPRESS)
+    ap.add_argument("--sliced", action="store_true")
+    ap.add_argument("--profile-slice", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--tiled", action="store_true")
     ap.add_argument("--profile-tiled", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--parent-tiled", action="store_true")
@@ -195,7 +203,7 @@ def main():
     from commet_amd import synth
     a.work = tempfile.mkdtemp(prefix="hits_bench_")
     try:
-        for i in (0, 1) if not a.wide else ():                                   # (the wide leg has shapes of its own)
+        for i in (0, 1) if not (a.wide or a.sliced) else ():                     # (the wide and sliced legs have shapes of their own)
             b, o = synth.synth_set(i, a.reads, a.read_len, base_set=0)
             np.save(os.path.join(a.work, f"c1{i}_b.npy"), b), np.save(os.path.join(a.work, f"c1{i}_o.npy"), o)
         res = {"workload": f"2 x {a.reads} x {a.read_len} bp, k={a.k}, t=1..{a.max_t}", "profile": [], "jobs": []}
@@ -217,6 +225,28 @@ def main():
                 print(json.dumps({"workload": shape["workload"], "hits_equal": w["hits_equal"], "job_t5_ms": shape["job_t5"]["per_t"]["5"]["total_ms"],
                                   **{name: {f: w[name][f] for f in ("total_ms", "index_ms", "search_ms", "total_ms_spread", "search_launches", "reads_walked", "chunks")}
                                      for name, _ in legs}}), flush=True)
+            if a.out:
+                os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+                open(a.out, "w").write(json.dumps(res) + "\n")
+            return
+        if a.sliced:
+            if not a.many_chunks:
+                raise SystemExit("--sliced measures the many-chunk shapes: give --many-chunks")
+            legs = [("slice1", ["--profile-slice", "1"]), ("slice2", ["--profile-slice", "2"])]
+            res = {"shapes": []}
+            for n in a.many_reads:
+                L = 150
+                for i in (0, 1):
+                    b, o = synth.synth_set(i, n, L, base_set=0)
+                    np.save(os.path.join(a.work, f"c4{i}_b.npy"), b), np.save(os.path.join(a.work, f"c4{i}_o.npy"), o)
+                shape = {"workload": f"2 x {n} x {L} bp, k=21, T={a.max_t}", "sliced": groups_leg(a, "c4", [], legs)}
+                res["shapes"].append(shape)
+                w = shape["sliced"]
+                print(json.dumps({"workload": shape["workload"], "hits_equal": w["hits_equal"],
+                                  "slice2_over_slice1": round(w["slice2"]["total_ms"] / w["slice1"]["total_ms"], 4),
+                                  **{name: {f: w[name][f] for f in ("total_ms", "index_ms", "search_ms", "total_ms_spread", "search_launches", "reads_walked", "chunks",
+                                                                    "kernels_ms")} for name, _ in legs},
+                                  "rounds_total_ms": {name: [med(c["total_ms"]) for c in w["runs"][name]] for name, _ in legs}}), flush=True)
             if a.out:
                 os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
                 open(a.out, "w").write(json.dumps(res) + "\n")
