@@ -268,6 +268,32 @@ class Context:
                                                        C.byref(info)))
         return hits, {f: getattr(info, f) for f, _ in _l.JobInfo._fields_}
 
+    def index_many_and_profile(self, index_sets, search_rs, index_selects=None, search_select=None, max_hits=8):
+        """commet_index_many_and_profile: job j indexes index_sets[j] (restricted to index_selects[j]) and profiles search_rs (under
+        search_select, the same for every job) with a cap of its own: max_hits is an int or a list with one entry per job.  The jobs
+        share hits passes over the search set where the library can arrange it (up to eight chunk filters a pass, a job never split;
+        set_option("multi_job", 1): job by job).  The same read set may appear in several jobs under different selections.
+        Returns (hits, info): hits[j] = np.uint8 per read of search_rs, byte for byte what
+        index_and_profile(index_sets[j], [search_rs], index_selects[j], [search_select], max_hits[j]) gives for job j alone; info sums
+        over the jobs (search_launches = the passes)."""
+        nj = len(index_sets)
+        caps = [int(max_hits)] * nj if np.isscalar(max_hits) else [int(x) for x in max_hits]
+        if len(caps) != nj:
+            raise CommetError(f"max_hits: need one entry per job ({nj}), got {len(caps)}")
+        isel = [None] * nj
+        if index_selects is not None:
+            isel = [_as_bits(s, rs.num_reads, "index_select") for s, rs in zip(index_selects, index_sets)]
+        ssel = _as_bits(search_select, search_rs.num_reads, "search_select")
+        hits = [np.zeros(search_rs.num_reads, dtype=np.uint8) for _ in range(nj)]
+        rs_arr = (C.c_void_p * max(nj, 1))(*[rs._h for rs in index_sets])
+        sel_arr = (C.c_void_p * max(nj, 1))(*[(_ptr(s).value if s is not None else None) for s in isel])
+        cap_arr = (C.c_int * max(nj, 1))(*caps)
+        hit_arr = (C.c_void_p * max(nj, 1))(*[(_ptr(h).value if h.size else None) for h in hits])
+        info = _l.JobInfo()
+        self._check(self._lib.commet_index_many_and_profile(self._h, nj, rs_arr, sel_arr, search_rs._h, _ptr(ssel), cap_arr, hit_arr,
+                                                            C.byref(info)))
+        return hits, {f: getattr(info, f) for f, _ in _l.JobInfo._fields_}
+
     def poison(self, byte):
         """test hook: every bit array of the context (filter slots, interleaved A planes, bit-sliced planes and tables) filled with `byte`"""
         self.set_option("poison", byte)

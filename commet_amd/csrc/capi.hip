@@ -12,6 +12,7 @@
 #include "long_search.hpp"
 #include "hit_profile.hpp"
 #include "hit_profile_group.hpp"
+#include "hit_profile_jobs.hpp"
 #include "hit_profile_wide.hpp"
 #include "hit_profile_sliced.hpp"
 #include "hit_profile_tiled.hpp"
@@ -61,5 +62,6 @@
 #include "capi/job.hpp"              // commet_index_reads / _search_reads / _index_and_search
 #include "capi/multi.hpp"            // commet_index_many_and_search: several jobs on one search set, their filters in one pass
 #include "capi/profile.hpp"          // commet_index_and_profile: per-read hit counts, the tags of every t from one job
+#include "capi/multi_profile.hpp"    // commet_index_many_and_profile: several profile jobs on one search set, their filters in one hits pass
 #include "capi/options.hpp"          // commet_set_option, measurement hooks
 #include "capi/microbench.hpp"       // commet_membench / _ldsbench

@@ -1,0 +1,296 @@
+// capi/multi_profile.hpp — commet_index_many_and_profile: several commet_index_and_profile jobs that search the SAME read set, their chunk filters
+// side by side in one hits pass (a part of the one translation unit capi.hip: included there, in order, after multi.hpp and profile.hpp)
+//
+// The threshold sweep of the symmetric comparison (commet_amd/sweep.py --full) runs, for every t, "A in (B restricted to the reads
+// found at t)": T jobs that index selections of ONE set and all search A.  Alone each job walks A and makes its plane-A gathers,
+// which depend on the read alone; with the chunk filters of up to eight slots of several such jobs in one pass (A planes
+// interleaved, hits_jobs_kernel, hit_profile_jobs.hpp) the set is walked once per pass.  Every job's bytes are what
+// commet_index_and_profile gives for it alone — tested against exactly that, and against the CPU checker.
+//
+// A pass: the jobs in their order while their chunks fit min(8, chunk_group) slots (a job that runs alone does not close a pass);
+// a job is never split, so its byte array is written by one pass.  The jobs are planned on the device (plan_index_on_device) and
+// built one after the other on the context's one stream — jobs may index the same set under different selections: the selection
+// bitmap, and the list made of it, go up in front of each job's build — a chunk that does not take the bucketed build into a zeroed
+// slot.  The search selection is the same for all jobs and reaches the kernel as the visited bitmap of plan_search: no list form.
+//
+// Through commet_index_and_profile itself, same bytes: the whole call when n_jobs < 2, k < 2, count_probes, multi_job = 1,
+// chunk_group = 1, the search set is empty or takes the wave-per-read hits kernel, or the device has no room for the slots or the
+// byte arrays; a single job that the device planner does not take (an empty read in the set, a file without a selected read, an
+// empty selection), that has no chunk or more chunks than a pass holds, or that is left alone in its pass — it picks its own regime
+// (wide, narrow, tiled), its neighbours still share.
+// Auto (multi_job = 0) shares: measured against the jobs one by one in MEASUREMENTS.md, "Jobs that share a hits pass".
+// Not built: a wave-per-read form of the shared pass, the tiled probe or the bit-sliced tables for shared passes, passes shared
+// between jobs whose search selections differ.
+#pragma once
+
+namespace {
+
+// one commet_index_many_and_profile call
+struct ProfileManyRun {
+    commet_ctx *c;
+    int n_jobs;
+    const commet_readset *const *index_rs;
+    const uint8_t *const *index_select;
+    const commet_readset *search_rs;
+    const uint8_t *search_select;
+    const int *max_hits;
+    uint8_t *const *hits_out;
+    struct Job {
+        IndexPlan plan;
+        const uint8_t *sel = nullptr;
+        std::vector<uint64_t> chunk_pos;        // first position of every chunk in the job's list of selected reads
+        bool shares = false;                    // planned on the device, 1 .. cap chunks, each with a read
+    };
+    std::vector<Job> jobs;
+    int cap = 8;                                // slots of a pass
+    std::vector<uint8_t> vis;                   // the reads the passes visit (plan_search), unless all of them
+    bool all_visited = false;
+    uint64_t stride = 256;                      // bytes between the arrays of two jobs of a pass
+    int shared_passes = 0;
+    commet_job_info sum = commet_job_info();
+    PhaseClock clk;
+    double ph_plan = 0, ph_launch = 0, ph_wait = 0;
+    JobTimer tm;                                // one bracket per shared pass: its builds, then its one scan
+    ProfileManyRun(commet_ctx *c_, int n, const commet_readset *const *irs, const uint8_t *const *isel, const commet_readset *srs, const uint8_t *ssel,
+                   const int *caps, uint8_t *const *hits)
+        : c(c_), n_jobs(n), index_rs(irs), index_select(isel), search_rs(srs), search_select(ssel), max_hits(caps), hits_out(hits), tm(c_, true, 1)
+    {
+    }
+    const uint64_t *d_sel() const { return all_visited ? nullptr : search_rs->d_sel; }
+};
+
+// jobs j0 .. j1 - 1 through commet_index_and_profile, one after the other, summed into the call's account
+int profile_alone(ProfileManyRun &m, int j0, int j1)
+{
+    for (int j = j0; j < j1; ++j) {
+        commet_job_info ji = commet_job_info();
+        const uint8_t *ss = m.search_select;
+        uint8_t *to = m.hits_out ? m.hits_out[j] : nullptr;
+        if (commet_index_and_profile(m.c, m.index_rs[j], m.index_select ? m.index_select[j] : nullptr, 1, &m.search_rs, m.search_select ? &ss : nullptr,
+                                     m.max_hits[j], m.hits_out ? &to : nullptr, &ji))
+            return 1;
+        add_info(m.sum, ji);
+    }
+    return 0;
+}
+
+// no room for the slots or the byte arrays of a shared pass: every job through commet_index_and_profile, which degrades on its own
+// (run_slot_groups).  The single calls write every byte of every job again
+int profile_no_room(ProfileManyRun &m)
+{
+    (void) hipGetLastError();
+    m.c->cur_slot = 0;
+    m.sum = commet_job_info();
+    m.shared_passes = 0;
+    return profile_alone(m, 0, m.n_jobs);
+}
+
+// does the call share passes at all?
+bool profile_many_ok(const ProfileManyRun &m)
+{
+    const commet_ctx *c = m.c;
+    const commet_readset *srs = m.search_rs;
+    return m.n_jobs >= 2 && c->k >= 2 && !c->count_probes && c->multi_job != 1 && m.cap >= 2 && srs->n_reads > 0 && !hits_wave_ok(c, srs) &&
+           (srs->n_reads + 255) / 256 < (1ull << 24);
+}
+
+// the plan of every job the device planner takes, and the reads the passes visit (as plan_job makes them), on the device on return
+int plan_profile_many(ProfileManyRun &m)
+{
+    commet_ctx *c = m.c;
+    const uint64_t max_kmer = commet_max_kmer(c);
+    m.jobs.resize((size_t) m.n_jobs);
+    for (int j = 0; j < m.n_jobs; ++j) {
+        const commet_readset *rs = m.index_rs[j];
+        ProfileManyRun::Job &job = m.jobs[(size_t) j];
+        job.sel = m.index_select ? m.index_select[j] : nullptr;
+        if (job.sel && all_ones(job.sel, rs->n_reads)) job.sel = nullptr;
+        if (!rs->n_reads || !plan_blocks_ok(rs->files, job.sel, rs->empty_reads, max_kmer)) continue;
+        if (plan_index_on_device(c, rs, job.sel, max_kmer, &job.plan)) return 1;
+        job.shares = !job.plan.chunks.empty() && job.plan.chunks.size() <= (size_t) m.cap;
+        for (const Chunk &ch : job.plan.chunks)
+            if (!ch.n_reads) job.shares = false;
+        job.chunk_pos = chunk_positions(job.plan);
+    }
+    const commet_readset *srs = m.search_rs;
+    const uint8_t *ssel = m.search_select;
+    if (ssel && all_ones(ssel, srs->n_reads)) ssel = nullptr;
+    m.all_visited = plan_fast_ok(srs->files, ssel, srs->empty_reads, 1);
+    if (!m.all_visited) {
+        uint64_t visited = 0;
+        m.vis = (ssel && srs->empty_reads.empty()) ? plan_search_select(srs->files, ssel, srs->n_reads, &visited)
+                                                    : plan_search(srs->files, ssel, srs->empty_reads, srs->n_reads, &visited);
+    }
+    return 0;
+}
+
+// the visited reads of the search set to the device (a job that ran alone in between has put the same bits there)
+int upload_visited(ProfileManyRun &m)
+{
+    if (m.all_visited) return 0;
+    if (upload_bits(m.c, m.search_rs->d_sel, m.vis.data(), m.search_rs->n_reads)) return 1;
+    HIP_OK(hipStreamSynchronize(m.c->stream));
+    return 0;
+}
+
+int launch_hits_jobs(commet_ctx *c, const commet_readset *rs, int g, int gs, const JobSlots &js, const uint64_t *d_sel, uint8_t *d_hits, uint64_t stride,
+                     unsigned long long *d_walked)
+{
+    if (launch_size_ok(rs->n_reads)) return 1;
+    const dim3 lanes((unsigned) ((rs->n_reads + 255) / 256));
+    const FilterGroupView fg = filter_group(c, g, 0, true);
+    KScope ks(c, "hits_jobs_kernel", c->stream);
+    with_key(c->k, [&](auto key) {
+        using W = decltype(key);
+        with_value<2, 4, 8>(gs, [&](auto NF) {
+            COMMET_LAUNCH((hits_jobs_kernel<W, NF>), lanes, dim3(256), 0, c->stream, rs->view(), fg, c->k, js, d_sel, d_hits, (uint32_t) (stride / 256), d_walked);
+        });
+    });
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+// ---- a shared pass: the jobs `in_pass`, whose g chunks fit the pass's slots ------------------------------------------------------------
+// 0 = done, 1 = error, 2 = no room
+int run_shared_hits_pass(ProfileManyRun &m, const std::vector<int> &in_pass, int g)
+{
+    commet_ctx *c = m.c;
+    const commet_readset *srs = m.search_rs;
+    const int gs = g <= 2 ? 2 : g <= 4 ? 4 : 8;
+    if (ensure_slots(c, g, gs)) return 2;
+    if (m.tm.begin_index()) return 1;
+    JobSlots js{0, 0};
+    int slot = 0;
+    for (int j : in_pass) {
+        const commet_readset *rs = m.index_rs[j];
+        const ProfileManyRun::Job &job = m.jobs[(size_t) j];
+        const int nc = (int) job.plan.chunks.size();
+        const uint64_t mates = ((1ull << nc) - 1ull) << slot;
+        for (int i = slot; i < slot + nc; ++i) js.mates |= mates << (8 * i), js.caps |= (uint64_t) m.max_hits[j] << (8 * i);
+        // the job's selection, and its selected reads as a list for the bucketed build of a fixed-length set (no room: the build walks
+        // the bitmap); builds, uploads and lists are ordered on the one stream, so the set's bitmap and the context's list buffer serve
+        // job after job — two jobs on one set under two selections included
+        const uint32_t *d_ids = nullptr;
+        if (!job.plan.dense && upload_bits(c, rs->d_sel, job.plan.indexed_bits.data(), rs->n_reads)) return 1;
+        if (!job.plan.dense && rs->uniform_len != 0 && !c->part_no_uni && c->index_mode != 1 && build_selection_list(c, c->sel_ids, rs, job.plan, &d_ids)) {
+            (void) hipGetLastError();
+            d_ids = nullptr;
+        }
+        for (int ci = 0; ci < nc; ++ci, ++slot) {
+            const Chunk &ch = job.plan.chunks[(size_t) ci];
+            c->cur_slot = slot;
+            // a chunk that does not take the bucketed build (which writes every tile of its slot) meets a zeroed slot, as in build_group
+            const bool self_zeroing = would_partition(c, rs, ch.kmers, ch.last - ch.first + 1);
+            if (!self_zeroing && commet_filter_reset(c)) return 1;
+            if (launch_index(c, rs, ch.first, ch.last - ch.first + 1, job.plan.dense ? nullptr : rs->d_sel, nullptr, ch.kmers, true, !self_zeroing, 0, d_ids,
+                             d_ids ? job.chunk_pos[(size_t) ci] : 0, ch.n_reads))
+                return 1;
+            ++m.sum.index_launches;
+        }
+        m.sum.n_chunks += (uint64_t) nc, m.sum.kmers_indexed += job.plan.kmers, m.sum.reads_indexed += job.plan.indexed_reads;
+    }
+    c->cur_slot = 0;
+    if (launch_interleave(c, g, gs) || m.tm.end_index()) return 1;
+    if (hipMemsetAsync(c->d_hits, 0, in_pass.size() * m.stride, c->stream) != hipSuccess ||
+        hipMemsetAsync(c->d_jobcnt, 0, sizeof(unsigned long long), c->stream) != hipSuccess)
+        return fail("memset failed");
+    if (launch_hits_jobs(c, srs, g, gs, js, m.d_sel(), c->d_hits, m.stride, c->d_jobcnt)) return 1;
+    ++m.sum.search_launches, ++m.shared_passes;
+    if (m.tm.end_set(0)) return 1;
+    m.clk.lap(m.ph_launch);
+    HIP_OK(hipMemcpyAsync(&c->h_counters[0], c->d_jobcnt, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    for (size_t q = 0; q < in_pass.size(); ++q)
+        if (m.hits_out && m.hits_out[in_pass[q]])
+            HIP_OK(hipMemcpyAsync(m.hits_out[in_pass[q]], c->d_hits + (uint64_t) q * m.stride, srs->n_reads, hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));
+    c->kclock.collect();
+    m.sum.reads_scanned += c->h_counters[0];
+    float ms_i = 0, ms_s = 0;
+    (void) m.tm.index_ms(m.tm.brackets() - 1, &ms_i);
+    (void) m.tm.set_ms(m.tm.brackets() - 1, 0, &ms_s);
+    m.sum.index_ms += ms_i, m.sum.index_kernel_ms += ms_i, m.sum.search_ms += ms_s;
+    m.clk.lap(m.ph_wait);
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int commet_index_many_and_profile(commet_ctx *c, int n_jobs, const commet_readset *const *index_rs, const uint8_t *const *index_select,
+                                  const commet_readset *search_rs, const uint8_t *search_select, const int *max_hits, uint8_t *const *hits_out,
+                                  commet_job_info *info)
+{
+    if (n_jobs < 0) return fail("n_jobs must be >= 0");
+    if (!search_rs->finalized) return fail("search read set not finalized");
+    if (search_rs->ctx != c) return fail("search read set belongs to another context");
+    for (int j = 0; j < n_jobs; ++j) {
+        if (!index_rs[j]->finalized) return fail("index read set %d not finalized", j);
+        if (index_rs[j]->ctx != c) return fail("index read set %d belongs to another context", j);
+        if (index_rs[j] == search_rs) return fail("a set cannot be searched against itself in one call");
+        if (max_hits[j] < 1 || max_hits[j] > 255) return fail("max_hits must be in 1..255 (got %d for job %d)", max_hits[j], j);
+    }
+    HIP_OK(hipSetDevice(c->device));
+    // the sets of this call are neither exported nor offloaded while it runs (the jobs that run alone count their own sets again: in_job is a depth)
+    SetUse in_jobs(c, search_rs);
+    for (int j = 0; j < n_jobs; ++j) in_jobs.add(index_rs[j]);
+    if (in_jobs.enter()) return 1;
+    ProfileManyRun m(c, n_jobs, index_rs, index_select, search_rs, search_select, max_hits, hits_out);
+    m.cap = std::max(1, std::min(8, c->chunk_group));
+    auto finish = [&](const char *what) {
+        m.sum.total_ms = m.clk.total_ms();
+        m.sum.probes = 0;
+        if (what && c->job_verbose)
+            fprintf(stderr, "[profiles x%d%s] %d shared pass(es); plans %.2f ms, launches %.2f ms, wait + download %.2f ms\n", n_jobs, what, m.shared_passes,
+                    m.ph_plan, m.ph_launch, m.ph_wait);
+        if (info) *info = m.sum;
+        return 0;
+    };
+    if (!profile_many_ok(m)) return profile_alone(m, 0, n_jobs) || finish(nullptr);
+    if (plan_profile_many(m)) return 1;
+    m.clk.lap(m.ph_plan);
+    // the passes: the sharing jobs in their order while their chunks fit the slots (a job that runs alone does not close a pass);
+    // a pass of one job runs alone too
+    std::vector<std::vector<int>> passes(1);
+    std::vector<int> alone;
+    int g = 0;
+    for (int j = 0; j < n_jobs; ++j) {
+        const ProfileManyRun::Job &job = m.jobs[(size_t) j];
+        if (!job.shares) {
+            alone.push_back(j);
+            continue;
+        }
+        if (g + (int) job.plan.chunks.size() > m.cap) passes.emplace_back(), g = 0;
+        passes.back().push_back(j);
+        g += (int) job.plan.chunks.size();
+    }
+    size_t most = 0;
+    for (const std::vector<int> &ps : passes) {
+        most = std::max(most, ps.size());
+        if (ps.size() == 1) alone.push_back(ps[0]);
+    }
+    if (most < 2) return profile_alone(m, 0, n_jobs) || finish(nullptr);
+    // a byte per read and job of a pass (each job's bytes start on a 256-byte line), and the count of walked reads
+    m.stride = (search_rs->n_reads + 255) & ~255ull;
+    const uint64_t n_bytes = (uint64_t) most * m.stride;
+    if (grow_kept(c, c->d_hits, c->hits_cap, n_bytes, n_bytes)) return profile_no_room(m) || finish(nullptr);
+    if (grow_kept(c, c->d_jobcnt, c->jobcnt_cap, 1, 64)) return 1;
+    for (int j : alone)
+        if (profile_alone(m, j, j + 1)) return 1;
+    if (upload_visited(m)) return 1;                // (behind the jobs that ran alone: they plan the search set on their own)
+    for (const std::vector<int> &ps : passes) {
+        if (ps.size() < 2) continue;
+        g = 0;
+        for (int j : ps) g += (int) m.jobs[(size_t) j].plan.chunks.size();
+        const int rc = run_shared_hits_pass(m, ps, g);
+        c->cur_slot = 0;
+        if (rc == 1) {
+            (void) hipStreamSynchronize(c->stream);     // (host bit arrays of the call may be on their way up)
+            return 1;
+        }
+        if (rc == 2) return profile_no_room(m) || finish(nullptr);
+    }
+    return finish("");
+}
+
+}  // extern "C"

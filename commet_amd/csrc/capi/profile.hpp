@@ -31,7 +31,7 @@
 // (run_profile_sliced below; hit_profile_sliced.hpp): the chunk filters of a pass, 32 x gw of them (gw as a job's: option "slice_words",
 // the 1 GiB clamp), in one table set built by run_narrow_passes (job.hpp) as a job's are, and ONE hits_sliced_kernel launch per search
 // set and pass.  No room for the tables: the slot loop.  1 = never; 0 = auto, which is never for now (MEASUREMENTS.md, "Hit profile").
-// Not done here: a profile form of commet_index_many_and_search (a pass function for the slot loop).
+// Several such jobs on one search set, their chunk filters in one hits pass: commet_index_many_and_profile (capi/multi_profile.hpp).
 #pragma once
 
 namespace {

@@ -338,10 +338,35 @@ int commet_index_many_and_search(commet_ctx *ctx, int n_jobs, const commet_reads
  * 2), and a chunk is replayed exactly only while its upper bound exceeds the read's best count so far.  Several passes fold by the
  * bytes' max; no room for the tables: the loop above.  search_launches, reads_scanned and index_launches (2 per pass) as for the wide
  * rows.  The bytes do not depend on it.
- * Not done here: a profile form of commet_index_many_and_search. */
+ * Several such jobs on one search set: commet_index_many_and_profile below. */
 int commet_index_and_profile(commet_ctx *ctx, const commet_readset *index_rs, const uint8_t *index_select,
                              int n_search, const commet_readset *const *search_rs, const uint8_t *const *search_select,
                              int max_hits, uint8_t *const *hits_out, commet_job_info *info);
+/* Several hit-profile jobs that search the SAME read set, in one call: job j indexes index_rs[j] (restricted to index_select[j], may
+ * be NULL) and searches search_rs under search_select (may be NULL; the same for every job) with max_hits[j] in 1..255.
+ * hits_out[j] (n bytes, n = the reads of search_rs) is byte for byte what commet_index_and_profile(ctx, index_rs[j],
+ * index_select[j], 1, &search_rs, &search_select, max_hits[j], ...) gives for job j alone.  Jobs may index the same read set under
+ * different selections (the threshold sweep of the symmetric comparison does: commet_amd/sweep.py --full).
+ * The jobs, in their order, share a hits pass while their chunk filters fit min(8, chunk_group) slots (a job that runs alone, see below,
+ * does not close a pass), a job never split between two passes:
+ * one walk of a read and one plane-A request per window serve the filters of every job of the pass (hits_jobs_kernel, a lane per
+ * read); per job the byte is min(max_hits[j], max over ITS chunks of max(F, R)), and a job that reaches its cap stops for itself
+ * alone.  The jobs' chunks are built one after the other on the context's stream (index_lanes plays no part here).
+ * Through commet_index_and_profile itself, with the same bytes: every job when n_jobs < 2, k < 2, under count_probes, with option
+ * "multi_job" = 1 or "chunk_group" = 1, for an empty search set or one that takes the wave-per-read hits kernel ("long_search"),
+ * and when the device has no room for the slots or the byte arrays of a pass; a single job when the device planner does not take it
+ * (an empty read in its set, a file without a selected read, an empty selection), when it has no chunk or more chunks than a pass
+ * holds, or when it is alone in its pass — such a job picks its own regime (wide rows, narrow tables, tiled probe) and its
+ * neighbours still share.  "multi_job" = 0 (auto) shares, as 2 does: measured faster than the jobs one by one (MEASUREMENTS.md,
+ * "Jobs that share a hits pass").
+ * info (may be NULL) sums over the jobs: search_launches = the passes (plus the launches of the jobs that ran alone), reads_scanned =
+ * the reads the passes walked, probes = 0.
+ * Open: a wave-per-read form of the shared pass; the tiled probe and the bit-sliced tables for shared passes; shared passes for jobs
+ * whose search selections differ (the third pass of the symmetric sweep). */
+int commet_index_many_and_profile(commet_ctx *ctx, int n_jobs, const commet_readset *const *index_rs,
+                                  const uint8_t *const *index_select, const commet_readset *search_rs,
+                                  const uint8_t *search_select, const int *max_hits, uint8_t *const *hits_out,
+                                  commet_job_info *info);
 
 /* ---- test / measurement hooks --------------------------------------------- */
 /* Tunables / diagnostics, by name.  Unknown names are an error.  None of them changes a result bit, except the test
@@ -385,7 +410,8 @@ int commet_index_and_profile(commet_ctx *ctx, const commet_readset *index_rs, co
  *                        larger lists — a 50 M-read set's is 11 GB — pay in long-lived contexts only: allocating them costs
  *                        15-30 ms per GiB; lists of more than 4 GiB are built for a set's second eligible scan)
  *   multi_job (0/1/2)    commet_index_many_and_search: 0 = chunk filters of several jobs in one pass where possible (search sets that
- *                        take long_search: job by job), 1 = job by job, 2 = as 0, and search sets that take long_search share passes too
+ *                        take long_search: job by job), 1 = job by job, 2 = as 0, and search sets that take long_search share passes too;
+ *                        commet_index_many_and_profile: 0 and 2 = jobs share hits passes where possible, 1 = job by job
  *   sparse_search (0/1/2) a pass over a SELECTION of a search set (a filter bv that leaves few reads: file_manager.h:88-112 skips the
  *                        others) walks the list of the selected, not yet tagged reads instead of the set's bitmap, so that every
  *                        lane of a wave has a read: 0 = when the host plan visits less than half of the set's reads, 1 = never,

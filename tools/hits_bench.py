@@ -26,6 +26,11 @@ stream synchronise and the copy back) and then runs once more with option kernel
                     list cached, `first_call` is the warm-up call that builds it (tq_count / tq_fill and the allocation)
   --parent-tiled    with --tiled and --jobs-lib: one more leg, `parent_tiled2`, --jobs-lib at profile_tiled = 2 (a parent that has the
                     option: the like-for-like partner of `tiled2` when the tiled kernels themselves changed)
+  --jobs N          ONLY the many-job leg (measured at --reads 5000000: 2 x 5 M x 100 bp, k = 32, the shape the tiled profile was measured
+                    on): N jobs, each indexing a disjoint N-th of set 0 by selection, all searching set 1 with max_hits = --max-t;
+                    (a) `alone`: the jobs one by one through commet_index_and_profile at its own auto choices, (b) `shared`: ONE
+                    commet_index_many_and_profile call; fresh child processes alternating over `--rounds`, the N byte arrays compared
+                    first, then per leg the median over the rounds of the per-process median wall time of the N jobs, and its spread
   python tools/hits_bench.py [--reads 10000000] [--read-len 100] [-k 32] [--max-t 8] [--rounds 2] [--reps 3] [--out FILE]"""
 import argparse
 import json
@@ -127,6 +132,75 @@ def child_jobs(a):
     print("RESULT " + json.dumps(out), flush=True)
 
 
+def child_many(a):
+    """the --jobs leg: a.n_jobs jobs on disjoint parts of set 0, all searching set 1; a.share: one many-job call, else one call per job"""
+    import time
+    import commet_amd
+    (b0, o0), (b1, o1) = _sets(a.work, a.tag)
+    out = {}
+    with commet_amd.Context(k=a.k, t=2) as ctx:
+        irs = commet_amd.ReadSet.from_files(ctx, [(b0, o0)])
+        qrs = commet_amd.ReadSet.from_files(ctx, [(b1, o1)])
+        n = irs.num_reads
+        part = np.arange(n) * a.n_jobs // n                                      # read r belongs to job r * N // n
+        sels = []
+        for j in range(a.n_jobs):
+            bits = np.zeros(n // 8 + 1, dtype=np.uint8)
+            packed = np.packbits(part == j, bitorder="little")
+            bits[:packed.size] = packed
+            sels.append(bits)
+
+        def call():
+            """-> (hits per job, summed info, wall ms); every library call ends in a stream synchronise and the copy back"""
+            t0 = time.perf_counter()
+            if a.share:
+                hits, info = ctx.index_many_and_profile([irs] * a.n_jobs, qrs, index_selects=sels, max_hits=a.max_t)
+            else:
+                hits, info = [], {}
+                for sel in sels:
+                    h, i = ctx.index_and_profile(irs, [qrs], index_select=sel, max_hits=a.max_t)
+                    hits.append(h[0])
+                    info = {f: info.get(f, 0) + i[f] for f in i}
+            return hits, info, (time.perf_counter() - t0) * 1e3
+
+        _, first, first_ms = call()                                              # warm-up (slots, workspaces, the query list of a tiled pass)
+        out["first_call_ms"] = round(first_ms, 3)
+        calls = [call() for _ in range(a.reps)]
+        hits, info, _ = calls[-1]
+        ctx.set_option("kernel_timing", 1)
+        call()
+        out["kernels_ms"] = _kernels(ctx)
+        ctx.set_option("kernel_timing", 0)
+        out["wall_ms"] = [round(c[2], 3) for c in calls]
+        out["index_ms"] = [round(c[1]["index_ms"], 3) for c in calls]
+        out["search_ms"] = [round(c[1]["search_ms"], 3) for c in calls]
+        out["chunks"], out["search_launches"], out["reads_walked"] = int(info["n_chunks"]), int(info["search_launches"]), int(info["reads_scanned"])
+        out["found_per_job"] = [int((h > 0).sum()) for h in hits]
+        np.save(os.path.join(a.work, a.hits_name), np.stack(hits))
+    print("RESULT " + json.dumps(out), flush=True)
+
+
+def many_leg(a):
+    legs = [("alone", ["--n-jobs", str(a.jobs)]), ("shared", ["--n-jobs", str(a.jobs), "--share"])]
+    runs = {name: [] for name, _ in legs}
+    equal = []
+    for r in range(a.rounds):
+        for name, extra in legs:
+            runs[name].append(run_child(a, "many", "c1", a.limit, extra + ["--hits-name", f"many_{name}.npy"]))
+            print(f"round {r} {name}: wall ms {runs[name][-1]['wall_ms']}", file=sys.stderr, flush=True)
+        equal.append(bool(np.array_equal(np.load(os.path.join(a.work, "many_alone.npy")), np.load(os.path.join(a.work, "many_shared.npy")))))
+    out = {"hits_equal": all(equal), "runs": runs}
+    for name, _ in legs:
+        per = [med(c["wall_ms"]) for c in runs[name]]
+        out[name] = {"wall_ms": round(med(per), 3), "rounds_wall_ms": per, "wall_ms_spread": round((max(per) - min(per)) / med(per), 4),
+                     "index_ms": round(med([med(c["index_ms"]) for c in runs[name]]), 3), "search_ms": round(med([med(c["search_ms"]) for c in runs[name]]), 3),
+                     "first_call_ms": round(med([c["first_call_ms"] for c in runs[name]]), 3), "chunks": runs[name][0]["chunks"],
+                     "search_launches": runs[name][0]["search_launches"], "reads_walked": runs[name][0]["reads_walked"], "kernels_ms": runs[name][0]["kernels_ms"]}
+    out["shared_over_alone"] = round(out["shared"]["wall_ms"] / out["alone"]["wall_ms"], 4)
+    out["found_per_job"] = runs["shared"][0]["found_per_job"]
+    return out
+
+
 def run_child(a, mode, tag, limit, extra=()):
     cmd = ["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--child", mode, "--work", a.work, "--tag", tag, "-k", str(a.k if tag == "c1" else 21),
            "--max-t", str(a.max_t), "--reps", str(a.reps)] + list(extra)
@@ -184,6 +258,9 @@ def main():
     ap.add_argument("--tiled", action="store_true")
     ap.add_argument("--profile-tiled", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--parent-tiled", action="store_true")
+    ap.add_argument("--jobs", type=int, default=0, help="N jobs on disjoint N-ths of set 0, all searching set 1: one by one against one many-job call")
+    ap.add_argument("--n-jobs", type=int, default=0, help=argparse.SUPPRESS)
+    ap.add_argument("--share", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--many-reads", type=int, nargs="+", default=[600_000])
     ap.add_argument("--limit", type=int, default=240, help="seconds a child may take")
     ap.add_argument("--out", default=None)
@@ -197,7 +274,7 @@ def main():
     if a.ts is None:
         a.ts = list(range(1, a.max_t + 1))
     if a.child:
-        return {"profile": child_profile, "jobs": child_jobs}[a.child](a)
+        return {"profile": child_profile, "jobs": child_jobs, "many": child_many}[a.child](a)
     if a.jobs_lib:
         a.jobs_lib = os.path.abspath(a.jobs_lib)
     from commet_amd import synth
@@ -252,6 +329,17 @@ def main():
                 open(a.out, "w").write(json.dumps(res) + "\n")
             return
         a.many_reads = a.many_reads[0]
+        if a.jobs:
+            if a.jobs < 2:
+                raise SystemExit("--jobs needs at least two jobs")
+            m = many_leg(a)
+            res = {"workload": f"2 x {a.reads} x {a.read_len} bp, k={a.k}, {a.jobs} jobs on disjoint parts of set 0, max_hits={a.max_t}", "many": m}
+            if a.out:
+                os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+                open(a.out, "w").write(json.dumps(res) + "\n")
+            print(json.dumps({"workload": res["workload"], "hits_equal": m["hits_equal"], "shared_over_alone": m["shared_over_alone"],
+                              "found_per_job": m["found_per_job"], "alone": m["alone"], "shared": m["shared"]}), flush=True)
+            return
         if a.tiled:
             legs = ([("parent", lib_args)] if lib_args else []) + ([("parent_tiled2", lib_args + ["--profile-tiled", "2"])] if a.parent_tiled else []) + \
                    [("tiled1", ["--profile-tiled", "1"]), ("tiled2", ["--profile-tiled", "2"]), ("auto", [])]
