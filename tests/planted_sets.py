@@ -1,5 +1,6 @@
-"""The read sets of the short-read search kernels' planted tests (test_gpu_planted_search.py on the GPU, test_planted_sets_cpu.py
-through the CPU checker alone): generators only, importable without a GPU, every case seeded and cached.
+"""The read sets of the planted tests of the short-read search kernels and of the hit-profile kernels (test_gpu_planted_search.py and
+test_gpu_planted_profile.py on the GPU, test_planted_sets_cpu.py through the CPU checker alone): generators only, importable without
+a GPU, every case seeded and cached.
 
 Every search read carries a DESIGNED count: the greedy non-overlapping full hits on its better strand in its best chunk filter (the
 hit byte of commet_index_and_profile); the read is found at t exactly when count >= t.  test_planted_sets_cpu.py proves design ==
@@ -389,3 +390,21 @@ SLOT_LADDERS = [(k, 6) for k in (16, 20, 25, 32, 33, 34)]
 SLICED_LADDERS = [(k, 300) for k in (12, 16, 21, 24)]
 JOB_LADDERS = [(25, 3), (33, 3), (32, 1)]                      # (k, chunks per index set)
 LARGEST_K = 36                                                  # family A alone, against the key-level checker
+
+# ---- the cases of the hit-profile kernels (test_gpu_planted_profile.py), proved as BYTES by test_planted_sets_cpu.py -------------------
+# the tiled profile takes sets of at most 255 complete windows per read: the t = 1 sweeps above (reads of fhw + k - 1 bases), and for
+# counts above 1 sweeps at t = 3 over the shorter first-hit ranges (129 + 2 k windows in the longest fixed-length read: 197 at k = 34)
+TILED_KS = (25, 32, 33, 34)
+TILED_WINDOWS = 255
+TILED_SWEEPS = [(k, 1, 6, FHW, 0) for k in TILED_KS] + [(k, 3, 6, SLICED_FHW, 0) for k in TILED_KS]
+TILED_LADDERS = [(k, 6) for k in TILED_KS]
+WIDE_PROFILE_KS = (12, 16, 21)                                  # (the k of the search file's wide rows)
+# (profile_wide_ok takes every k the tables have, so the ladder also runs at their largest: rows of 128 bytes, tables of 8 GiB)
+WIDE_PROFILE_LADDERS = [(k, 300) for k in WIDE_PROFILE_KS + (24,)]
+# two index sets of 1, 2 and 3 chunks: passes of 2, 4 and 6 filter slots (hits_jobs_kernel<., 2 | 4 | 8>), 32-bit keys and 64-bit keys
+PROFILE_JOB_LADDERS = [(32, 1), (25, 2), (25, 3), (33, 1), (33, 2), (33, 3)]
+
+
+def tiled_sets(case):
+    """the names of a case's sets that the tiled profile takes: no read of more than TILED_WINDOWS complete windows"""
+    return [n for n, (reads, _) in case["sets"].items() if max(len(r) for r in reads) - case["k"] + 1 <= TILED_WINDOWS]

@@ -1,6 +1,7 @@
 """The short-read search kernels on planted windows and lane decoys (planted_sets.py): search_kernel, search_group_kernel<2 | 4>,
 search_group8_kernel at its five mask widths, tq_probe_kernel / tq_replay_kernel, search_sliced_kernel, search_wide_kernel, their
-list forms, and family A through search_long_kernel and the hit-profile kernels.
+list forms, and family A through search_long_kernel and the slot loop's hit-profile kernels.  The profile kernels of the wide rows, the
+narrow tables, the tiled probe and the shared jobs pass run on the same fixtures in test_gpu_planted_profile.py, count for count.
 
 Every read has a designed count (found at t exactly when count >= t) that test_planted_sets_cpu.py proves equal to the CPU checker;
 here the tags are compared with the design, the log numbers, chunk and k-mer counts (and in counting builds the probe count) with the

@@ -1,6 +1,9 @@
-"""What the planted search tests (test_gpu_planted_search.py) presuppose of their read sets, proved through the CPU checker alone:
-for every read of every case the designed count says exactly what the checker finds, at every t; the chunk counts; and that every
-decoy shares exactly its one lane key with its k-mer (oracle_binding.keys_of_read)."""
+"""What the planted tests (test_gpu_planted_search.py, test_gpu_planted_profile.py) presuppose of their read sets, proved through the
+CPU checker alone: for every read of every case the designed count says exactly what the checker finds, at every t; the chunk counts;
+and that every decoy shares exactly its one lane key with its k-mer (oracle_binding.keys_of_read).
+
+The search file compares tags at the case's own t.  The profile file compares the designed count itself, as a byte: for every case it
+imports, the design is proved at every t in 1 .. max(count) + 1 (_byte_ts; the last t shows that no count is larger than designed)."""
 import numpy as np
 import pytest
 
@@ -18,6 +21,11 @@ def _design_equals_checker(tmp_path, k, ts, index, sets, max_kmer, n_chunks):
             want = sets[name][1] >= t
             wrong = np.nonzero(tg != want)[0]
             assert wrong.size == 0, (k, t, name, wrong[:10].tolist())
+
+
+def _byte_ts(*counts):
+    """every t at which a hit byte of these designed counts says something: 1 .. max + 1"""
+    return tuple(range(1, max(int(c.max()) for c in counts) + 2))
 
 
 def _decoys_share_one_lane(k, decoyed):
@@ -42,11 +50,21 @@ def _translations_share_one_lane(k, reads):
             assert (same == want).all(), (X, name)
 
 
-@pytest.mark.parametrize("k,t,n_chunks,fhws,per_chunk", ps.SLOT_SWEEPS + ps.SMALL_SWEEPS + ps.SLICED_SWEEPS)
+PROFILE_SWEEPS = ps.SLICED_SWEEPS + ps.TILED_SWEEPS           # the sweeps whose counts the profile file compares as bytes
+
+
+@pytest.mark.parametrize("k,t,n_chunks,fhws,per_chunk", ps.SLOT_SWEEPS + ps.SMALL_SWEEPS + ps.SLICED_SWEEPS + [s for s in ps.TILED_SWEEPS if s not in ps.SLOT_SWEEPS])
 def test_position_sweeps(tmp_path, k, t, n_chunks, fhws, per_chunk):
     c = ps.sweep_case(k, t, n_chunks, fhws, per_chunk)
     assert c["n_chunks"] == n_chunks or per_chunk
-    _design_equals_checker(tmp_path, k, (t,), c["index"], c["sets"], c["max_kmer"], c["n_chunks"])
+    byte = (k, t, n_chunks, fhws, per_chunk) in PROFILE_SWEEPS
+    ts = _byte_ts(*[counts for _, counts in c["sets"].values()]) if byte else (t,)
+    assert ts[-1] >= t
+    _design_equals_checker(tmp_path, k, ts, c["index"], c["sets"], c["max_kmer"], c["n_chunks"])
+    if (k, t, n_chunks, fhws, per_chunk) in ps.TILED_SWEEPS:   # what the tiled profile takes: every fixed-length set; at t = 1 all of them
+        took = ps.tiled_sets(c)
+        assert set(took) >= {f"f{fhw}" for fhw in fhws} and (t > 1 or took == list(c["sets"]))
+        assert max(int(c["sets"][n][1].max()) for n in took) >= t
     for fhw in fhws:                                            # the sets are what they are named for
         reads, counts = c["sets"][f"f{fhw}"]
         assert {len(r) for r in reads} == {fhw + t * k - 1} and len(reads) % 64 and len(reads) >= 2 * fhw
@@ -59,7 +77,11 @@ def test_position_sweeps(tmp_path, k, t, n_chunks, fhws, per_chunk):
 @pytest.mark.parametrize("k,n_chunks", ps.SLOT_LADDERS + ps.SLICED_LADDERS)
 def test_lane_ladders(tmp_path, k, n_chunks):
     c = ps.ladder_case(k, n_chunks)
-    _design_equals_checker(tmp_path, k, (1, 2, 3), c["index"], c["sets"], c["max_kmer"], n_chunks)
+    ts = _byte_ts(*[counts for _, counts in c["sets"].values()])
+    assert ts[-1] >= 3
+    _design_equals_checker(tmp_path, k, ts, c["index"], c["sets"], c["max_kmer"], n_chunks)
+    if (k, n_chunks) in ps.TILED_LADDERS:
+        assert ps.tiled_sets(c) == ["ladder", "whole"]
     counts = c["sets"]["ladder"][1]
     assert {0, 1, 2} == set(counts.tolist()) and (counts == 0).sum() > (counts > 0).sum()
     if "whole" in c["sets"]:
@@ -68,11 +90,13 @@ def test_lane_ladders(tmp_path, k, n_chunks):
     _decoys_share_one_lane(k, c["decoyed"])
 
 
-@pytest.mark.parametrize("k,n_chunks", ps.JOB_LADDERS)
+@pytest.mark.parametrize("k,n_chunks", ps.JOB_LADDERS + [j for j in ps.PROFILE_JOB_LADDERS if j not in ps.JOB_LADDERS])
 def test_ladders_split_between_two_index_sets(tmp_path, k, n_chunks):
     c = ps.ladder_jobs(k, n_chunks)
+    ts = _byte_ts(*c["counts"])
+    assert ts == (1, 2, 3)
     for j in range(2):
-        _design_equals_checker(tmp_path / f"j{j}", k, (1, 2), c["index_sets"][j], {"s": (c["search"], c["counts"][j])}, c["max_kmer"], c["n_chunks"])
+        _design_equals_checker(tmp_path / f"j{j}", k, ts, c["index_sets"][j], {"s": (c["search"], c["counts"][j])}, c["max_kmer"], c["n_chunks"])
     both = (c["counts"][0] > 0) & (c["counts"][1] > 0)
     assert not both.any() and (c["counts"][0] > 0).any() and (c["counts"][1] > 0).any()
     _decoys_share_one_lane(k, c["decoyed"])
