@@ -272,7 +272,8 @@ class Context:
         """commet_index_many_and_profile: job j indexes index_sets[j] (restricted to index_selects[j]) and profiles search_rs (under
         search_select, the same for every job) with a cap of its own: max_hits is an int or a list with one entry per job.  The jobs
         share hits passes over the search set where the library can arrange it (up to eight chunk filters a pass, a job never split;
-        set_option("multi_job", 1): job by job).  The same read set may appear in several jobs under different selections.
+        set_option("multi_job", 1): job by job; 2: a search set of long reads, which takes a wave per read ("long_search"), shares
+        hits passes too — by default its jobs run one by one).  The same read set may appear in several jobs under different selections.
         Returns (hits, info): hits[j] = np.uint8 per read of search_rs, byte for byte what
         index_and_profile(index_sets[j], [search_rs], index_selects[j], [search_select], max_hits[j]) gives for job j alone; info sums
         over the jobs (search_launches = the passes)."""

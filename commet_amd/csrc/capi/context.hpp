@@ -36,7 +36,7 @@ commet_ctx *commet_create(int device, int kmer_size, int min_hits)
     c->t = min_hits < 1 ? 1 : min_hits;
     if (const char *e = getenv("COMMET_INDEX_LANES")) c->index_lanes = atoi(e) == 1 ? 1 : 2;   // 1: one kernel at a time (per-kernel profiles)
     if (const char *e = getenv("COMMET_TILED")) c->tiled_mode = std::max(0, std::min(2, atoi(e)));
-    if (const char *e = getenv("COMMET_MULTI_JOB")) c->multi_job = atoi(e) == 1 ? 1 : atoi(e) == 2 ? 2 : 0;   // A/B runs: 1 = commet_index_many_and_search job by job, 2 = shared passes for long-read search sets too
+    if (const char *e = getenv("COMMET_MULTI_JOB")) c->multi_job = atoi(e) == 1 ? 1 : atoi(e) == 2 ? 2 : 0;   // A/B runs: 1 = commet_index_many_and_search job by job, 2 = shared passes for long-read search sets too (commet_index_many_and_profile as well)
     if (const char *e = getenv("COMMET_SPARSE_SEARCH")) c->sparse_search = std::max(0, std::min(2, atoi(e)));   // A/B runs
     if (const char *e = getenv("COMMET_LONG_SEARCH")) c->long_search = std::max(0, std::min(2, atoi(e)));       // A/B runs
     c->job_verbose = getenv("COMMET_JOB_VERBOSE") != nullptr;

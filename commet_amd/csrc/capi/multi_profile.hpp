@@ -6,6 +6,8 @@
 // which depend on the read alone; with the chunk filters of up to eight slots of several such jobs in one pass (A planes
 // interleaved, hits_jobs_kernel, hit_profile_jobs.hpp) the set is walked once per pass.  Every job's bytes are what
 // commet_index_and_profile gives for it alone — tested against exactly that, and against the CPU checker.
+// A search set of long reads (hits_wave_ok, profile.hpp) takes hits_jobs_wave_kernel, a wave per read on a persistent grid, under
+// multi_job = 2: the same slots, builds and byte arrays, one other launch.
 //
 // A pass: the jobs in their order while their chunks fit min(8, chunk_group) slots (a job that runs alone does not close a pass);
 // a job is never split, so its byte array is written by one pass.  The jobs are planned on the device (plan_index_on_device) and
@@ -14,13 +16,13 @@
 // slot.  The search selection is the same for all jobs and reaches the kernel as the visited bitmap of plan_search: no list form.
 //
 // Through commet_index_and_profile itself, same bytes: the whole call when n_jobs < 2, k < 2, count_probes, multi_job = 1,
-// chunk_group = 1, the search set is empty or takes the wave-per-read hits kernel, or the device has no room for the slots or the
-// byte arrays; a single job that the device planner does not take (an empty read in the set, a file without a selected read, an
+// chunk_group = 1, the search set is empty or takes the wave-per-read hits kernel and multi_job is not 2, or the device has no room
+// for the slots or the byte arrays; a single job that the device planner does not take (an empty read in the set, a file without a selected read, an
 // empty selection), that has no chunk or more chunks than a pass holds, or that is left alone in its pass — it picks its own regime
 // (wide, narrow, tiled), its neighbours still share.
-// Auto (multi_job = 0) shares: measured against the jobs one by one in MEASUREMENTS.md, "Jobs that share a hits pass".
-// Not built: a wave-per-read form of the shared pass, the tiled probe or the bit-sliced tables for shared passes, passes shared
-// between jobs whose search selections differ.
+// Auto (multi_job = 0) shares where the search set takes a lane per read: measured against the jobs one by one in MEASUREMENTS.md,
+// "Jobs that share a hits pass".  A search set of long reads stays job by job in auto, as on the search side (multi.hpp).
+// Not built: the tiled probe or the bit-sliced tables for shared passes, passes shared between jobs whose search selections differ.
 #pragma once
 
 namespace {
@@ -85,13 +87,14 @@ int profile_no_room(ProfileManyRun &m)
     return profile_alone(m, 0, m.n_jobs);
 }
 
-// does the call share passes at all?
+// does the call share passes at all?  A search set of long reads (hits_wave_ok, profile.hpp) under multi_job = 2 only: auto keeps
+// such a set job by job, as multi.hpp does on the search side
 bool profile_many_ok(const ProfileManyRun &m)
 {
     const commet_ctx *c = m.c;
     const commet_readset *srs = m.search_rs;
-    return m.n_jobs >= 2 && c->k >= 2 && !c->count_probes && c->multi_job != 1 && m.cap >= 2 && srs->n_reads > 0 && !hits_wave_ok(c, srs) &&
-           (srs->n_reads + 255) / 256 < (1ull << 24);
+    return m.n_jobs >= 2 && c->k >= 2 && !c->count_probes && c->multi_job != 1 && m.cap >= 2 && srs->n_reads > 0 &&
+           (c->multi_job == 2 || !hits_wave_ok(c, srs)) && (srs->n_reads + 255) / 256 < (1ull << 24);
 }
 
 // the plan of every job the device planner takes, and the reads the passes visit (as plan_job makes them), on the device on return
@@ -136,14 +139,20 @@ int upload_visited(ProfileManyRun &m)
 int launch_hits_jobs(commet_ctx *c, const commet_readset *rs, int g, int gs, const JobSlots &js, const uint64_t *d_sel, uint8_t *d_hits, uint64_t stride,
                      unsigned long long *d_walked)
 {
-    if (launch_size_ok(rs->n_reads)) return 1;
+    const bool wave = hits_wave_ok(c, rs);          // a wave per read on a persistent grid, else a lane per read
+    if (!wave && launch_size_ok(rs->n_reads)) return 1;
     const dim3 lanes((unsigned) ((rs->n_reads + 255) / 256));
     const FilterGroupView fg = filter_group(c, g, 0, true);
-    KScope ks(c, "hits_jobs_kernel", c->stream);
+    KScope ks(c, wave ? "hits_jobs_wave_kernel" : "hits_jobs_kernel", c->stream);
     with_key(c->k, [&](auto key) {
         using W = decltype(key);
         with_value<2, 4, 8>(gs, [&](auto NF) {
-            COMMET_LAUNCH((hits_jobs_kernel<W, NF>), lanes, dim3(256), 0, c->stream, rs->view(), fg, c->k, js, d_sel, d_hits, (uint32_t) (stride / 256), d_walked);
+            if (wave)
+                COMMET_LAUNCH((hits_jobs_wave_kernel<W, NF>), dim3((unsigned) resident_blocks<hits_jobs_wave_kernel<W, NF>>(c, rs->n_reads)), dim3(LONG_WG), 0,
+                              c->stream, rs->view(), fg, c->k, js, d_sel, d_hits, (uint32_t) (stride / 256), d_walked);
+            else
+                COMMET_LAUNCH((hits_jobs_kernel<W, NF>), lanes, dim3(256), 0, c->stream, rs->view(), fg, c->k, js, d_sel, d_hits, (uint32_t) (stride / 256),
+                              d_walked);
         });
     });
     HIP_OK(hipGetLastError());

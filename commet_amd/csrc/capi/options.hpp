@@ -50,7 +50,7 @@ int commet_set_option(commet_ctx *c, const char *name, int64_t value)
         c->profile_tiled = (int) value;
         return 0;
     }
-    if (!strcmp(name, "multi_job")) {         // 0 = commet_index_many_and_search puts the chunk filters of several jobs into one pass where it can, 1 = job by job, 2 = as 0, and search sets of long reads share passes too (capi/multi.hpp)
+    if (!strcmp(name, "multi_job")) {         // 0 = commet_index_many_and_search puts the chunk filters of several jobs into one pass where it can, 1 = job by job, 2 = as 0, and search sets of long reads share passes too (capi/multi.hpp); commet_index_many_and_profile likewise: 2 also shares hits passes on long-read search sets (capi/multi_profile.hpp)
         if (value < 0 || value > 2) return fail("multi_job must be 0, 1 or 2");
         c->multi_job = (int) value;
         return 0;

@@ -1,6 +1,6 @@
 """Threshold sweep: the `.bv` vectors of `index_and_search -t t` for every t in 1..T from ONE profile job.
 
-    python -m commet_amd.sweep -i index.txt -s search.txt -k K --max-t T -o OUT [--full] [--chunk-group N] [--profile-wide {0,1,2}] [--profile-slice {0,1,2}] [--profile-tiled {0,1,2}]
+    python -m commet_amd.sweep -i index.txt -s search.txt -k K --max-t T -o OUT [--full] [--chunk-group N] [--multi-job {0,1,2}] [--profile-wide {0,1,2}] [--profile-slice {0,1,2}] [--profile-tiled {0,1,2}]
 
 -i / -s take the reference's set-config grammar (`name:file[,bv];file[,bv]...`, one set per line; the index file holds exactly one
 set).  The sets are parsed and packed by the library's own ingest (ReadSet.from_fasta), one Context.index_and_profile(max_hits=T) gives a hit count per read, and
@@ -29,7 +29,10 @@ only the first search set is used (stderr says so when more are given).  With A 
     pass 3   per t, index_and_profile(A under T2(t) -> B under T1(t), max_hits = t)   -> OUT/t<t>/<B file>_in_<A tag>.bv
 
 The T jobs of pass 2 share hits passes over A (up to eight chunk filters a pass); only pass 3 stays one job per threshold, because its
-search selection differs per t.  sweep.csv holds the rows of both directions."""
+search selection differs per t.  sweep.csv holds the rows of both directions.
+--multi-job (the library's option "multi_job") decides how pass 2 shares: 0 the library's choice (default: shared passes, except
+over a set A of long reads, which takes a wave per read and is walked once per job), 1 never, 2 always — a set of long reads
+included (hits_jobs_wave_kernel: A is walked once per pass, not once per t)."""
 import argparse
 import os
 import sys
@@ -92,6 +95,8 @@ def parser():
     p.add_argument("--full", dest="full", action="store_true",
                    help="the symmetric comparison of `index_and_search -f` on the first search set: both directions for every t")
     p.add_argument("--chunk-group", dest="chunk_group", type=int, default=None, help="chunk filters per search pass (1..8; default: the library's)")
+    p.add_argument("--multi-job", dest="multi_job", type=int, default=None, choices=(0, 1, 2),
+                   help="--full: the jobs of pass 2 in shared hits passes: 0 the library's choice, 1 never, 2 always (sets of long reads too)")
     p.add_argument("--profile-wide", dest="profile_wide", type=int, default=None, choices=(0, 1, 2),
                    help="the profile through the wide bit-sliced rows (12 <= k <= 24): 0 the library's choice, 1 never, 2 always")
     p.add_argument("--profile-slice", dest="profile_slice", type=int, default=None, choices=(0, 1, 2),
@@ -163,6 +168,8 @@ def main(argv=None, api=None):
         loaded = [(tag, entries) + _load(api, ctx, entries) for tag, entries in search_sets]
         if a.chunk_group is not None:
             ctx.set_option("chunk_group", a.chunk_group)
+        if a.multi_job is not None:
+            ctx.set_option("multi_job", a.multi_job)
         if a.profile_wide is not None:
             ctx.set_option("profile_wide", a.profile_wide)
         if a.profile_slice is not None:

@@ -350,18 +350,18 @@ int commet_index_and_profile(commet_ctx *ctx, const commet_readset *index_rs, co
  * The jobs, in their order, share a hits pass while their chunk filters fit min(8, chunk_group) slots (a job that runs alone, see below,
  * does not close a pass), a job never split between two passes:
  * one walk of a read and one plane-A request per window serve the filters of every job of the pass (hits_jobs_kernel, a lane per
- * read); per job the byte is min(max_hits[j], max over ITS chunks of max(F, R)), and a job that reaches its cap stops for itself
+ * read; hits_jobs_wave_kernel, a wave per read, for a search set of long reads under "multi_job" = 2); per job the byte is min(max_hits[j], max over ITS chunks of max(F, R)), and a job that reaches its cap stops for itself
  * alone.  The jobs' chunks are built one after the other on the context's stream (index_lanes plays no part here).
  * Through commet_index_and_profile itself, with the same bytes: every job when n_jobs < 2, k < 2, under count_probes, with option
- * "multi_job" = 1 or "chunk_group" = 1, for an empty search set or one that takes the wave-per-read hits kernel ("long_search"),
- * and when the device has no room for the slots or the byte arrays of a pass; a single job when the device planner does not take it
+ * "multi_job" = 1 or "chunk_group" = 1, for an empty search set or, unless "multi_job" is 2, one that takes the wave-per-read
+ * hits kernel ("long_search"), and when the device has no room for the slots or the byte arrays of a pass; a single job when the device planner does not take it
  * (an empty read in its set, a file without a selected read, an empty selection), when it has no chunk or more chunks than a pass
  * holds, or when it is alone in its pass — such a job picks its own regime (wide rows, narrow tables, tiled probe) and its
- * neighbours still share.  "multi_job" = 0 (auto) shares, as 2 does: measured faster than the jobs one by one (MEASUREMENTS.md,
- * "Jobs that share a hits pass").
+ * neighbours still share.  "multi_job" = 0 (auto) shares where the search set takes a lane per read, as 2 does: measured faster
+ * than the jobs one by one (MEASUREMENTS.md, "Jobs that share a hits pass"); a search set of long reads shares under 2 only.
  * info (may be NULL) sums over the jobs: search_launches = the passes (plus the launches of the jobs that ran alone), reads_scanned =
  * the reads the passes walked, probes = 0.
- * Open: a wave-per-read form of the shared pass; the tiled probe and the bit-sliced tables for shared passes; shared passes for jobs
+ * Open: the tiled probe and the bit-sliced tables for shared passes; shared passes for jobs
  * whose search selections differ (the third pass of the symmetric sweep). */
 int commet_index_many_and_profile(commet_ctx *ctx, int n_jobs, const commet_readset *const *index_rs,
                                   const uint8_t *const *index_select, const commet_readset *search_rs,
@@ -411,7 +411,8 @@ int commet_index_many_and_profile(commet_ctx *ctx, int n_jobs, const commet_read
  *                        15-30 ms per GiB; lists of more than 4 GiB are built for a set's second eligible scan)
  *   multi_job (0/1/2)    commet_index_many_and_search: 0 = chunk filters of several jobs in one pass where possible (search sets that
  *                        take long_search: job by job), 1 = job by job, 2 = as 0, and search sets that take long_search share passes too;
- *                        commet_index_many_and_profile: 0 and 2 = jobs share hits passes where possible, 1 = job by job
+ *                        commet_index_many_and_profile: 0 = jobs share hits passes where possible (search sets that take long_search:
+ *                        job by job), 1 = job by job, 2 = as 0, and search sets that take long_search share hits passes too
  *   sparse_search (0/1/2) a pass over a SELECTION of a search set (a filter bv that leaves few reads: file_manager.h:88-112 skips the
  *                        others) walks the list of the selected, not yet tagged reads instead of the set's bitmap, so that every
  *                        lane of a wave has a read: 0 = when the host plan visits less than half of the set's reads, 1 = never,
@@ -420,7 +421,8 @@ int commet_index_many_and_profile(commet_ctx *ctx, int n_jobs, const commet_read
  *                        consecutive windows per step, the reference's greedy rule on the ballots (search_long_kernel), groups of up to
  *                        eight chunk filters: 0 = such sets whose longest read has 5000 bases or more (measured: the lane-per-read
  *                        kernels win below 2500, the wave from 3000 on), 1 = never, 2 = whenever the set has a read (tests);
- *                        commet_index_many_and_search lets the jobs of such a search set share passes under multi_job = 2
+ *                        commet_index_many_and_search and commet_index_many_and_profile let the jobs of such a search set share
+ *                        passes under multi_job = 2
  *   ordered_scan (0/1/2) ragged sets (reads of several lengths): the first pass of a gather kernel over a whole set walks its reads in
  *                        order of their first-hit window counts (a list made once per set: a workgroup lives as long as its longest
  *                        read, its other lanes idle meanwhile): 0 = sets of 2^16 reads and more, 1 = never, 2 = any ragged set (tests)

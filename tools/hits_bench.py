@@ -31,6 +31,10 @@ stream synchronise and the copy back) and then runs once more with option kernel
                     (a) `alone`: the jobs one by one through commet_index_and_profile at its own auto choices, (b) `shared`: ONE
                     commet_index_many_and_profile call; fresh child processes alternating over `--rounds`, the N byte arrays compared
                     first, then per leg the median over the rounds of the per-process median wall time of the N jobs, and its spread
+  --long            with --jobs N: the many-job leg on search sets of LONG reads, which take a wave per read — the two sets of
+                    tools/long_read_bench.py's workloads `ragged_1k_10k` and `len5500` (--long-workloads, --scale), one result line
+                    each; both legs are ONE commet_index_many_and_profile call, (a) `alone` under multi_job = 1 (the jobs one by one
+                    through hits_wave_kernel), (b) `shared` under multi_job = 2 (hits_jobs_wave_kernel); the protocol is --jobs' own
   python tools/hits_bench.py [--reads 10000000] [--read-len 100] [-k 32] [--max-t 8] [--rounds 2] [--reps 3] [--out FILE]"""
 import argparse
 import json
@@ -139,6 +143,8 @@ def child_many(a):
     (b0, o0), (b1, o1) = _sets(a.work, a.tag)
     out = {}
     with commet_amd.Context(k=a.k, t=2) as ctx:
+        if a.multi_job >= 0:
+            ctx.set_option("multi_job", a.multi_job)
         irs = commet_amd.ReadSet.from_files(ctx, [(b0, o0)])
         qrs = commet_amd.ReadSet.from_files(ctx, [(b1, o1)])
         n = irs.num_reads
@@ -182,6 +188,8 @@ def child_many(a):
 
 def many_leg(a):
     legs = [("alone", ["--n-jobs", str(a.jobs)]), ("shared", ["--n-jobs", str(a.jobs), "--share"])]
+    if a.long:                                                                   # one many-job call either way: the option decides
+        legs = [("alone", ["--n-jobs", str(a.jobs), "--share", "--multi-job", "1"]), ("shared", ["--n-jobs", str(a.jobs), "--share", "--multi-job", "2"])]
     runs = {name: [] for name, _ in legs}
     equal = []
     for r in range(a.rounds):
@@ -199,6 +207,31 @@ def many_leg(a):
     out["shared_over_alone"] = round(out["shared"]["wall_ms"] / out["alone"]["wall_ms"], 4)
     out["found_per_job"] = runs["shared"][0]["found_per_job"]
     return out
+
+
+def long_jobs(a):
+    """the --jobs leg on long-read sets: per workload of long_read_bench.py its two sets (made by that tool's own generator), then many_leg"""
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import long_read_bench as lrb
+    res = {"shapes": []}
+    for name in a.long_workloads:
+        n, total = lrb.make_pair(name, a.scale, a.work)
+        offs = np.load(os.path.join(a.work, f"{name}_offs.npy"))
+        for i in (0, 1):                                                         # (as _sets reads them)
+            os.replace(os.path.join(a.work, f"{name}_{i}_bases.npy"), os.path.join(a.work, f"c1{i}_b.npy"))
+            np.save(os.path.join(a.work, f"c1{i}_o.npy"), offs)
+        os.remove(os.path.join(a.work, f"{name}_offs.npy"))
+        m = many_leg(a)
+        shape = {"workload": f"{name}: 2 x {n} reads, {total} bases a set, longest {int(np.diff(offs.astype(np.int64)).max())}, k={a.k}, {a.jobs} jobs on disjoint parts "
+                             f"of set 0, max_hits={a.max_t}; alone: multi_job = 1, shared: multi_job = 2", "many": m}
+        res["shapes"].append(shape)
+        print(json.dumps({"workload": shape["workload"], "hits_equal": m["hits_equal"], "shared_over_alone": m["shared_over_alone"],
+                          "found_per_job": m["found_per_job"], "alone": m["alone"], "shared": m["shared"]}), flush=True)
+        if not m["hits_equal"]:
+            raise SystemExit(f"{name}: the bytes of the shared passes and of the jobs alone differ")
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        open(a.out, "w").write(json.dumps(res) + "\n")
 
 
 def run_child(a, mode, tag, limit, extra=()):
@@ -261,6 +294,10 @@ def main():
     ap.add_argument("--jobs", type=int, default=0, help="N jobs on disjoint N-ths of set 0, all searching set 1: one by one against one many-job call")
     ap.add_argument("--n-jobs", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--share", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("--long", action="store_true", help="with --jobs: on long-read search sets, multi_job = 1 against multi_job = 2")
+    ap.add_argument("--long-workloads", nargs="+", default=["ragged_1k_10k", "len5500"], help="--long: workloads of tools/long_read_bench.py")
+    ap.add_argument("--scale", type=float, default=1.0, help="--long: reads per set, as a share of the workload's")
+    ap.add_argument("--multi-job", type=int, default=-1, help=argparse.SUPPRESS)     # (-1 = leave the option alone)
     ap.add_argument("--many-reads", type=int, nargs="+", default=[600_000])
     ap.add_argument("--limit", type=int, default=240, help="seconds a child may take")
     ap.add_argument("--out", default=None)
@@ -278,8 +315,12 @@ def main():
     if a.jobs_lib:
         a.jobs_lib = os.path.abspath(a.jobs_lib)
     from commet_amd import synth
+    if a.long and a.jobs < 2:
+        raise SystemExit("--long measures the many-job leg: give --jobs N, N >= 2")
     a.work = tempfile.mkdtemp(prefix="hits_bench_")
     try:
+        if a.long:
+            return long_jobs(a)
         for i in (0, 1) if not (a.wide or a.sliced) else ():                     # (the wide and sliced legs have shapes of their own)
             b, o = synth.synth_set(i, a.reads, a.read_len, base_set=0)
             np.save(os.path.join(a.work, f"c1{i}_b.npy"), b), np.save(os.path.join(a.work, f"c1{i}_o.npy"), o)
