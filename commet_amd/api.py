@@ -47,6 +47,31 @@ def _ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+def _handles(sets):
+    return (C.c_void_p * max(len(sets), 1))(*[rs._h for rs in sets])
+
+
+def _selections(selects, sets, what):
+    """one optional selection per set -> their byte arrays (None: no selection)"""
+    if selects is None:
+        return [None] * len(sets)
+    return [_as_bits(s, rs.num_reads, what) for s, rs in zip(selects, sets)]
+
+
+def _ptrs(arrays):
+    """c_void_p array over host arrays; None, and an array without bytes, is a null pointer"""
+    return (C.c_void_p * max(len(arrays), 1))(*[(_ptr(a).value if a is not None and a.size else None) for a in arrays])
+
+
+def _info_dict(info):
+    return {f: getattr(info, f) for f, _ in _l.JobInfo._fields_}
+
+
+def _stats_list(stats, n):
+    return [dict(indexed=int(stats[i].indexed), searched=int(stats[i].searched), shared=int(stats[i].shared),
+                 search_ms=float(stats[i].search_ms)) for i in range(n)]
+
+
 def device_count():
     """commet_device_count: HIP devices this process sees (0 without one; counting initialises nothing a later fork would mind)"""
     return int(_l.load().commet_device_count())
@@ -199,42 +224,27 @@ class Context:
         searched, shared) — the numbers of the reference's log line."""
         ns = len(search_sets)
         isel = _as_bits(index_select, index_rs.num_reads, "index_select")
-        ssel = [None] * ns
-        if search_selects is not None:
-            ssel = [_as_bits(s, rs.num_reads, "search_select") for s, rs in zip(search_selects, search_sets)]
+        ssel = _selections(search_selects, search_sets, "search_select")
         tags = [np.zeros(bits_nbytes(rs.num_reads), dtype=np.uint8) for rs in search_sets]
-        rs_arr = (C.c_void_p * max(ns, 1))(*[rs._h for rs in search_sets])
-        sel_arr = (C.c_void_p * max(ns, 1))(*[(_ptr(s).value if s is not None else None) for s in ssel])
-        tag_arr = (C.c_void_p * max(ns, 1))(*[_ptr(t).value for t in tags])
         stats = (_l.PairStats * max(ns, 1))()
         info = _l.JobInfo()
-        self._check(self._lib.commet_index_and_search(self._h, index_rs._h, _ptr(isel), ns, rs_arr, sel_arr, tag_arr,
+        self._check(self._lib.commet_index_and_search(self._h, index_rs._h, _ptr(isel), ns, _handles(search_sets), _ptrs(ssel), _ptrs(tags),
                                                       stats, C.byref(info)))
-        st = [dict(indexed=int(stats[i].indexed), searched=int(stats[i].searched), shared=int(stats[i].shared),
-                   search_ms=float(stats[i].search_ms)) for i in range(ns)]
-        inf = {f: getattr(info, f) for f, _ in _l.JobInfo._fields_}
-        return tags, st, inf
+        return tags, _stats_list(stats, ns), _info_dict(info)
 
     def index_many_and_search(self, index_sets, search_rs, index_selects=None, search_select=None):
         """commet_index_many_and_search: job j indexes index_sets[j] (restricted to index_selects[j]) and searches search_rs; the jobs
         share passes over the search set where the library can arrange it.  Returns (tags, stats, info): tags[j], stats[j] as
         index_and_search(index_sets[j], [search_rs], ...) gives them for job j alone."""
         nj = len(index_sets)
-        isel = [None] * nj
-        if index_selects is not None:
-            isel = [_as_bits(s, rs.num_reads, "index_select") for s, rs in zip(index_selects, index_sets)]
+        isel = _selections(index_selects, index_sets, "index_select")
         ssel = _as_bits(search_select, search_rs.num_reads, "search_select")
         tags = [np.zeros(bits_nbytes(search_rs.num_reads), dtype=np.uint8) for _ in range(nj)]
-        rs_arr = (C.c_void_p * max(nj, 1))(*[rs._h for rs in index_sets])
-        sel_arr = (C.c_void_p * max(nj, 1))(*[(_ptr(s).value if s is not None else None) for s in isel])
-        tag_arr = (C.c_void_p * max(nj, 1))(*[_ptr(t).value for t in tags])
         stats = (_l.PairStats * max(nj, 1))()
         info = _l.JobInfo()
-        self._check(self._lib.commet_index_many_and_search(self._h, nj, rs_arr, sel_arr, search_rs._h, _ptr(ssel), tag_arr, stats,
-                                                           C.byref(info)))
-        st = [dict(indexed=int(stats[i].indexed), searched=int(stats[i].searched), shared=int(stats[i].shared),
-                   search_ms=float(stats[i].search_ms)) for i in range(nj)]
-        return tags, st, {f: getattr(info, f) for f, _ in _l.JobInfo._fields_}
+        self._check(self._lib.commet_index_many_and_search(self._h, nj, _handles(index_sets), _ptrs(isel), search_rs._h, _ptr(ssel), _ptrs(tags),
+                                                           stats, C.byref(info)))
+        return tags, _stats_list(stats, nj), _info_dict(info)
 
     def index_and_profile(self, index_rs, search_sets, index_select=None, search_selects=None, max_hits=8):
         """commet_index_and_profile: the chunk loop with a search that does not stop at t.  Returns (hits, info): hits[i] = np.uint8
@@ -256,17 +266,12 @@ class Context:
         Independent of "tiled_search"; the bytes do not depend on it."""
         ns = len(search_sets)
         isel = _as_bits(index_select, index_rs.num_reads, "index_select")
-        ssel = [None] * ns
-        if search_selects is not None:
-            ssel = [_as_bits(s, rs.num_reads, "search_select") for s, rs in zip(search_selects, search_sets)]
+        ssel = _selections(search_selects, search_sets, "search_select")
         hits = [np.zeros(rs.num_reads, dtype=np.uint8) for rs in search_sets]
-        rs_arr = (C.c_void_p * max(ns, 1))(*[rs._h for rs in search_sets])
-        sel_arr = (C.c_void_p * max(ns, 1))(*[(_ptr(s).value if s is not None else None) for s in ssel])
-        hit_arr = (C.c_void_p * max(ns, 1))(*[(_ptr(h).value if h.size else None) for h in hits])
         info = _l.JobInfo()
-        self._check(self._lib.commet_index_and_profile(self._h, index_rs._h, _ptr(isel), ns, rs_arr, sel_arr, int(max_hits), hit_arr,
-                                                       C.byref(info)))
-        return hits, {f: getattr(info, f) for f, _ in _l.JobInfo._fields_}
+        self._check(self._lib.commet_index_and_profile(self._h, index_rs._h, _ptr(isel), ns, _handles(search_sets), _ptrs(ssel), int(max_hits),
+                                                       _ptrs(hits), C.byref(info)))
+        return hits, _info_dict(info)
 
     def index_many_and_profile(self, index_sets, search_rs, index_selects=None, search_select=None, max_hits=8):
         """commet_index_many_and_profile: job j indexes index_sets[j] (restricted to index_selects[j]) and profiles search_rs (under
@@ -281,19 +286,14 @@ class Context:
         caps = [int(max_hits)] * nj if np.isscalar(max_hits) else [int(x) for x in max_hits]
         if len(caps) != nj:
             raise CommetError(f"max_hits: need one entry per job ({nj}), got {len(caps)}")
-        isel = [None] * nj
-        if index_selects is not None:
-            isel = [_as_bits(s, rs.num_reads, "index_select") for s, rs in zip(index_selects, index_sets)]
+        isel = _selections(index_selects, index_sets, "index_select")
         ssel = _as_bits(search_select, search_rs.num_reads, "search_select")
         hits = [np.zeros(search_rs.num_reads, dtype=np.uint8) for _ in range(nj)]
-        rs_arr = (C.c_void_p * max(nj, 1))(*[rs._h for rs in index_sets])
-        sel_arr = (C.c_void_p * max(nj, 1))(*[(_ptr(s).value if s is not None else None) for s in isel])
         cap_arr = (C.c_int * max(nj, 1))(*caps)
-        hit_arr = (C.c_void_p * max(nj, 1))(*[(_ptr(h).value if h.size else None) for h in hits])
         info = _l.JobInfo()
-        self._check(self._lib.commet_index_many_and_profile(self._h, nj, rs_arr, sel_arr, search_rs._h, _ptr(ssel), cap_arr, hit_arr,
-                                                            C.byref(info)))
-        return hits, {f: getattr(info, f) for f, _ in _l.JobInfo._fields_}
+        self._check(self._lib.commet_index_many_and_profile(self._h, nj, _handles(index_sets), _ptrs(isel), search_rs._h, _ptr(ssel), cap_arr,
+                                                            _ptrs(hits), C.byref(info)))
+        return hits, _info_dict(info)
 
     def poison(self, byte):
         """test hook: every bit array of the context (filter slots, interleaved A planes, bit-sliced planes and tables) filled with `byte`"""

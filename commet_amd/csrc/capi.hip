@@ -60,6 +60,7 @@
 #include "capi/search_dispatch.hpp"  // search regimes: which one, its launches
 #include "capi/job_parts.hpp"        // what the two job entry points share: phase clock, timing recorder, device planner, pass steps
 #include "capi/job.hpp"              // commet_index_reads / _search_reads / _index_and_search
+#include "capi/many.hpp"             // what the two many-job calls share: their record, plans, pass packing, the build of a pass's filters
 #include "capi/multi.hpp"            // commet_index_many_and_search: several jobs on one search set, their filters in one pass
 #include "capi/profile.hpp"          // commet_index_and_profile: per-read hit counts, the tags of every t from one job
 #include "capi/multi_profile.hpp"    // commet_index_many_and_profile: several profile jobs on one search set, their filters in one hits pass

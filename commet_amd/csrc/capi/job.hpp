@@ -141,20 +141,14 @@ int plan_job(JobRun &j, const uint8_t *index_select, const uint8_t *const *searc
     }
     const IndexPlan &plan = j.plan;
     j.clk.lap(j.ph_plan);
-    if (!plan.dense && upload_bits(c, irs->d_sel, plan.indexed_bits.data(), irs->n_reads)) return 1;
-    // a selection on a fixed-length set (Commet.py's J2 / J3 jobs): the selected reads' numbers as a list, so that the bucketed
-    // build walks them arithmetically; no room: the round planner walks the bitmap, as before
-    if (!plan.dense && irs->uniform_len != 0 && !c->part_no_uni && plan.indexed_reads && c->index_mode != 1) {
-        const uint32_t *d_len = nullptr;
-        if (build_selection_list(c, c->sel_ids, irs, plan, &j.d_ids, &d_len) == 0) {
-            // (the list must hold exactly the plan's indexed reads: checked when the job's stream is next synchronised)
-            c->h_counters[N_COUNTERS - 1] = ~0ull;
-            HIP_OK(hipMemcpyAsync(&c->h_counters[N_COUNTERS - 1], d_len, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-            j.ids_expected = plan.indexed_reads;
-            j.chunk_pos = chunk_positions(plan);
-        } else {
-            (void) hipGetLastError();
-        }
+    const uint32_t *d_len = nullptr;
+    if (prepare_job_selection(c, irs, plan, c->sel_ids, &j.d_ids, &d_len)) return 1;
+    if (j.d_ids) {
+        // (the list must hold exactly the plan's indexed reads: checked when the job's stream is next synchronised)
+        c->h_counters[N_COUNTERS - 1] = ~0ull;
+        HIP_OK(hipMemcpyAsync(&c->h_counters[N_COUNTERS - 1], d_len, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        j.ids_expected = plan.indexed_reads;
+        j.chunk_pos = chunk_positions(plan);
     }
     j.clk.lap(j.ph_upload);
     for (int s = 0; s < j.n_search; ++s) {

@@ -117,6 +117,24 @@ int build_selection_list(commet_ctx *c, commet_ctx::IdList &l, const commet_read
     return 0;
 }
 
+// What the builds of a planned job read of its selection, queued on the context's stream: the plan's bitmap into rs->d_sel and, for a
+// set of one read length (Commet.py's J2 / J3 jobs), the selected reads' numbers as a list in `buf`, which the bucketed build walks
+// arithmetically.  A dense plan indexes whole read ranges and needs neither.  The list is an optimisation: without room for it
+// *d_ids = nullptr and the build walks the bitmap, so only a failed upload is an error (1).  Every job entry point takes this step
+int prepare_job_selection(commet_ctx *c, const commet_readset *rs, const IndexPlan &plan, commet_ctx::IdList &buf, const uint32_t **d_ids,
+                          const uint32_t **d_len = nullptr)
+{
+    *d_ids = nullptr;
+    if (plan.dense) return 0;
+    if (upload_bits(c, rs->d_sel, plan.indexed_bits.data(), rs->n_reads)) return 1;
+    if (rs->uniform_len == 0 || c->part_no_uni || !plan.indexed_reads || c->index_mode == 1) return 0;
+    if (build_selection_list(c, buf, rs, plan, d_ids, d_len)) {
+        (void) hipGetLastError();
+        *d_ids = nullptr;
+    }
+    return 0;
+}
+
 // first position of every chunk of a plan in the list of its indexed reads
 std::vector<uint64_t> chunk_positions(const IndexPlan &plan)
 {

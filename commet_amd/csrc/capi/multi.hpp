@@ -19,65 +19,26 @@
 // multi_job = 2 only: whether such a pass beats the jobs alone has not been measured (MEASUREMENTS.md, "Long reads"), so auto runs
 // them job by job.  For such a search set a chunk may take index_kernel (auto keeps it for sets with reads of more than 4096
 // k-mers): its slot is zeroed first, as in build_group.
+//
+// Here: which calls take a fast path (plan_many), the pass itself — found flags, the scan, tags and statistics of every job — and two
+// single-chunk jobs per tiled scan (run_pair).  In many.hpp, with commet_index_many_and_profile: the call's record (ManyCall), the
+// argument checks, a job's plan, jobs run alone, the packing of jobs into passes, the build of a pass's filters, the account.
 #pragma once
-
 
 namespace {
 
-// one commet_index_many_and_search call
-struct ManyRun {
-    commet_ctx *c;
-    int n_jobs;
-    const commet_readset *const *index_rs;
-    const uint8_t *const *index_select;
-    const commet_readset *search_rs;
-    const uint8_t *search_select;
+// one commet_index_many_and_search call (the record both many-job calls keep: ManyCall, many.hpp)
+struct ManyRun : ManyCall {
     uint8_t *const *tags_out;
     commet_pair_stats *stats;
-    struct Job {
-        IndexPlan plan;
-        const uint8_t *sel = nullptr;
-        std::vector<uint64_t> chunk_pos;        // first position of every chunk in the job's list of selected reads
-    };
-    std::vector<Job> jobs;                      // the fast paths' plans
-    commet_job_info sum = commet_job_info();
-    PhaseClock clk;
-    double ph_plan = 0, ph_launch = 0, ph_wait = 0;
-    JobTimer tm;                                // one bracket per pass: its builds, then its one scan
     bool lng = false;                           // the search set takes the wave-per-read kernel (long_ok)
     ManyRun(commet_ctx *c_, int n, const commet_readset *const *irs, const uint8_t *const *isel, const commet_readset *srs, const uint8_t *ssel,
             uint8_t *const *tags, commet_pair_stats *st)
-        : c(c_), n_jobs(n), index_rs(irs), index_select(isel), search_rs(srs), search_select(ssel), tags_out(tags), stats(st), tm(c_, true, 1)
+        : ManyCall(c_, n, irs, isel, srs, ssel), tags_out(tags), stats(st)
     {
     }
     uint64_t tag_words() const { return bitmap_words(search_rs->n_reads); }
 };
-
-// jobs j0 .. j1 - 1 through commet_index_and_search, one after the other, summed into the call's account
-int run_alone(ManyRun &m, int j0, int j1)
-{
-    for (int j = j0; j < j1; ++j) {
-        commet_job_info ji = commet_job_info();
-        const uint8_t *ss = m.search_select;
-        uint8_t *to = m.tags_out ? m.tags_out[j] : nullptr;
-        if (commet_index_and_search(m.c, m.index_rs[j], m.index_select ? m.index_select[j] : nullptr, 1, &m.search_rs, m.search_select ? &ss : nullptr,
-                                    m.tags_out ? &to : nullptr, m.stats ? &m.stats[j] : nullptr, &ji))
-            return 1;
-        add_info(m.sum, ji);
-    }
-    return 0;
-}
-
-// No room for what a shared pass needs (eight filter slots + their interleaved A planes are 20 GiB at k = 32): the jobs one after the
-// other, as the header promises — commet_index_and_search itself degrades to groups of four, then one.  Nothing a caller depends on
-// has been written by then that the jobs do not write again.
-int no_room(ManyRun &m)
-{
-    (void) hipGetLastError();
-    m.c->cur_slot = 0;
-    m.sum = commet_job_info();
-    return run_alone(m, 0, m.n_jobs);
-}
 
 // found flags of the jobs of a pass (`need` bitmaps over the search set; eight are taken) and their counters: 0 = there, 1 = no room
 // for the flags, 2 = error
@@ -100,47 +61,20 @@ int plan_many(ManyRun &m, bool *fast)
     if (ssel && all_ones(ssel, srs->n_reads)) ssel = nullptr;
     const uint64_t max_kmer = commet_max_kmer(c);
     m.lng = long_ok(c, srs);
-    *fast = m.n_jobs >= 2 && c->k >= 2 && !c->count_probes && c->chunk_group >= 8 && c->multi_job != 1 && srs->n_reads > 0 &&
+    *fast = m.n_jobs >= 2 && c->k >= 2 && !c->count_probes && c->chunk_group >= 8 && c->multi_job != 1 && !c->part_no_uni && srs->n_reads > 0 &&
             slice_words(c, 8) == 0 && (m.lng ? c->multi_job == 2 : group8_ok(c, srs)) && plan_fast_ok(srs->files, ssel, srs->empty_reads, 1) &&
             (srs->n_reads + 255) / 256 < (1ull << 24);
     m.jobs.resize(*fast ? (size_t) m.n_jobs : 0);
     for (int j = 0; j < m.n_jobs && *fast; ++j) {
         const commet_readset *rs = m.index_rs[j];
         ManyRun::Job &job = m.jobs[(size_t) j];
-        job.sel = m.index_select ? m.index_select[j] : nullptr;
-        if (job.sel && all_ones(job.sel, rs->n_reads)) job.sel = nullptr;
-        if (!rs->n_reads || c->part_no_uni || !plan_blocks_ok(rs->files, job.sel, rs->empty_reads, max_kmer)) {
-            *fast = false;
-            break;
-        }
-        if (plan_index_on_device(c, rs, job.sel, max_kmer, &job.plan)) return 1;
+        if (plan_many_job(m, j, max_kmer, fast)) return 1;
         if (job.plan.chunks.empty() || job.plan.chunks.size() > 8) *fast = false;
         for (const Chunk &ch : job.plan.chunks)
             if (!ch.n_reads || (!m.lng && !would_partition(c, rs, ch.kmers, ch.last - ch.first + 1))) *fast = false;    // (the bucketed build writes every tile of its slot itself; a pass of long reads zeroes the slots of the others)
-        job.chunk_pos = chunk_positions(job.plan);
+        job.shares = *fast;
     }
     return 0;
-}
-
-// the call's account to the caller, and one line on stderr under COMMET_JOB_VERBOSE (`what`: which path ran; nullptr = job by job, whose calls print their own)
-int finish_many(ManyRun &m, commet_job_info *info, const char *what)
-{
-    m.sum.total_ms = m.clk.total_ms();
-    if (what && m.c->job_verbose)
-        fprintf(stderr, "[jobs x%d%s] plans %.2f ms, launches %.2f ms, wait + download %.2f ms; device: index %.2f ms, search %.2f ms\n", m.n_jobs, what,
-                m.ph_plan, m.ph_launch, m.ph_wait, m.sum.index_ms, m.sum.search_ms);
-    if (info) *info = m.sum;
-    return 0;
-}
-
-// the device times of the pass that just ended (the last bracket) into the account; returns the scan's
-float account_pass_times(ManyRun &m)
-{
-    float ms_i = 0, ms_s = 0;
-    (void) m.tm.index_ms(m.tm.brackets() - 1, &ms_i);
-    (void) m.tm.set_ms(m.tm.brackets() - 1, 0, &ms_s);
-    m.sum.index_ms += ms_i, m.sum.index_kernel_ms += ms_i, m.sum.search_ms += ms_s;
-    return ms_s;
 }
 
 // counters and the tags of jobs j0 .. j1 - 1 of a pass to the host; waits for the pass
@@ -179,14 +113,7 @@ int run_pair(ManyRun &m, int j0)
     // second job's in a buffer of its own — then the fork
     const uint32_t *ids_of[2] = {nullptr, nullptr};
     const bool same_set = m.index_rs[j0] == m.index_rs[j0 + 1];    // (one set in both jobs: ONE selection bitmap on the device — the second job's goes up behind the first build)
-    auto prepare = [&](int j) -> int {
-        const commet_readset *rs = m.index_rs[j];
-        const IndexPlan &plan = m.jobs[(size_t) j].plan;
-        if (plan.dense) return 0;
-        if (upload_bits(c, rs->d_sel, plan.indexed_bits.data(), rs->n_reads)) return 1;
-        if (rs->uniform_len == 0) return 0;
-        return build_selection_list(c, j == j0 ? c->sel_ids : c->sel_ids2, rs, plan, &ids_of[j - j0]);
-    };
+    auto prepare = [&](int j) { return prepare_job_selection(c, m.index_rs[j], m.jobs[(size_t) j].plan, j == j0 ? c->sel_ids : c->sel_ids2, &ids_of[j - j0]); };
     if (prepare(j0) || (!same_set && prepare(j0 + 1))) return 1;
     const bool lanes = c->index_lanes > 1 && !c->kclock.on && !same_set;
     if (lanes) {
@@ -240,42 +167,17 @@ int run_pair(ManyRun &m, int j0)
     return 0;
 }
 
-// ---- a shared pass: consecutive jobs j0 .. j1 - 1, whose g chunks fit the eight slots ----------------------------------------------
+// ---- a shared pass: the consecutive jobs `in_pass`, whose chunks fit the eight slots -----------------------------------------------------
 // 0 = done, 1 = error, 2 = no room
-int run_shared_pass(ManyRun &m, int j0, int j1, int g)
+int run_shared_pass(ManyRun &m, const std::vector<int> &in_pass)
 {
     commet_ctx *c = m.c;
     const commet_readset *srs = m.search_rs;
-    if (ensure_slots(c, g, 8)) return 2;
-    if (m.tm.begin_index()) return 1;
-    uint32_t job_mask = 0;
+    const int j0 = in_pass.front(), j1 = in_pass.back() + 1, g = pass_chunks(m, in_pass);
+    if (const int rc = build_pass_filters(m, in_pass, g, 8)) return rc;
+    uint32_t job_mask = 0;                          // the first slot of every job
     int slot = 0;
-    for (int j = j0; j < j1; ++j) {
-        const commet_readset *rs = m.index_rs[j];
-        const ManyRun::Job &job = m.jobs[(size_t) j];
-        job_mask |= 1u << slot;
-        const uint32_t *d_ids = nullptr;
-        if (!job.plan.dense && upload_bits(c, rs->d_sel, job.plan.indexed_bits.data(), rs->n_reads)) return 1;
-        // the job's selected reads as a list (ragged sets: the bucketed build lists the chunk's items itself, from the bitmap); the chunks
-        // of every job are built on the one stream, one after the other, so the list buffer of the context serves job after job
-        if (!job.plan.dense && rs->uniform_len != 0 && build_selection_list(c, c->sel_ids, rs, job.plan, &d_ids)) {
-            (void) hipStreamSynchronize(c->stream);      // (chunks of earlier jobs of the pass may be under way)
-            return 2;
-        }
-        for (size_t ci = 0; ci < job.plan.chunks.size(); ++ci, ++slot) {
-            const Chunk &ch = job.plan.chunks[ci];
-            c->cur_slot = slot;
-            // (a pass of long reads only: a chunk that takes index_kernel meets a zeroed slot, as in build_group)
-            const bool self_zeroing = would_partition(c, rs, ch.kmers, ch.last - ch.first + 1);
-            if (!self_zeroing && commet_filter_reset(c)) return 1;
-            if (launch_index(c, rs, ch.first, ch.last - ch.first + 1, job.plan.dense ? nullptr : rs->d_sel, nullptr, ch.kmers, true, !self_zeroing, 0, d_ids,
-                             d_ids ? job.chunk_pos[ci] : 0, ch.n_reads))
-                return 1;
-            ++m.sum.index_launches;
-        }
-    }
-    c->cur_slot = 0;
-    if (launch_interleave(c, g, 8) || m.tm.end_index()) return 1;
+    for (int j : in_pass) job_mask |= 1u << slot, slot += m.n_chunks(j);
     if (hipMemsetAsync(c->d_mtags, 0, (size_t) (j1 - j0) * m.tag_words() * sizeof(uint64_t), c->stream) != hipSuccess ||
         hipMemsetAsync(c->d_jobcnt, 0, 16 * sizeof(unsigned long long), c->stream) != hipSuccess)
         return fail("memset failed");
@@ -291,7 +193,7 @@ int run_shared_pass(ManyRun &m, int j0, int j1, int g)
     const float ms_s = account_pass_times(m);
     int rc = 0;
     slot = 0;
-    for (int j = j0; j < j1; ++j) {
+    for (int j : in_pass) {
         const ManyRun::Job &job = m.jobs[(size_t) j];
         uint64_t shared = 0, last_scanned = 0;
         for (size_t ci = 0; ci < job.plan.chunks.size(); ++ci, ++slot) {
@@ -321,21 +223,25 @@ int commet_index_many_and_search(commet_ctx *c, int n_jobs, const commet_readset
                                  const commet_readset *search_rs, const uint8_t *search_select, uint8_t *const *tags_out,
                                  commet_pair_stats *stats, commet_job_info *info)
 {
-    if (n_jobs < 0) return fail("n_jobs must be >= 0");
-    ManyRun m(c, n_jobs, index_rs, index_select, search_rs, search_select, tags_out, stats);
-    if (!search_rs->finalized) return fail("search read set not finalized");
-    if (search_rs->ctx != c) return fail("search read set belongs to another context");
-    for (int j = 0; j < n_jobs; ++j) {
-        if (!index_rs[j]->finalized) return fail("index read set %d not finalized", j);
-        if (index_rs[j]->ctx != c) return fail("index read set %d belongs to another context", j);
-        if (index_rs[j] == search_rs) return fail("a set cannot be searched against itself in one call");
-    }
+    if (validate_many(c, n_jobs, index_rs, search_rs)) return 1;
     HIP_OK(hipSetDevice(c->device));
     // the sets of this call keep their cached query lists, and are neither exported nor offloaded, while it runs (as in
     // commet_index_and_search; the jobs that run one by one count their own sets again: in_job is a depth)
     SetUse in_jobs(c, search_rs);
     for (int j = 0; j < n_jobs; ++j) in_jobs.add(index_rs[j]);
     if (in_jobs.enter()) return 1;
+    ManyRun m(c, n_jobs, index_rs, index_select, search_rs, search_select, tags_out, stats);
+    const OneJob one = [&](int j, commet_job_info *ji) {
+        uint8_t *to = tags_out ? tags_out[j] : nullptr;
+        return commet_index_and_search(c, index_rs[j], index_select ? index_select[j] : nullptr, 1, &search_rs, search_select ? &search_select : nullptr,
+                                       tags_out ? &to : nullptr, stats ? &stats[j] : nullptr, ji);
+    };
+    auto finish = [&](const char *what) {
+        return finish_many(m, info, what, [&](const char *w) {
+            fprintf(stderr, "[jobs x%d%s] plans %.2f ms, launches %.2f ms, wait + download %.2f ms; device: index %.2f ms, search %.2f ms\n", n_jobs, w,
+                    m.ph_plan, m.ph_launch, m.ph_wait, m.sum.index_ms, m.sum.search_ms);
+        });
+    };
     bool fast = false, pairs = false;              // pairs: jobs of ONE chunk each on a search set that takes the tiled search, two jobs per scan
     if (plan_many(m, &fast)) return 1;
     if (fast) {
@@ -351,10 +257,10 @@ int commet_index_many_and_search(commet_ctx *c, int n_jobs, const commet_readset
             pairs = most == 1;
         }
     }
-    if (!fast && !pairs) return run_alone(m, 0, n_jobs) || finish_many(m, info, nullptr);
+    if (!fast && !pairs) return run_jobs_alone(m, 0, n_jobs, one) || finish(nullptr);
     m.clk.lap(m.ph_plan);
     const int pb = ensure_pass_buffers(m, pairs ? 2 : 8);
-    if (pb) return pb == 2 ? 1 : no_room(m) || finish_many(m, info, nullptr);
+    if (pb) return pb == 2 ? 1 : rerun_alone_no_room(m, one) || finish(nullptr);
     if (pairs) {
         int j0 = 0;
         for (; j0 + 1 < n_jobs; j0 += 2) {
@@ -362,18 +268,14 @@ int commet_index_many_and_search(commet_ctx *c, int n_jobs, const commet_readset
             if (rc == 1) return 1;
             if (rc == 2) break;
         }
-        return run_alone(m, j0, n_jobs) || finish_many(m, info, ", two per tiled scan");
+        return run_jobs_alone(m, j0, n_jobs, one) || finish(", two per tiled scan");
     }
-    // passes: consecutive jobs while their chunks fit the eight slots
-    for (int j0 = 0; j0 < n_jobs;) {
-        int j1 = j0, g = 0;
-        while (j1 < n_jobs && g + (int) m.jobs[(size_t) j1].plan.chunks.size() <= 8) g += (int) m.jobs[(size_t) j1].plan.chunks.size(), ++j1;
-        const int rc = run_shared_pass(m, j0, j1, g);
+    for (const std::vector<int> &in_pass : pack_passes(m, 8)) {      // (every job shares: the passes are runs of consecutive jobs)
+        const int rc = run_shared_pass(m, in_pass);
         if (rc == 1) return 1;
-        if (rc == 2) return no_room(m) || finish_many(m, info, nullptr);
-        j0 = j1;
+        if (rc == 2) return rerun_alone_no_room(m, one) || finish(nullptr);
     }
-    return finish_many(m, info, "");
+    return finish("");
 }
 
 }  // extern "C"

@@ -1,5 +1,7 @@
 // capi/multi_profile.hpp — commet_index_many_and_profile: several commet_index_and_profile jobs that search the SAME read set, their chunk filters
-// side by side in one hits pass (a part of the one translation unit capi.hip: included there, in order, after multi.hpp and profile.hpp)
+// side by side in one hits pass (a part of the one translation unit capi.hip: included there, in order, after many.hpp, multi.hpp and profile.hpp)
+// Here: which jobs a pass admits, the visited reads of the search set, the hits pass and its byte arrays.  The call's record, the argument
+// checks, a job's plan, jobs run alone, the packing and the build of a pass's filters are many.hpp's, shared with commet_index_many_and_search.
 //
 // The threshold sweep of the symmetric comparison (commet_amd/sweep.py --full) runs, for every t, "A in (B restricted to the reads
 // found at t)": T jobs that index selections of ONE set and all search A.  Alone each job walks A and makes its plane-A gathers,
@@ -12,8 +14,8 @@
 // A pass: the jobs in their order while their chunks fit min(8, chunk_group) slots (a job that runs alone does not close a pass);
 // a job is never split, so its byte array is written by one pass.  The jobs are planned on the device (plan_index_on_device) and
 // built one after the other on the context's one stream — jobs may index the same set under different selections: the selection
-// bitmap, and the list made of it, go up in front of each job's build — a chunk that does not take the bucketed build into a zeroed
-// slot.  The search selection is the same for all jobs and reaches the kernel as the visited bitmap of plan_search: no list form.
+// bitmap, and the list made of it, go up in front of each job's build (build_pass_filters, many.hpp) — a chunk that does not take the
+// bucketed build into a zeroed slot.  The search selection is the same for all jobs and reaches the kernel as the visited bitmap of plan_search: no list form.
 //
 // Through commet_index_and_profile itself, same bytes: the whole call when n_jobs < 2, k < 2, count_probes, multi_job = 1,
 // chunk_group = 1, the search set is empty or takes the wave-per-read hits kernel and multi_job is not 2, or the device has no room
@@ -27,65 +29,22 @@
 
 namespace {
 
-// one commet_index_many_and_profile call
-struct ProfileManyRun {
-    commet_ctx *c;
-    int n_jobs;
-    const commet_readset *const *index_rs;
-    const uint8_t *const *index_select;
-    const commet_readset *search_rs;
-    const uint8_t *search_select;
+// one commet_index_many_and_profile call (the record both many-job calls keep: ManyCall, many.hpp)
+struct ProfileManyRun : ManyCall {
     const int *max_hits;
     uint8_t *const *hits_out;
-    struct Job {
-        IndexPlan plan;
-        const uint8_t *sel = nullptr;
-        std::vector<uint64_t> chunk_pos;        // first position of every chunk in the job's list of selected reads
-        bool shares = false;                    // planned on the device, 1 .. cap chunks, each with a read
-    };
-    std::vector<Job> jobs;
     int cap = 8;                                // slots of a pass
     std::vector<uint8_t> vis;                   // the reads the passes visit (plan_search), unless all of them
     bool all_visited = false;
     uint64_t stride = 256;                      // bytes between the arrays of two jobs of a pass
     int shared_passes = 0;
-    commet_job_info sum = commet_job_info();
-    PhaseClock clk;
-    double ph_plan = 0, ph_launch = 0, ph_wait = 0;
-    JobTimer tm;                                // one bracket per shared pass: its builds, then its one scan
     ProfileManyRun(commet_ctx *c_, int n, const commet_readset *const *irs, const uint8_t *const *isel, const commet_readset *srs, const uint8_t *ssel,
                    const int *caps, uint8_t *const *hits)
-        : c(c_), n_jobs(n), index_rs(irs), index_select(isel), search_rs(srs), search_select(ssel), max_hits(caps), hits_out(hits), tm(c_, true, 1)
+        : ManyCall(c_, n, irs, isel, srs, ssel), max_hits(caps), hits_out(hits)
     {
     }
     const uint64_t *d_sel() const { return all_visited ? nullptr : search_rs->d_sel; }
 };
-
-// jobs j0 .. j1 - 1 through commet_index_and_profile, one after the other, summed into the call's account
-int profile_alone(ProfileManyRun &m, int j0, int j1)
-{
-    for (int j = j0; j < j1; ++j) {
-        commet_job_info ji = commet_job_info();
-        const uint8_t *ss = m.search_select;
-        uint8_t *to = m.hits_out ? m.hits_out[j] : nullptr;
-        if (commet_index_and_profile(m.c, m.index_rs[j], m.index_select ? m.index_select[j] : nullptr, 1, &m.search_rs, m.search_select ? &ss : nullptr,
-                                     m.max_hits[j], m.hits_out ? &to : nullptr, &ji))
-            return 1;
-        add_info(m.sum, ji);
-    }
-    return 0;
-}
-
-// no room for the slots or the byte arrays of a shared pass: every job through commet_index_and_profile, which degrades on its own
-// (run_slot_groups).  The single calls write every byte of every job again
-int profile_no_room(ProfileManyRun &m)
-{
-    (void) hipGetLastError();
-    m.c->cur_slot = 0;
-    m.sum = commet_job_info();
-    m.shared_passes = 0;
-    return profile_alone(m, 0, m.n_jobs);
-}
 
 // does the call share passes at all?  A search set of long reads (hits_wave_ok, profile.hpp) under multi_job = 2 only: auto keeps
 // such a set job by job, as multi.hpp does on the search side
@@ -104,16 +63,12 @@ int plan_profile_many(ProfileManyRun &m)
     const uint64_t max_kmer = commet_max_kmer(c);
     m.jobs.resize((size_t) m.n_jobs);
     for (int j = 0; j < m.n_jobs; ++j) {
-        const commet_readset *rs = m.index_rs[j];
         ProfileManyRun::Job &job = m.jobs[(size_t) j];
-        job.sel = m.index_select ? m.index_select[j] : nullptr;
-        if (job.sel && all_ones(job.sel, rs->n_reads)) job.sel = nullptr;
-        if (!rs->n_reads || !plan_blocks_ok(rs->files, job.sel, rs->empty_reads, max_kmer)) continue;
-        if (plan_index_on_device(c, rs, job.sel, max_kmer, &job.plan)) return 1;
-        job.shares = !job.plan.chunks.empty() && job.plan.chunks.size() <= (size_t) m.cap;
+        if (plan_many_job(m, j, max_kmer, &job.shares)) return 1;
+        // a pass takes a planned job of 1 .. cap chunks, each with a read
+        if (job.plan.chunks.empty() || job.plan.chunks.size() > (size_t) m.cap) job.shares = false;
         for (const Chunk &ch : job.plan.chunks)
             if (!ch.n_reads) job.shares = false;
-        job.chunk_pos = chunk_positions(job.plan);
     }
     const commet_readset *srs = m.search_rs;
     const uint8_t *ssel = m.search_select;
@@ -159,47 +114,24 @@ int launch_hits_jobs(commet_ctx *c, const commet_readset *rs, int g, int gs, con
     return 0;
 }
 
-// ---- a shared pass: the jobs `in_pass`, whose g chunks fit the pass's slots ------------------------------------------------------------
+// ---- a shared pass: the jobs `in_pass`, whose chunks fit the pass's slots ---------------------------------------------------------------
 // 0 = done, 1 = error, 2 = no room
-int run_shared_hits_pass(ProfileManyRun &m, const std::vector<int> &in_pass, int g)
+int run_shared_hits_pass(ProfileManyRun &m, const std::vector<int> &in_pass)
 {
     commet_ctx *c = m.c;
     const commet_readset *srs = m.search_rs;
-    const int gs = g <= 2 ? 2 : g <= 4 ? 4 : 8;
-    if (ensure_slots(c, g, gs)) return 2;
-    if (m.tm.begin_index()) return 1;
-    JobSlots js{0, 0};
+    const int g = pass_chunks(m, in_pass), gs = g <= 2 ? 2 : g <= 4 ? 4 : 8;
+    if (const int rc = build_pass_filters(m, in_pass, g, gs)) return rc;
+    JobSlots js{0, 0};                              // per slot: the slots of its job, and the job's cap
     int slot = 0;
     for (int j : in_pass) {
-        const commet_readset *rs = m.index_rs[j];
         const ProfileManyRun::Job &job = m.jobs[(size_t) j];
-        const int nc = (int) job.plan.chunks.size();
+        const int nc = m.n_chunks(j);
         const uint64_t mates = ((1ull << nc) - 1ull) << slot;
         for (int i = slot; i < slot + nc; ++i) js.mates |= mates << (8 * i), js.caps |= (uint64_t) m.max_hits[j] << (8 * i);
-        // the job's selection, and its selected reads as a list for the bucketed build of a fixed-length set (no room: the build walks
-        // the bitmap); builds, uploads and lists are ordered on the one stream, so the set's bitmap and the context's list buffer serve
-        // job after job — two jobs on one set under two selections included
-        const uint32_t *d_ids = nullptr;
-        if (!job.plan.dense && upload_bits(c, rs->d_sel, job.plan.indexed_bits.data(), rs->n_reads)) return 1;
-        if (!job.plan.dense && rs->uniform_len != 0 && !c->part_no_uni && c->index_mode != 1 && build_selection_list(c, c->sel_ids, rs, job.plan, &d_ids)) {
-            (void) hipGetLastError();
-            d_ids = nullptr;
-        }
-        for (int ci = 0; ci < nc; ++ci, ++slot) {
-            const Chunk &ch = job.plan.chunks[(size_t) ci];
-            c->cur_slot = slot;
-            // a chunk that does not take the bucketed build (which writes every tile of its slot) meets a zeroed slot, as in build_group
-            const bool self_zeroing = would_partition(c, rs, ch.kmers, ch.last - ch.first + 1);
-            if (!self_zeroing && commet_filter_reset(c)) return 1;
-            if (launch_index(c, rs, ch.first, ch.last - ch.first + 1, job.plan.dense ? nullptr : rs->d_sel, nullptr, ch.kmers, true, !self_zeroing, 0, d_ids,
-                             d_ids ? job.chunk_pos[(size_t) ci] : 0, ch.n_reads))
-                return 1;
-            ++m.sum.index_launches;
-        }
+        slot += nc;
         m.sum.n_chunks += (uint64_t) nc, m.sum.kmers_indexed += job.plan.kmers, m.sum.reads_indexed += job.plan.indexed_reads;
     }
-    c->cur_slot = 0;
-    if (launch_interleave(c, g, gs) || m.tm.end_index()) return 1;
     if (hipMemsetAsync(c->d_hits, 0, in_pass.size() * m.stride, c->stream) != hipSuccess ||
         hipMemsetAsync(c->d_jobcnt, 0, sizeof(unsigned long long), c->stream) != hipSuccess)
         return fail("memset failed");
@@ -214,10 +146,7 @@ int run_shared_hits_pass(ProfileManyRun &m, const std::vector<int> &in_pass, int
     HIP_OK(hipStreamSynchronize(c->stream));
     c->kclock.collect();
     m.sum.reads_scanned += c->h_counters[0];
-    float ms_i = 0, ms_s = 0;
-    (void) m.tm.index_ms(m.tm.brackets() - 1, &ms_i);
-    (void) m.tm.set_ms(m.tm.brackets() - 1, 0, &ms_s);
-    m.sum.index_ms += ms_i, m.sum.index_kernel_ms += ms_i, m.sum.search_ms += ms_s;
+    (void) account_pass_times(m);
     m.clk.lap(m.ph_wait);
     return 0;
 }
@@ -230,15 +159,9 @@ int commet_index_many_and_profile(commet_ctx *c, int n_jobs, const commet_readse
                                   const commet_readset *search_rs, const uint8_t *search_select, const int *max_hits, uint8_t *const *hits_out,
                                   commet_job_info *info)
 {
-    if (n_jobs < 0) return fail("n_jobs must be >= 0");
-    if (!search_rs->finalized) return fail("search read set not finalized");
-    if (search_rs->ctx != c) return fail("search read set belongs to another context");
-    for (int j = 0; j < n_jobs; ++j) {
-        if (!index_rs[j]->finalized) return fail("index read set %d not finalized", j);
-        if (index_rs[j]->ctx != c) return fail("index read set %d belongs to another context", j);
-        if (index_rs[j] == search_rs) return fail("a set cannot be searched against itself in one call");
+    if (validate_many(c, n_jobs, index_rs, search_rs)) return 1;
+    for (int j = 0; j < n_jobs; ++j)
         if (max_hits[j] < 1 || max_hits[j] > 255) return fail("max_hits must be in 1..255 (got %d for job %d)", max_hits[j], j);
-    }
     HIP_OK(hipSetDevice(c->device));
     // the sets of this call are neither exported nor offloaded while it runs (the jobs that run alone count their own sets again: in_job is a depth)
     SetUse in_jobs(c, search_rs);
@@ -246,58 +169,54 @@ int commet_index_many_and_profile(commet_ctx *c, int n_jobs, const commet_readse
     if (in_jobs.enter()) return 1;
     ProfileManyRun m(c, n_jobs, index_rs, index_select, search_rs, search_select, max_hits, hits_out);
     m.cap = std::max(1, std::min(8, c->chunk_group));
-    auto finish = [&](const char *what) {
-        m.sum.total_ms = m.clk.total_ms();
-        m.sum.probes = 0;
-        if (what && c->job_verbose)
-            fprintf(stderr, "[profiles x%d%s] %d shared pass(es); plans %.2f ms, launches %.2f ms, wait + download %.2f ms\n", n_jobs, what, m.shared_passes,
-                    m.ph_plan, m.ph_launch, m.ph_wait);
-        if (info) *info = m.sum;
-        return 0;
+    const OneJob one = [&](int j, commet_job_info *ji) {
+        uint8_t *to = hits_out ? hits_out[j] : nullptr;
+        return commet_index_and_profile(c, index_rs[j], index_select ? index_select[j] : nullptr, 1, &search_rs, search_select ? &search_select : nullptr,
+                                        max_hits[j], hits_out ? &to : nullptr, ji);
     };
-    if (!profile_many_ok(m)) return profile_alone(m, 0, n_jobs) || finish(nullptr);
+    auto finish = [&](const char *what) {
+        m.sum.probes = 0;
+        return finish_many(m, info, what, [&](const char *w) {
+            fprintf(stderr, "[profiles x%d%s] %d shared pass(es); plans %.2f ms, launches %.2f ms, wait + download %.2f ms\n", n_jobs, w, m.shared_passes,
+                    m.ph_plan, m.ph_launch, m.ph_wait);
+        });
+    };
+    // no room for the slots or the byte arrays of a shared pass: the single calls write every byte of every job again
+    auto no_room = [&]() {
+        m.shared_passes = 0;
+        return rerun_alone_no_room(m, one) || finish(nullptr);
+    };
+    if (!profile_many_ok(m)) return run_jobs_alone(m, 0, n_jobs, one) || finish(nullptr);
     if (plan_profile_many(m)) return 1;
     m.clk.lap(m.ph_plan);
-    // the passes: the sharing jobs in their order while their chunks fit the slots (a job that runs alone does not close a pass);
-    // a pass of one job runs alone too
-    std::vector<std::vector<int>> passes(1);
+    // a pass of one job runs alone too, as the jobs that do not share; fewer than two jobs in every pass: the whole call job by job
+    const std::vector<std::vector<int>> passes = pack_passes(m, m.cap);
     std::vector<int> alone;
-    int g = 0;
-    for (int j = 0; j < n_jobs; ++j) {
-        const ProfileManyRun::Job &job = m.jobs[(size_t) j];
-        if (!job.shares) {
-            alone.push_back(j);
-            continue;
-        }
-        if (g + (int) job.plan.chunks.size() > m.cap) passes.emplace_back(), g = 0;
-        passes.back().push_back(j);
-        g += (int) job.plan.chunks.size();
-    }
+    for (int j = 0; j < n_jobs; ++j)
+        if (!m.jobs[(size_t) j].shares) alone.push_back(j);
     size_t most = 0;
     for (const std::vector<int> &ps : passes) {
         most = std::max(most, ps.size());
         if (ps.size() == 1) alone.push_back(ps[0]);
     }
-    if (most < 2) return profile_alone(m, 0, n_jobs) || finish(nullptr);
+    if (most < 2) return run_jobs_alone(m, 0, n_jobs, one) || finish(nullptr);
     // a byte per read and job of a pass (each job's bytes start on a 256-byte line), and the count of walked reads
     m.stride = (search_rs->n_reads + 255) & ~255ull;
     const uint64_t n_bytes = (uint64_t) most * m.stride;
-    if (grow_kept(c, c->d_hits, c->hits_cap, n_bytes, n_bytes)) return profile_no_room(m) || finish(nullptr);
+    if (grow_kept(c, c->d_hits, c->hits_cap, n_bytes, n_bytes)) return no_room();
     if (grow_kept(c, c->d_jobcnt, c->jobcnt_cap, 1, 64)) return 1;
     for (int j : alone)
-        if (profile_alone(m, j, j + 1)) return 1;
+        if (run_jobs_alone(m, j, j + 1, one)) return 1;
     if (upload_visited(m)) return 1;                // (behind the jobs that ran alone: they plan the search set on their own)
     for (const std::vector<int> &ps : passes) {
         if (ps.size() < 2) continue;
-        g = 0;
-        for (int j : ps) g += (int) m.jobs[(size_t) j].plan.chunks.size();
-        const int rc = run_shared_hits_pass(m, ps, g);
+        const int rc = run_shared_hits_pass(m, ps);
         c->cur_slot = 0;
         if (rc == 1) {
             (void) hipStreamSynchronize(c->stream);     // (host bit arrays of the call may be on their way up)
             return 1;
         }
-        if (rc == 2) return profile_no_room(m) || finish(nullptr);
+        if (rc == 2) return no_room();
     }
     return finish("");
 }

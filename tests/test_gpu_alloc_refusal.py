@@ -2,8 +2,8 @@
 of dm_malloc, capi/state.hpp) on small shapes, every result against the CPU checker on the same reads.
 
 "Out of device memory costs speed, never correctness" is promised at more than a dozen sites (the slot ladder 8 -> 4 -> 1 of
-run_slot_groups, ensure_slots' "only the g needed now", wide rows -> narrow tables -> slot loop, no_room / run_alone of
-commet_index_many_and_search, query lists, length order, sparse lists, item lists, dev_alloc's retry, restore, create).  A refusal at
+run_slot_groups, ensure_slots' "only the g needed now", wide rows -> narrow tables -> slot loop, rerun_alone_no_room of
+the many-job calls, the list of a job's selected reads, query lists, length order, sparse lists, item lists, dev_alloc's retry, restore, create).  A refusal at
 the top of dm_malloc is, for every caller, the driver saying no.
 
 Two modes.  By size: every request of at least `at_least` bytes is refused.  By count: the nth request from arming on is refused once
@@ -25,7 +25,7 @@ returns the unarmed outputs, or raises an allocation error (never "internal erro
 refused == 1 for every n; the sites that promise a fallback must return.  A line per n is printed: n, last_refused_bytes, outcome.
 
 Two cases differ from the issue's table, by reading the code.  (g) Index sets of 3 + 5 chunks fit ONE pass of eight slots, so the
-refusal sends the call to no_room before any pass has run; the described course — pass one on three granted slots, pass two without
+refusal sends the call to rerun_alone_no_room before any pass has run; the described course — pass one on three granted slots, pass two without
 room, after pass one has written its stats — needs 3 + 6, which runs as well.  (p) An oversize read under index_mode = 2 is a clean
 error ("needs memory for the item list"); the atomic fallback behind it is reached only with LONG_INDEX_AUTO, which is false."""
 import re
@@ -255,8 +255,8 @@ def check_many(what, got, truths, n):
 
 @pytest.mark.parametrize("chunk_counts", [(3, 5), (3, 6)])
 def test_shared_passes_without_room(tmp_path, chunk_counts):
-    """3 + 5 chunks are ONE pass of eight slots: refused at once, no_room before anything ran.  3 + 6: pass one (job 0) runs on three
-    granted slots and writes its stats, pass two finds no room, no_room runs every job again alone and the account starts over"""
+    """3 + 5 chunks are ONE pass of eight slots: refused at once, rerun_alone_no_room before anything ran.  3 + 6: pass one (job 0) runs on three
+    granted slots and writes its stats, pass two finds no room, rerun_alone_no_room runs every job again alone and the account starts over"""
     k = SLOT_K
     jobs, search, truths = many_case(tmp_path, k, chunk_counts)
     n, total = len(search), sum(chunk_counts)
@@ -338,6 +338,124 @@ def test_pairs_without_room(tmp_path):
         assert r.seen["refused"] == 1 and r.seen["last_refused_bytes"] == (n_slices * n_pieces + 1) * 8, r.seen
         assert only(ran, tq) == {"search_kernel": 5} and got[2]["search_launches"] == 5, (ran, got[2])
         check_many("no list", got, truths, n)
+
+
+# ---- (i') the list of a job's selected reads, refused inside a call of several jobs ------------------------------------------------------------------
+# The list (sel_ids; job_parts.hpp, prepare_job_selection) is an optimisation of the bucketed build of a set of one read length: without
+# room for it the build walks the selection bitmap.  That must hold inside a shared pass and a pair as it does for a job alone: the
+# call goes on sharing, and every output is the checker's.
+_SELECTED = {}
+
+
+def selected_case(tmp_path, k, chunk_counts, n0=60, L=100, n_search=150):
+    """many_case for index sets of ONE read length under a real selection (every third read dropped: plans neither dense nor all-ones).
+    Job 0 fixes max_kmer for its chunk count, the others get the fewest reads that make theirs at that max_kmer; jobs of one chunk
+    are one chunk without the selection too.  -> (jobs [dict(index, select, max_kmer)], search, truths)"""
+    import oracle_pool
+    key = (k, tuple(chunk_counts), n0, L, n_search)
+    if key not in _SELECTED:
+        rng = np.random.default_rng(7000 + 100 * k + sum(chunk_counts))
+        w = L - k + 1
+        select = lambda n: np.arange(n) % 3 != 0
+        first = [hg.rand(rng, L) for _ in range(n0)]
+        max_kmer = n0 * w + 1 if chunk_counts[0] == 1 else jf.max_kmer_for(k, first, chunk_counts[0], select(n0))[0]
+        jobs = [dict(index=first, select=select(n0), max_kmer=max_kmer)]
+        for c in chunk_counts[1:]:
+            for n in range(n0, 8 * n0):
+                cut = oracle_pool.chunks_from_counts(np.full(int(select(n).sum()), w), max_kmer)
+                if len(cut) == c and cut[-1][1] - cut[-1][0] >= 3:
+                    break
+            jobs.append(dict(index=[hg.rand(rng, L) for _ in range(n)], select=select(n), max_kmer=max_kmer))
+        search = []
+        for i in range(n_search):                                               # every job finds some of them
+            job = jobs[i // 3 % len(jobs)]
+            if i % 3 == 2:
+                search.append(hg.rand(rng, 80))
+            else:
+                r = job["index"][int(rng.choice(np.nonzero(job["select"])[0]))]
+                a = int(rng.integers(0, L - 80 + 1))
+                search.append(r[a:a + 80])
+        _SELECTED[key] = jobs, search
+    jobs, search = _SELECTED[key]
+    truths = [truth_of(tmp_path, ("selected", key, j), k, T, job["index"], [search], job["max_kmer"], index_select=job["select"]) for j, job in enumerate(jobs)]
+    assert [tr["chunks"] for tr in truths] == list(chunk_counts)
+    assert all(tr["stats"][0]["shared"] > 0 for tr in truths)
+    return jobs, search, truths
+
+
+def ids_bytes(n_reads, indexed):
+    """build_selection_list -> build_id_list: max(the plan's indexed reads, half the set) ids of four bytes"""
+    return max(indexed, n_reads // 2) * 4
+
+
+def test_selection_list_refused_in_a_shared_pass(tmp_path):
+    """by count: the context has run the call on the whole sets (dense plans: every buffer of a shared pass, no list), so job 0's list is
+    the first thing the call under selections asks for.  Job 0 is built from the bitmap, job 1 from its list, in ONE pass"""
+    k = SLOT_K
+    jobs, search, truths = selected_case(tmp_path, k, (2, 3))
+    n = len(search)
+    sels = [util.bits_from_bools(j["select"]) for j in jobs]
+    with context(k, jobs[0]["max_kmer"]) as ctx:
+        sets, qrs = [load(ctx, j["index"]) for j in jobs], load(ctx, search)
+        _, ran = timed(ctx, lambda: ctx.index_many_and_search(sets, qrs))
+        assert "search_group8_kernel" in ran and "sel_ids_kernels" not in ran, ran
+        call = lambda: ctx.index_many_and_search(sets, qrs, index_selects=sels)
+        with refusing(nth=1) as r:
+            got, ran = timed(ctx, call)
+        print("list, shared pass", ran, r.seen, got[2])
+        assert r.seen["refused"] == 1 and r.seen["last_refused_bytes"] == ids_bytes(len(jobs[0]["index"]), truths[0]["stats"][0]["indexed"]), r.seen
+        assert only(ran, tps.SEARCH_KERNELS) == {"search_group8_kernel": 1} and got[2]["search_launches"] == 1, ran
+        assert ran.get("sel_ids_kernels") == 1, ran
+        check_many("armed", got, truths, n)
+        again, ran = timed(ctx, call)                                            # disarmed: both lists, the same result
+        assert only(ran, tps.SEARCH_KERNELS) == {"search_group8_kernel": 1} and ran.get("sel_ids_kernels") == 2, ran
+        check_many("disarmed", again, truths, n)
+        assert same_job(again, got)
+
+
+def test_selection_list_refused_in_a_pair(tmp_path):
+    """the same for two jobs of one chunk each that go through one tiled scan (run_pair)"""
+    k = 25                                                                       # (the tiled search: k > 24)
+    jobs, search, truths = selected_case(tmp_path, k, (1, 1))
+    n = len(search)
+    sels = [util.bits_from_bools(j["select"]) for j in jobs]
+    tq = ("tq_probe_kernel", "tq_replay_kernel", "search_kernel", "search_group_kernel", "search_group8_kernel")
+    with context(k, jobs[0]["max_kmer"], tiled_search=2) as ctx:
+        sets, qrs = [load(ctx, j["index"]) for j in jobs], load(ctx, search)
+        _, ran = timed(ctx, lambda: ctx.index_many_and_search(sets, qrs))
+        assert only(ran, tq) == {"tq_probe_kernel": 1, "tq_replay_kernel": 1} and "sel_ids_kernels" not in ran, ran
+        qrs.drop_cache()                                                         # (else dev_alloc gives the set's query list back and asks again: granted)
+        with refusing(nth=1) as r:
+            got, ran = timed(ctx, lambda: ctx.index_many_and_search(sets, qrs, index_selects=sels))
+        print("list, pair", ran, r.seen, got[2])
+        assert r.seen["refused"] == 1 and r.seen["last_refused_bytes"] == ids_bytes(len(jobs[0]["index"]), truths[0]["stats"][0]["indexed"]), r.seen
+        assert only(ran, tq) == {"tq_probe_kernel": 1, "tq_replay_kernel": 1} and got[2]["search_launches"] == 1, ran
+        assert ran.get("sel_ids_kernels") == 1, ran
+        check_many("armed", got, truths, n)
+
+
+def test_selection_list_refused_in_a_shared_profile_pass(tmp_path):
+    """the threshold sweep's shape: two jobs on ONE set under two selections, caps 2 and 4; bytes as each job gives alone"""
+    k = SLOT_K
+    jobs, search, _ = selected_case(tmp_path, k, (2, 3))
+    index = jobs[0]["index"]
+    sels = [util.bits_from_bools(np.arange(len(index)) % 3 != m) for m in (0, 1)]
+    caps = [2, 4]
+    with context(k, jobs[0]["max_kmer"]) as ctx:
+        irs, qrs = load(ctx, index), load(ctx, search)
+        _, ran = timed(ctx, lambda: ctx.index_many_and_profile([irs, irs], qrs, max_hits=caps))
+        assert ran.get("hits_jobs_kernel") == 1 and "sel_ids_kernels" not in ran, ran
+        with refusing(nth=1) as r:
+            (hits, info), ran = timed(ctx, lambda: ctx.index_many_and_profile([irs, irs], qrs, index_selects=sels, max_hits=caps))
+        print("list, shared hits pass", ran, r.seen, info)
+        assert ran.get("hits_jobs_kernel") == 1 and not only(ran, HITS_KERNELS) and info["search_launches"] == 1, ran
+        assert ran.get("sel_ids_kernels") == 1, ran
+        alone = [ctx.index_and_profile(irs, [qrs], index_select=sels[j], max_hits=caps[j]) for j in range(2)]
+        assert r.seen["refused"] == 1 and r.seen["last_refused_bytes"] == ids_bytes(len(index), alone[0][1]["reads_indexed"]), r.seen
+        for j in range(2):
+            assert np.array_equal(hits[j], alone[j][0][0]) and hits[j].any(), j
+        for f in ("n_chunks", "kmers_indexed", "reads_indexed"):
+            assert info[f] == sum(a[1][f] for a in alone), (f, info)
 
 
 # ---- (j) the query list of one job ---------------------------------------------------------------------------------------------------------------
@@ -844,6 +962,27 @@ def test_sweep_pairs(tmp_path):
                      {2 * filter_bytes(k), 2 * plane_bytes(k), (entries + 1) * 8})
     check_many("sweep pairs", base, truths, len(search))
     assert base[2]["search_launches"] == 2
+
+
+def test_sweep_shared_profile_passes(tmp_path):
+    """commet_index_many_and_profile: the slot group, the interleaved planes and the jobs' byte arrays promise a fallback.  (More than
+    256 search reads: two lines of bytes per job, so that the byte arrays are not the 512 bytes of the walked-reads counter, whose
+    refusal is an error)"""
+    commet = _commet()
+    k, caps = SWEEP_K, [2, 4]
+    jobs, search, truths = many_case(tmp_path, k, (2, 3), n_search=300)
+    lines = (len(search) + 255) // 256
+    assert lines == 2
+
+    def make():
+        ctx = context(k, jobs[0]["max_kmer"])
+        return ctx, [load(ctx, j["index"]) for j in jobs], load(ctx, search)
+
+    base, *_ = sweep("shared profile passes", make, lambda s: s[0].index_many_and_profile(s[1], s[2], max_hits=caps), same_profile,
+                     {8 * filter_bytes(k), 8 * plane_bytes(k), len(jobs) * 256 * lines})
+    for j, tr in enumerate(truths):
+        assert np.array_equal(util.bools_from_bits(commet.tags_at(base[0][j], T), len(search)), tr["tags"][0]), j
+    assert base[1]["search_launches"] == 1 and base[1]["n_chunks"] == 5 and base[1]["kmers_indexed"] == sum(tr["kmers"] for tr in truths)
 
 
 def test_sweep_long_reads(tmp_path):
