@@ -307,6 +307,18 @@ class Context:
         self._check(self._lib.commet_filter_export_reference(self._h, _ptr(out), out.size))
         return out[:nbytes]
 
+    def filter_set_bits(self, slot=0, cap=1 << 23):
+        """test hook: the set bits of `slot` as stored, sorted np.uint64 words (plane << 56) | address within the plane (plane 0 = A at
+        its psi_a address, 1..3 = B, C, D at the key) — exact at every k, where the byte export needs 2^(k-1) bytes of host memory.
+        More than `cap` set bits: CommetError, which names the count."""
+        self.set_option("export_slot", slot)
+        out = np.zeros(max(int(cap), 1), dtype=np.uint64)
+        n = C.c_uint64(0)
+        self._check(self._lib.commet_filter_set_bits(self._h, _ptr(out), int(cap), C.byref(n)))
+        if n.value > cap:
+            raise CommetError(f"filter_set_bits: slot {slot} holds {n.value} set bits, cap = {cap}")
+        return np.sort(out[:n.value])
+
     def last_kernel_ms(self):
         i = C.c_double(0)
         s = C.c_double(0)

@@ -17,6 +17,7 @@
 #include "hit_profile_sliced.hpp"
 #include "hit_profile_tiled.hpp"
 #include "read_filter.hpp"
+#include "filter_bits.hpp"
 #include "read_iter.hpp"
 #include "host/fasta_source.hpp"
 #include "host/ingest_pack.hpp"

@@ -187,6 +187,32 @@ int commet_filter_export_reference(commet_ctx *c, uint8_t *out, uint64_t out_byt
     return 0;
 }
 
+int commet_filter_set_bits(commet_ctx *c, uint64_t *out, uint64_t cap, uint64_t *n_out)
+{
+    if (!c || !n_out || (cap && !out)) return fail("commet_filter_set_bits: null argument");
+    if (c->export_slot < 0 || c->export_slot >= c->n_slots)
+        return fail("filter set bits: slot %d asked for (option export_slot), the context has %d", c->export_slot, c->n_slots);
+    HIP_OK(hipSetDevice(c->device));
+    uint64_t *d_buf = nullptr;                                  // [count][cap words]
+    HIP_OK(dm_malloc((void **) &d_buf, (cap + 1) * sizeof(uint64_t)));
+    unsigned long long n = 0;
+    hipError_t e = hipMemsetAsync(d_buf, 0, sizeof(uint64_t), c->stream);
+    if (e == hipSuccess) {
+        const uint64_t blocks = std::min<uint64_t>((c->plane_words + 255) / 256, 1u << 14);   // grid-stride beyond; 16 B per thread and round
+        COMMET_LAUNCH(filter_set_bits_kernel, dim3((unsigned) blocks), dim3(256), 0, c->stream, c->slot_ptr(c->export_slot), c->plane_words,
+                      1ull << c->k, cap, d_buf + 1, (unsigned long long *) d_buf);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(&n, d_buf, sizeof n, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    const uint64_t have = std::min<uint64_t>(n, cap);
+    if (e == hipSuccess && have) e = hipMemcpy(out, d_buf + 1, have * sizeof(uint64_t), hipMemcpyDeviceToHost);
+    (void) dm_free(d_buf);
+    if (e != hipSuccess) return fail("filter set bits failed: %s", hipGetErrorString(e));
+    *n_out = n;
+    return 0;
+}
+
 int commet_launched_kernels(const void **out, int cap, int *n_out)
 {
     std::lock_guard<std::mutex> lk(g_launch_mu);

@@ -98,6 +98,7 @@ SIGNATURES = {
                                                 C.POINTER(C.c_int), C.POINTER(C.c_void_p), C.POINTER(JobInfo)]),
     "commet_set_option": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int64]),
     "commet_filter_export_reference": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
+    "commet_filter_set_bits": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, u64p]),
     "commet_last_kernel_ms": (C.c_int, [C.c_void_p, f64p, f64p]),
     "commet_kernel_times": (C.c_int, [C.c_void_p, C.POINTER(KernelTime), C.c_int, C.POINTER(C.c_int)]),
     "commet_launched_kernels": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_int)]),

@@ -449,6 +449,11 @@ int commet_set_option(commet_ctx *ctx, const char *name, int64_t value);
  * bloom_filter.h:63-70,114-117); out has 2^(k-1) bytes.  For parity tests.
  * The slot of option "export_slot" (default 0). */
 int commet_filter_export_reference(commet_ctx *ctx, uint8_t *out, uint64_t out_bytes);
+/* TEST HOOK. The set bits of the filter slot of option "export_slot", as stored: one 64-bit word per bit,
+ * (plane << 56) | bit address within the plane (plane 0 = A at its psi_a address, 1..3 = B, C, D at `key`).
+ * Only addresses below 2^k are reported. Order unspecified. Writes at most cap words; *n_out = set bits found
+ * (> cap: the caller's list is incomplete). Fails like commet_filter_export_reference when the context has no such slot. */
+int commet_filter_set_bits(commet_ctx *ctx, uint64_t *out, uint64_t cap, uint64_t *n_out);
 /* Device time in ms of the most recent index / search kernel launch on this
  * ctx, measured with hipEvents on the ctx's stream (synchronises). */
 int commet_last_kernel_ms(commet_ctx *ctx, double *index_ms, double *search_ms);

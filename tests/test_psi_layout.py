@@ -1,7 +1,8 @@
 """The strand-paired layout of filter plane A (psi_a, commet_amd/csrc/kernels.hpp), mirrored in numpy:
 a bijection of [0, 2^k) with psi(T(key)) == psi(key) ^ 1, T(x) = ~bitreverse_k(x) being the map from a
 window's forward keya to its reverse-complement keya (hash_key.h:63-123).  The device implementation itself
-is exercised by the GPU parity tests (filter export + search results)."""
+is exercised by the GPU parity tests (filter export + search results) and compared with `psi` itself, bit by bit,
+in test_gpu_filter_bits.py (filter_bits.py imports `psi` from here: the one copy; k = 17 .. 38 on samples: test_filter_bits_cpu.py)."""
 import numpy as np
 import pytest
 
