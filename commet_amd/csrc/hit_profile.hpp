@@ -18,8 +18,8 @@
 // filters are ordered on the context's stream.  A read whose byte is max_hits on entry is skipped (exact: nothing can raise it).
 // `walked` (optional) counts the reads a pass did walk.
 //
-// Included by capi.hip behind long_search.hpp (KeyCtx, ItemWords, psi_a, probe_bcd_chain, search_lane, LONG_WG, LONG_STAGE_WORDS); not
-// meant to stand alone.
+// Included by capi.hip behind long_search.hpp (KeyCtx, ItemWords, psi_a, probe_bcd_chain, search_lane, count_walked, LONG_WG,
+// wave_block_words, greedy_take); not meant to stand alone.
 #pragma once
 
 namespace commet {
@@ -97,12 +97,7 @@ __global__ __launch_bounds__(256) COMMET_SGPRS void hits_kernel(ReadsView rv, Fi
         const int h = min(max_hits, max(cnt_f, cnt_r));
         if (h > before) hits[r] = (uint8_t) h;
     }
-    if (walked) {
-        __shared__ unsigned int wg_walked;
-        if (threadIdx.x == 0) wg_walked = 0;
-        __syncthreads();
-        add_walked(walked, walk, wg_walked);
-    }
+    count_walked(walked, walk);
 }
 
 // ---------------------------------------------------------------------------
@@ -140,23 +135,9 @@ __global__ __launch_bounds__(LONG_WG) void hits_wave_kernel(ReadsView rv, Filter
         const int n_win = (int) len - k + 1;               // windows of the read, by their start (<= 0: none)
         int next_free[2] = {0, 0}, count[2] = {0, 0};      // [strand]
         for (int base = 0; base < n_win && count[0] < max_hits && count[1] < max_hits; base += 64) {
-            // the read's words this block's windows stand on: words w0 - 2 .. w0 + 4, one per lane (zeros outside the read)
-            const int w0 = base >> 5;
-            uint32_t staged = 0;
-            {
-                const int wi = w0 - 2 + lane / 3;
-                if (lane < 3 * LONG_STAGE_WORDS && wi >= 0 && wi < n_words) staged = p[3 * wi + lane % 3];
-            }
             const int s = base + lane, q = s + k - 1;
-            ItemWords<W> it;                               // (every lane takes every shuffle)
-            constexpr int NWD = sizeof(W) == 4 ? 2 : 3;
-#pragma unroll
-            for (int j = 0; j < NWD; ++j) {
-                const int src = 3 * ((q >> 5) - (NWD - 1) + j - (w0 - 2));   // 0 .. 3 * LONG_STAGE_WORDS - 3
-                it.hi[j] = (uint32_t) __shfl((int) staged, src, 64);
-                it.lo[j] = (uint32_t) __shfl((int) staged, src + 1, 64);
-                it.va[j] = (uint32_t) __shfl((int) staged, src + 2, 64);
-            }
+            ItemWords<W> it;
+            wave_block_words<W>(p, n_words, base, lane, q, it);   // (every lane)
             W wh, wl;
             const bool valid = it.window((uint32_t) q & 31u, k, kc.mask, wh, wl) && s < n_win;
             const bool want_f = valid && s >= next_free[0], want_r = valid && s >= next_free[1];
@@ -169,19 +150,7 @@ __global__ __launch_bounds__(LONG_WG) void hits_wave_kernel(ReadsView rv, Filter
             const bool full_r = want_r && ar && probe_bcd_chain<W>(bcd, kar, kbr);
             const uint64_t full[2] = {__ballot(full_f), __ballot(full_r)};
 #pragma unroll
-            for (int strand = 0; strand < 2; ++strand) {
-                // the greedy walk, by the whole wave (block-relative window starts)
-                uint64_t m = full[strand];
-                int from = max(next_free[strand] - base, 0);
-                while (from < 64 && count[strand] < max_hits) {
-                    m &= ~0ull << from;
-                    if (!m) break;
-                    const int b = __ffsll((unsigned long long) m) - 1;
-                    ++count[strand];
-                    next_free[strand] = base + b + k;
-                    from = b + k;
-                }
-            }
+            for (int strand = 0; strand < 2; ++strand) greedy_take(full[strand], base, k, max_hits, next_free[strand], count[strand]);   // (by the whole wave)
         }
         const int h = min(max_hits, max(count[0], count[1]));
         if (lane == 0 && h > before) hits[r] = (uint8_t) h;

@@ -1,5 +1,8 @@
 // hit_profile_group.hpp — hits_group_kernel and hits_group_wave_kernel: the hits passes of hit_profile.hpp over a GROUP of up to eight
-// chunk filters, one walk of the read and one plane-A request per window for all of them (commet_index_and_profile, capi/profile.hpp).
+// chunk filters, one walk of the read and one plane-A request per window for all of them (commet_index_and_profile, capi/profile.hpp)
+// — and the two bodies that these kernels share with the passes over the filters of SEVERAL jobs (hit_profile_jobs.hpp: JOBS = true):
+// hits_lanes below, a lane per read, and hit_profile_wave_body.hpp, a wave per read.  The four kernels only name their body: a
+// carry or block-bound fix is made once.
 //
 // Why grouping is exact.  Per chunk filter c and strand, the accepted hits are one greedy sequence that depends on that filter
 // alone (hit_profile.hpp), and hits = min(T, max over c of max(F_c, R_c)): a max fold is order-free.  Holding the (free, cnt) state
@@ -16,52 +19,96 @@
 // plane A): the host takes such a job one filter per pass.
 //
 // The per-filter state lives in registers: every loop over NF unrolls fully, no array is indexed by a run-time value, the counts
-// (<= max_hits <= 255) are bytes of one word per strand.  The lane kernel walks its lane-a candidates bit by bit and addresses each
-// one's slot per lane; the wave kernel keeps its uniform state in the lanes of two registers and loops over the g filters.  Either
-// way no table of per-slot plane pointers is held in scalar registers, and none of the twelve instantiations spills.
+// (<= max_hits <= 255) are bytes of one word per strand.  The lane body walks its lane-a candidates bit by bit and addresses each
+// one's slot per lane; the wave body keeps its uniform state in the lanes of two registers and loops over the g filters.  Either
+// way no table of per-slot plane pointers is held in scalar registers, and none of the twenty-four instantiations spills.
 //
-// Included by capi.hip behind hit_profile.hpp (long_load_a, planes_bcd, FilterGroupView as well); not meant to stand alone.
+// Included by capi.hip behind hit_profile.hpp (long_load_a, wave_block_words, greedy_take, planes_bcd, FilterGroupView, search_lane,
+// count_walked as well); not meant to stand alone.
 #pragma once
 
 namespace commet {
 
-// ---------------------------------------------------------------------------
-// a lane per read: the walk of hits_kernel, NF filters' states side by side
-// ---------------------------------------------------------------------------
-template <typename W, int NF>
-__global__ __launch_bounds__(256) COMMET_SGPRS void hits_group_kernel(ReadsView rv, FilterGroupView fg, int k, int max_hits,
-                                                                      const uint64_t *__restrict__ sel, uint8_t *__restrict__ hits,
-                                                                      unsigned long long *__restrict__ walked, ActiveList al)
+// (JOBS) which job owns a slot of the pass, and its cap, as packed scalars, no pointer tables.  Consecutive slots belong to one job:
+//   mates  byte i = the mask of the slots of slot i's job (slot i among them); 0 for a slot behind the pass's filters
+//   caps   byte i = max_hits of slot i's job
+// Slot i is the first of its job when it is the lowest bit of its own mask; the job's number in the pass is the count of first slots
+// below i
+struct JobSlots {
+    uint64_t mates;
+    uint64_t caps;
+};
+
+// The layout words live in vector registers: they are uniform, but the lane kernel is at its scalar budget (COMMET_SGPRS) without
+// them, and their bytes are picked by a per-lane slot number anyway.  Passes of up to four slots hold the low halves only
+template <int NF>
+__device__ __forceinline__ uint64_t layout_in_vgprs(uint64_t packed)
 {
-    static_assert(NF == 2 || NF == 4 || NF == 8, "groups of 2, 4 or 8 filter slots");
+    uint32_t lo, hi = 0;
+    asm("v_mov_b32 %0, %1" : "=v"(lo) : "s"((uint32_t) packed));
+    if (NF > 4) asm("v_mov_b32 %0, %1" : "=v"(hi) : "s"((uint32_t) (packed >> 32)));
+    return ((uint64_t) hi << 32) | lo;
+}
+
+// byte i of a layout word
+template <int NF>
+__device__ __forceinline__ uint32_t slot_byte(uint64_t packed, int i)
+{
+    if (NF <= 4) return ((uint32_t) packed >> (8 * i)) & 255u;
+    return (uint32_t) (packed >> (8 * i)) & 255u;
+}
+
+// ---------------------------------------------------------------------------
+// a lane per read: the walk of hits_kernel, NF filters' states side by side.  JOBS = false: the filters of one job fold into the
+// read's byte of `hits` (max_hits, al; js and lines are not looked at).  JOBS = true: the slots belong to the jobs of js, a byte
+// array of `lines` lines of 256 bytes per job (js, lines; max_hits and al are not looked at).
+// ---------------------------------------------------------------------------
+template <typename W, int NF, bool JOBS>
+__device__ __forceinline__ void hits_lanes(const ReadsView &rv, const FilterGroupView &fg, int k, int max_hits, JobSlots js,
+                                           const uint64_t *__restrict__ sel, uint8_t *__restrict__ hits, uint32_t lines,
+                                           unsigned long long *__restrict__ walked, ActiveList al)
+{
+    static_assert(NF == 2 || NF == 4 || NF == 8, "passes of 2, 4 or 8 filter slots");
     const SearchLane me = search_lane(rv, al, sel, nullptr);
     const uint64_t r = me.r;
     int before = 0;
-    bool walk = false;
-    if (me.active) {
-        before = (int) hits[r];
-        walk = before < max_hits;
+    bool walk = me.active;
+    if constexpr (!JOBS) {
+        if (walk) {
+            before = (int) hits[r];
+            walk = before < max_hits;
+        }
     }
+    // (JOBS) no `before` skip: the host zeroes the byte arrays per call and never splits a job across passes, so a job's bytes are
+    // written by exactly one pass, and by the one lane that owns the read.  `walked` then counts the active lanes
     if (walk) {
         uint64_t t0;
         uint32_t len;
         read_extent(rv, r, t0, len);
         const uint32_t *p = rv.planes + 3 * t0;
         const KeyCtx<W> kc(k);
+        uint64_t slot_mates = 0, slot_caps = 0;
+        if constexpr (JOBS) slot_mates = layout_in_vgprs<NF>(js.mates), slot_caps = layout_in_vgprs<NF>(js.caps);
         W wh = 0, wl = 0;
         uint32_t run = 0;
-        // [filter]: first window start the strand's state takes again (never, for the slots behind the group's filters); the hits of
-        // filter i on a strand are byte i of cnt_f / cnt_r
+        // [slot]: first window start the strand's state takes again (never, for the slots behind the pass's filters and (JOBS) for the
+        // slots of a job that has reached its cap); the hits of slot i on a strand are byte i of cnt_f / cnt_r
         int free_f[NF], free_r[NF];
         uint64_t cnt_f = 0, cnt_r = 0;
 #pragma unroll
         for (int i = 0; i < NF; ++i) free_f[i] = free_r[i] = i < fg.g ? 0 : INT_MAX;
         int min_free = 0;                           // the lowest of the 2 NF: a window in front of it is wanted by nobody
-        int best = 0;                               // the highest of the 2 NF counts
-        for (uint32_t w = 0; w * 32u < len && best < max_hits; ++w) {
+        int best = 0;                               // (one job) the highest of the 2 NF counts
+        // One job: the walk ends as soon as any count is max_hits, the byte is then max_hits.  Several: it ends only when no state
+        // wants a window (or the read ends) — a job that reaches its cap does not end the walk for the others
+        const auto more = [&] {
+            if constexpr (JOBS) return min_free != INT_MAX;
+            else return best < max_hits;
+        };
+        for (uint32_t w = 0; w * 32u < len && more(); ++w) {
             const uint32_t hi = p[3 * w], lo = p[3 * w + 1], va = p[3 * w + 2];
             const uint32_t nb = min(32u, len - w * 32u);
-            for (uint32_t j = 0; j < nb && best < max_hits; ++j) {
+            for (uint32_t j = 0; j < nb && more(); ++j) {
                 wh = (wh >> 1) | ((W) ((hi >> j) & 1u) << (k - 1));
                 wl = (wl >> 1) | ((W) ((lo >> j) & 1u) << (k - 1));
                 run = ((va >> j) & 1u) ? run + 1 : 0;
@@ -76,7 +123,7 @@ __global__ __launch_bounds__(256) COMMET_SGPRS void hits_group_kernel(ReadsView 
                 uint32_t xa[NF];
                 long_load_a<NF>(fg.il_a + (uint64_t) (addr >> 5) * NF, xa);
                 const uint32_t bit_f = (uint32_t) addr & 31u, bit_r = selfp ? bit_f : bit_f ^ 1u;
-                // the lane-a candidates among the states that want the window: bit i = filter i forward, bit NF + i = its reverse complement
+                // the lane-a candidates among the states that want the window: bit i = slot i forward, bit NF + i = its reverse complement
                 uint32_t cand = 0;
 #pragma unroll
                 for (int i = 0; i < NF; ++i) {
@@ -94,11 +141,22 @@ __global__ __launch_bounds__(256) COMMET_SGPRS void hits_group_kernel(ReadsView 
                     hit = true;
                     uint64_t &cnt = rev ? cnt_r : cnt_f;
                     cnt += 1ull << (8 * i);
-                    best = max(best, (int) ((cnt >> (8 * i)) & 255ull));
+                    const uint32_t mine = (uint32_t) (cnt >> (8 * i)) & 255u;
+                    uint32_t stop = 0;
+                    if constexpr (JOBS) {
+                        // The stop is per job.  When a slot's count on a strand reaches its job's cap, the job's byte is decided: none
+                        // of its states, both strands of all mates, wants a window any more (free = INT_MAX), the candidates of its
+                        // mates in this window included.  Counts never pass the cap (<= 255): bytes of one word per strand
+                        if (mine >= slot_byte<NF>(slot_caps, i)) stop = slot_byte<NF>(slot_mates, i);
+                        cand &= ~(stop | (stop << NF));
+                    } else {
+                        best = max(best, (int) mine);
+                    }
 #pragma unroll
                     for (int q = 0; q < NF; ++q) {
                         if (q == i && !rev) free_f[q] = start + k;
                         if (q == i && rev) free_r[q] = start + k;
+                        if (JOBS && ((stop >> q) & 1u)) free_f[q] = free_r[q] = INT_MAX;
                     }
                 }
                 if (hit) {
@@ -108,133 +166,50 @@ __global__ __launch_bounds__(256) COMMET_SGPRS void hits_group_kernel(ReadsView 
                 }
             }
         }
-        const int h = min(max_hits, best);
-        if (h > before) hits[r] = (uint8_t) h;
+        if constexpr (JOBS) {
+            // per job, at its first slot: the fold over its slots, byte = min(cap, max over ITS slots of max(F, R)), a plain store to
+            // hits + job_in_pass * 256 * lines + r; a zero is not stored
+            int job = 0;
+#pragma unroll
+            for (int i = 0; i < NF; ++i) {
+                const uint32_t mates = slot_byte<NF>(slot_mates, i);
+                if ((mates & (0u - mates)) != (1u << i)) continue;      // (not the first slot of a job, or no job's)
+                uint32_t most = 0;
+#pragma unroll
+                for (int q = 0; q < NF; ++q)
+                    if ((mates >> q) & 1u) most = max(most, max((uint32_t) (cnt_f >> (8 * q)) & 255u, (uint32_t) (cnt_r >> (8 * q)) & 255u));
+                const uint32_t h = min(most, slot_byte<NF>(slot_caps, i));
+                if (h) hits[(uint64_t) job * lines * 256ull + r] = (uint8_t) h;
+                ++job;
+            }
+        } else {
+            const int h = min(max_hits, best);
+            if (h > before) hits[r] = (uint8_t) h;
+        }
     }
-    if (walked) {
-        __shared__ unsigned int wg_walked;
-        if (threadIdx.x == 0) wg_walked = 0;
-        __syncthreads();
-        add_walked(walked, walk, wg_walked);
-    }
+    count_walked(walked, walk);
+}
+
+template <typename W, int NF>
+__global__ __launch_bounds__(256) COMMET_SGPRS void hits_group_kernel(ReadsView rv, FilterGroupView fg, int k, int max_hits,
+                                                                      const uint64_t *__restrict__ sel, uint8_t *__restrict__ hits,
+                                                                      unsigned long long *__restrict__ walked, ActiveList al)
+{
+    hits_lanes<W, NF, false>(rv, fg, k, max_hits, JobSlots{0, 0}, sel, hits, 0, walked, al);
 }
 
 // ---------------------------------------------------------------------------
-// a wave per read: the blocks of hits_wave_kernel (64 consecutive windows per block, staged words, shuffles, persistent grid).  Per
-// block one interleaved plane-A load per lane serves every filter and both strands; per filter and strand one ballot of full hits,
-// walked greedily by the whole wave.  (next_free, count) per filter and strand are uniform over the wave and carried from block to
-// block: filter i's hit in the last windows of block b forbids filter i's first windows of block b + 1, and nobody else's.  Blocks
-// behind the one in which any count reaches max_hits are not loaded.
+// a wave per read: the body is hit_profile_wave_body.hpp, text included here and into hits_jobs_wave_kernel
 // ---------------------------------------------------------------------------
 template <typename W, int NF>
 __global__ __launch_bounds__(LONG_WG) void hits_group_wave_kernel(ReadsView rv, FilterGroupView fg, int k, int max_hits,
                                                                   const uint64_t *__restrict__ sel, uint8_t *__restrict__ hits,
                                                                   unsigned long long *__restrict__ walked, ActiveList al)
 {
-    static_assert(NF == 2 || NF == 4 || NF == 8, "groups of 2, 4 or 8 filter slots");
-    const int lane = threadIdx.x & 63;
-    const uint64_t wave0 = (uint64_t) blockIdx.x * (LONG_WG / 64) + (threadIdx.x >> 6);
-    const uint64_t n_waves = (uint64_t) gridDim.x * (LONG_WG / 64);
-    const uint64_t n_items = al.ids ? (uint64_t) *al.n : rv.n;
-    const KeyCtx<W> kc(k);
-    const int g = fg.g;
-    unsigned long long n_walked = 0;
-
-    for (uint64_t item = wave0; item < n_items; item += n_waves) {   // (uniform per wave)
-        uint64_t r = item;
-        if (al.ids) r = (uint64_t) al.ids[item];
-        else if (sel && !((sel[r >> 6] >> (r & 63ull)) & 1ull)) continue;
-        const int before = (int) hits[r];
-        if (before >= max_hits) continue;
-        ++n_walked;
-        uint64_t t0;
-        uint32_t len;
-        read_extent(rv, r, t0, len);
-        const uint32_t *p = rv.planes + 3 * t0;
-        const int n_words = (int) ((len + 31u) >> 5);
-        const int n_win = (int) len - k + 1;               // windows of the read, by their start (<= 0: none)
-        // (next_free, count) of filter i: lane i of the two state registers holds the forward strand's, lane NF + i the reverse
-        // complement's.  Uniform values, read with readlane by the whole wave and written by their lane: the filters of the group
-        // are then a loop over i < g, with no table of 2 NF states and 3 NF plane pointers to keep in scalar registers
-        int st_next = 0, st_count = 0;
-        int min_next = 0;                                  // the lowest next_free of the 2 g: a window in front of it is wanted by nobody
-        int best = 0;                                      // the highest of the 2 g counts
-        for (int base = 0; base < n_win && best < max_hits; base += 64) {
-            // the read's words this block's windows stand on: words w0 - 2 .. w0 + 4, one per lane (zeros outside the read)
-            const int w0 = base >> 5;
-            uint32_t staged = 0;
-            {
-                const int wi = w0 - 2 + lane / 3;
-                if (lane < 3 * LONG_STAGE_WORDS && wi >= 0 && wi < n_words) staged = p[3 * wi + lane % 3];
-            }
-            const int s = base + lane, q = s + k - 1;
-            ItemWords<W> it;                               // (every lane takes every shuffle)
-            constexpr int NWD = sizeof(W) == 4 ? 2 : 3;
-#pragma unroll
-            for (int j = 0; j < NWD; ++j) {
-                const int src = 3 * ((q >> 5) - (NWD - 1) + j - (w0 - 2));   // 0 .. 3 * LONG_STAGE_WORDS - 3
-                it.hi[j] = (uint32_t) __shfl((int) staged, src, 64);
-                it.lo[j] = (uint32_t) __shfl((int) staged, src + 1, 64);
-                it.va[j] = (uint32_t) __shfl((int) staged, src + 2, 64);
-            }
-            W wh, wl;
-            const bool valid = it.window((uint32_t) q & 31u, k, kc.mask, wh, wl) && s < n_win;
-            const bool wanted = valid && s >= min_next;    // by at least one of the 2 g states
-            W kaf, kbf, kar, kbr;
-            kc.strand_keys(wh, wl, 0, kaf, kbf);
-            kc.strand_keys(wh, wl, 1, kar, kbr);
-            uint32_t xa[NF];
-            uint32_t bit_f = 0, bit_r = 0;
-            if (wanted) {
-                bool selfp;
-                const W addr = psi_a<W>(kaf, k, selfp);
-                long_load_a<NF>(fg.il_a + (uint64_t) (addr >> 5) * NF, xa);
-                bit_f = (uint32_t) addr & 31u, bit_r = selfp ? bit_f : bit_f ^ 1u;
-            } else {
-#pragma unroll
-                for (int i = 0; i < NF; ++i) xa[i] = 0;
-            }
-            bool any_hit = false;
-#pragma unroll 1
-            for (int i = 0; i < g; ++i) {                  // (uniform)
-                uint32_t x = xa[0];                        // filter i's word of the load
-#pragma unroll
-                for (int j = 1; j < NF; ++j) x = (i == j) ? xa[j] : x;
-                const PlanesBCD bcd = planes_bcd(fg, i);
-#pragma unroll
-                for (int strand = 0; strand < 2; ++strand) {
-                    const int slot = i + strand * NF;
-                    int next_free = __builtin_amdgcn_readlane(st_next, slot), count = __builtin_amdgcn_readlane(st_count, slot);
-                    const bool full = wanted && s >= next_free && ((x >> (strand ? bit_r : bit_f)) & 1u) &&
-                                      probe_bcd_chain<W>(bcd, strand ? kar : kaf, strand ? kbr : kbf);
-                    // the greedy walk, by the whole wave (block-relative window starts)
-                    uint64_t m = __ballot(full);
-                    if (!m) continue;
-                    int from = max(next_free - base, 0);
-                    while (from < 64 && count < max_hits) {
-                        m &= ~0ull << from;
-                        if (!m) break;
-                        const int b = __ffsll((unsigned long long) m) - 1;
-                        ++count;
-                        next_free = base + b + k;
-                        from = b + k;
-                    }
-                    if (lane == slot) st_next = next_free, st_count = count;
-                    best = max(best, count);
-                    any_hit = true;
-                }
-            }
-            if (any_hit) {
-                min_next = INT_MAX;
-#pragma unroll 1
-                for (int i = 0; i < g; ++i)
-                    min_next = min(min_next, min(__builtin_amdgcn_readlane(st_next, i), __builtin_amdgcn_readlane(st_next, i + NF)));
-            }
-        }
-        const int h = min(max_hits, best);
-        if (lane == 0 && h > before) hits[r] = (uint8_t) h;
-    }
-    if (walked && lane == 0 && n_walked) atomicAdd(walked, n_walked);
+    constexpr bool JOBS = false;
+    constexpr JobSlots js{0, 0};
+    constexpr uint32_t lines = 0;
+#include "hit_profile_wave_body.hpp"
 }
 
 }  // namespace commet

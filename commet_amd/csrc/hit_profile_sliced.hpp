@@ -191,12 +191,7 @@ __global__ __launch_bounds__(256) void hits_sliced_kernel(ReadsView rv, const ui
         }
         if (best > before) hits[r] = (uint8_t) best;
     }
-    if (walked) {
-        __shared__ unsigned int wg_walked;
-        if (threadIdx.x == 0) wg_walked = 0;
-        __syncthreads();
-        add_walked(walked, walk, wg_walked);
-    }
+    count_walked(walked, walk);
 }
 
 }  // namespace commet

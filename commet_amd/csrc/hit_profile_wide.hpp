@@ -202,12 +202,7 @@ __global__ __launch_bounds__(256) void hits_wide_kernel(ReadsView rv, const uint
     }
     const bool mine = walk && sl == 0;
     if (mine && best > (int) hits[r]) hits[r] = (uint8_t) best;
-    if (walked) {
-        __shared__ unsigned int wg_walked;
-        if (threadIdx.x == 0) wg_walked = 0;
-        __syncthreads();
-        add_walked(walked, mine, wg_walked);
-    }
+    count_walked(walked, mine);
 }
 
 }  // namespace commet

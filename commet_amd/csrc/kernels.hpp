@@ -125,6 +125,18 @@ __device__ __forceinline__ void add_walked(unsigned long long *__restrict__ walk
     if (threadIdx.x == 0 && wg_walked) atomicAdd(walked, (unsigned long long) wg_walked);
 }
 
+// the same as the last statement of a lane-per-read kernel that has no barrier of its own: the LDS word and its zeroing with it.
+// walked is optional (uniform); every thread of the workgroup calls it
+__device__ __forceinline__ void count_walked(unsigned long long *__restrict__ walked, bool mine)
+{
+    if (walked) {
+        __shared__ unsigned int wg_walked;
+        if (threadIdx.x == 0) wg_walked = 0;
+        __syncthreads();
+        add_walked(walked, mine, wg_walked);
+    }
+}
+
 // ---------------------------------------------------------------------------
 // Which read a search thread works on.  Usually thread i of the launch takes read i and the bitmaps decide (sel: reads to
 // search, tags: reads found by an earlier chunk).  A pass over FEW of a set's reads — Commet.py's third job searches a set

@@ -48,6 +48,45 @@ template <int NF> __device__ __forceinline__ void long_load_a(const uint32_t *__
     }
 }
 
+// The loader of a block (the 64 consecutive windows from window start `base`, one per lane): the read's words the block's windows
+// stand on, words w0 - 2 .. w0 + 4, are staged one per lane (zeros outside the read, which is what ItemWords::load puts in front of
+// it) and shuffled into `it` for the window that ends at base q = base + lane + k - 1, NWD words per plane.  EVERY lane of the wave
+// must call it, whatever its window: a lane that sat out would hand out nothing
+template <typename W>
+__device__ __forceinline__ void wave_block_words(const uint32_t *__restrict__ p, int n_words, int base, int lane, int q, ItemWords<W> &it)
+{
+    const int w0 = base >> 5;
+    uint32_t staged = 0;
+    {
+        const int wi = w0 - 2 + lane / 3;
+        if (lane < 3 * LONG_STAGE_WORDS && wi >= 0 && wi < n_words) staged = p[3 * wi + lane % 3];
+    }
+    constexpr int NWD = sizeof(W) == 4 ? 2 : 3;
+#pragma unroll
+    for (int j = 0; j < NWD; ++j) {
+        const int src = 3 * ((q >> 5) - (NWD - 1) + j - (w0 - 2));   // 0 .. 3 * LONG_STAGE_WORDS - 3
+        it.hi[j] = (uint32_t) __shfl((int) staged, src, 64);
+        it.lo[j] = (uint32_t) __shfl((int) staged, src + 1, 64);
+        it.va[j] = (uint32_t) __shfl((int) staged, src + 2, 64);
+    }
+}
+
+// The greedy walk of a block's ballot of full hits by the whole wave, for the kernels that count hits up to a cap (hit_profile*.hpp;
+// the walk of search_long_kernel also records what it passes, ends scans and prunes: a loop of its own).  m: bit b = the window that
+// starts at base + b is a full hit; lowest set bit at or after next_free, count it, next_free = its start + k, again
+__device__ __forceinline__ void greedy_take(uint64_t m, int base, int k, int cap, int &next_free, int &count)
+{
+    int from = max(next_free - base, 0);                   // (block-relative)
+    while (from < 64 && count < cap) {
+        m &= ~0ull << from;
+        if (!m) break;
+        const int b = __ffsll((unsigned long long) m) - 1;
+        ++count;
+        next_free = base + b + k;
+        from = b + k;
+    }
+}
+
 // (several jobs in a pass) the filters of filter i's job behind it, and in front of it.  opens: bit j = filter j opens a job (bit 0
 // is set); all: the filters of the pass.  Uniform over the wave
 __device__ __forceinline__ uint32_t job_behind(uint32_t opens, uint32_t all, int i)

@@ -45,25 +45,10 @@
                 if ((int64_t) len < (int64_t) t * k) open = 0;   // no room for t windows
             }
             for (int base = 0; base < n_win && open; base += 64) {
-                // the read's words this block's windows stand on, one per lane, handed out by shuffles
-                const int w0 = base >> 5;
-                uint32_t staged = 0;
-                {
-                    const int wi = w0 - 2 + lane / 3;
-                    if (lane < 3 * LONG_STAGE_WORDS && wi >= 0 && wi < n_words) staged = p[3 * wi + lane % 3];
-                }
+                // the read's words this block's windows stand on, one per lane, handed out by shuffles (every lane)
                 const int s = base + lane, q = s + k - 1;
-                // (every lane takes every shuffle: a lane that sat out would hand out nothing.  Words in front of the read are staged
-                // as zeros, which is what ItemWords::load puts there)
                 ItemWords<W> it;
-                constexpr int NWD = sizeof(W) == 4 ? 2 : 3;
-#pragma unroll
-                for (int j = 0; j < NWD; ++j) {
-                    const int src = 3 * ((q >> 5) - (NWD - 1) + j - (w0 - 2));   // 0 .. 3 * LONG_STAGE_WORDS - 3
-                    it.hi[j] = (uint32_t) __shfl((int) staged, src, 64);
-                    it.lo[j] = (uint32_t) __shfl((int) staged, src + 1, 64);
-                    it.va[j] = (uint32_t) __shfl((int) staged, src + 2, 64);
-                }
+                wave_block_words<W>(p, n_words, base, lane, q, it);
                 W ka, kb;
                 const bool valid = kc.window_keys(it, q, strand, ka, kb) && s < n_win;
                 // which filters this lane asks: open ones whose last hit the window does not overlap

@@ -178,8 +178,9 @@ def wave_sets(k):
             read = rand(rng, n_win + k - 1)
             exp_r.append(plant(read, p))
             ragged.append(read)
+    n_win = max(257, 192 + 2 * k)                               # (every plant fits: the last one starts at 191 + 2 k; 257 up to k = 32)
     for p in wave_plants(k):
-        read = rand(rng, 257 + k - 1)
+        read = rand(rng, n_win + k - 1)
         exp_f.append(plant(read, p))
         fixed.append(read)
     # N runs that split a block: every clean window of the read is a k-mer of the index set, on one strand or the other (these index

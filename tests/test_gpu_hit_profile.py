@@ -294,7 +294,7 @@ def _wave_sets(rng, k):
     return index, ragged, exp_r, fixed, exp_f
 
 
-@pytest.mark.parametrize("k", [31, 32])
+@pytest.mark.parametrize("k", [31, 32, 33])                   # (33: the loader's three-word path, 64-bit keys)
 def test_wave_kernel_at_block_edges(tmp_path, k):
     import commet_amd as commet
     rng = np.random.default_rng(k)

@@ -113,7 +113,7 @@ def test_state_is_per_filter(tmp_path, long_search, case):
 
 
 # ---- 3. the wave form at block edges -----------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("k", [31, 32])
+@pytest.mark.parametrize("k", [31, 32, 33])                   # (33: the loader's three-word path, 64-bit keys)
 def test_wave_form_at_block_edges(tmp_path, k):
     index, ragged, exp_r, fixed, exp_f, max_kmer = gs.wave_sets(k)
     got = {}

@@ -80,7 +80,7 @@ def test_planted_reads_reach_their_counts(tmp_path, case):
             assert tags[0].tolist() == [False]
 
 
-@pytest.mark.parametrize("k", [31, 32])
+@pytest.mark.parametrize("k", [31, 32, 33])
 def test_wave_sets_reach_their_counts(tmp_path, k):
     index, ragged, exp_r, fixed, exp_f, max_kmer = gs.wave_sets(k)
     assert len(set(len(r) for r in ragged)) > 5 and len(set(len(r) for r in fixed)) == 1
