@@ -7,17 +7,17 @@
 // F_c / R_c = the reference's greedy non-overlapping full four-lane hits of the forward / reverse-complement strand in chunk c
 // (search_reads.h:45-83 run to the end of the read): the quantity hits_kernel computes, one filter at a time.
 //
-//   (1) row pass over EVERY complete window (a profile has no t: no `pe`, no `lim`), both strands: the entries of planes A, B, C and D
-//       ANDed with search_sliced_kernel's short circuit, so a set bit is a FULL hit of that window in that chunk.  Window end positions
-//       are cut into blocks of k; per chunk bit and strand a 2-bit saturating counter of the blocks that hold a hit (wide_fold on every
-//       word of a SliceWord): 4 * GW registers, and 2 * GW for the open block.
+//   (1) row pass over EVERY complete window (a profile has no t: no `pe`, no `lim`), both strands: search_sliced_kernel's entry test
+//       (slice_window_masks), so a set bit is a FULL hit of that window in that chunk.  Window end positions are cut into blocks of k
+//       (roll_blocks); per chunk bit and strand a 2-bit saturating counter of the blocks that hold a hit (wide_fold on every word of a
+//       SliceWord): 4 * GW registers, and 2 * GW for the open block.
 //   (2) the counters bound the greedy count from BOTH sides.  Hits inside one block end fewer than k positions apart, so they overlap
 //       pairwise; hits in blocks i and i + 2 end more than k apart, so they do not; and the greedy scan takes the largest set of
 //       non-overlapping hits.  Hence
 //           counter 1: exactly 1        counter 2: 1 or 2        counter 3 (saturated: three blocks or more): at least 2.
 //       best starts at max(the byte in hits[r], min(cap, the largest lower bound)).  A counter of 1 never needs a replay, a counter of
 //       2 only while best < 2, a saturated one while best < cap.  The replay of one chunk and strand is search_sliced_kernel's
-//       single-bit walk without a stop at t: it counts to the end of the strand, or to where its bound or cap stops it.  Saturated
+//       single-bit walk (slice_strand_count) without pruning: it counts to the end of the strand, or to where its bound or cap stops it.  Saturated
 //       counters first (the higher bound), then the counters of 2; max is order-free, so the order decides speed only.
 //
 // Columns at or past g are masked out of the counters: they are never read as chunks.  A read that is not selected, has fewer than k
@@ -28,17 +28,6 @@
 #include "slice_search.hpp"
 
 namespace commet {
-
-// word cw of a (a select per word keeps the words in registers)
-template <int GW>
-__device__ __forceinline__ uint32_t slice_pick(const SliceWord<GW> &a, int cw)
-{
-    uint32_t m = 0;
-#pragma unroll
-    for (int i = 0; i < GW; ++i)
-        if (i == cw) m = a.x[i];
-    return m;
-}
 
 template <int GW>
 __device__ __forceinline__ void slice_fold(SliceWord<GW> &cur, SliceWord<GW> &c0, SliceWord<GW> &c1)
@@ -55,7 +44,7 @@ __global__ __launch_bounds__(256) void hits_sliced_kernel(ReadsView rv, const ui
     const uint64_t r = (uint64_t) blockIdx.x * 256ull + threadIdx.x;
     bool active = r < rv.n;
     if (active && sel) active = (sel[r >> 6] >> (r & 63)) & 1ull;
-    const uint32_t *TA = tables, *TB = tables + ((1ull << k) * GW), *TC = tables + ((2ull << k) * GW), *TD = tables + ((3ull << k) * GW);
+    const SlicePlanes T(tables, k, GW);
     uint64_t t0 = 0;
     uint32_t len = 0;
     int before = 0;
@@ -67,8 +56,6 @@ __global__ __launch_bounds__(256) void hits_sliced_kernel(ReadsView rv, const ui
     const bool walk = active && before < cap;             // (a read of fewer than k bases has cap 0)
     if (walk) {
         const uint32_t *p = rv.planes + 3 * t0;
-        const int sh = 32 - k;
-        const uint32_t mask = (1u << k) - 1u;
         const int last = (int) len - 1;
         SliceWord<GW> f0, f1, r0, r1;                     // blocks with a hit per chunk bit: 2-bit counters (f1 f0), (r1 r0)
         f0.clear(), f1.clear(), r0.clear(), r1.clear();
@@ -76,66 +63,21 @@ __global__ __launch_bounds__(256) void hits_sliced_kernel(ReadsView rv, const ui
         {
             SliceWord<GW> cur_f, cur_r;
             cur_f.clear(), cur_r.clear();
-            uint32_t wh = 0, wl = 0, run = 0;
-            int in_block = 0;                              // window positions since the block began
-            for (uint32_t w = 0; (int) (w * 32u) <= last; ++w) {
-                const uint32_t hi = p[3 * w], lo = p[3 * w + 1], va = p[3 * w + 2];
-                const uint32_t nb = (uint32_t) min(32, last - (int) (w * 32u) + 1);
-                for (uint32_t j = 0; j < nb; ++j) {
-                    wh = (wh >> 1) | (((hi >> j) & 1u) << (k - 1));
-                    wl = (wl >> 1) | (((lo >> j) & 1u) << (k - 1));
-                    run = ((va >> j) & 1u) ? run + 1 : 0;
-                    if ((int) (32u * w + j) < k - 1) continue;              // not a window position yet
-                    if (run >= (uint32_t) k) {
-                        const uint32_t ka = __brev(wh) >> sh, kb = __brev(wl) >> sh;
-                        bool selfp;
-                        const uint32_t addr = psi_a<uint32_t>(ka, k, selfp);
-                        SliceWord<GW> mf, mr, x;
-                        if constexpr (GW <= 2) {
-                            // the pair (addr & ~1, addr | 1) is 2 * GW contiguous words: one load for both strands
-                            SliceWord<2 * GW> pr;
-                            pr.load(TA + (uint64_t) (addr & ~1u) * GW);
+            roll_blocks(
+                p, bases_to(last), k,
+                [&](uint32_t wh, uint32_t wl) {
+                    SliceWord<GW> mf, mr;
+                    const int reached = slice_window_masks<GW>(T, k, wh, wl, mf, mr);
+                    if (reached & 1) {
 #pragma unroll
-                            for (int i = 0; i < GW; ++i) {
-                                mf.x[i] = pr.x[(addr & 1u) * GW + i];
-                                mr.x[i] = selfp ? mf.x[i] : pr.x[((addr & 1u) ^ 1u) * GW + i];
-                            }
-                        } else {
-                            mf.load(TA + (uint64_t) addr * GW);
-                            if (selfp) mr = mf;
-                            else mr.load(TA + (uint64_t) (addr ^ 1u) * GW);
-                        }
-                        if (mf.any()) {
-                            x.load(TB + (uint64_t) kb * GW), mf.and_with(x);
-                            if (mf.any()) {
-                                x.load(TC + (uint64_t) (ka ^ kb) * GW), mf.and_with(x);
-                                if (mf.any()) {
-                                    x.load(TD + (uint64_t) (ka | kb) * GW), mf.and_with(x);
-#pragma unroll
-                                    for (int i = 0; i < GW; ++i) cur_f.x[i] |= mf.x[i];
-                                }
-                            }
-                        }
-                        if (mr.any()) {
-                            const uint32_t ra = ~wh & mask, rb = ~wl & mask;
-                            x.load(TB + (uint64_t) rb * GW), mr.and_with(x);
-                            if (mr.any()) {
-                                x.load(TC + (uint64_t) (ra ^ rb) * GW), mr.and_with(x);
-                                if (mr.any()) {
-                                    x.load(TD + (uint64_t) (ra | rb) * GW), mr.and_with(x);
-#pragma unroll
-                                    for (int i = 0; i < GW; ++i) cur_r.x[i] |= mr.x[i];
-                                }
-                            }
-                        }
+                        for (int i = 0; i < GW; ++i) cur_f.x[i] |= mf.x[i];
                     }
-                    if (++in_block == k) {                  // the block is complete
-                        in_block = 0;
-                        slice_fold(cur_f, f0, f1), slice_fold(cur_r, r0, r1);
+                    if (reached & 2) {
+#pragma unroll
+                        for (int i = 0; i < GW; ++i) cur_r.x[i] |= mr.x[i];
                     }
-                }
-            }
-            slice_fold(cur_f, f0, f1), slice_fold(cur_r, r0, r1);   // the last, partial block
+                },
+                [&]() { slice_fold(cur_f, f0, f1), slice_fold(cur_r, r0, r1); });
         }
         // columns at or past g are no chunks of this pass
         uint32_t any1 = 0, any3 = 0;
@@ -161,30 +103,9 @@ __global__ __launch_bounds__(256) void hits_sliced_kernel(ReadsView rv, const ui
                 while (m && best < stop) {
                     const int cb = __ffs((int) m) - 1;
                     m &= m - 1u;
-                    auto bit = [&](const uint32_t *T, uint32_t key) -> bool { return (T[(uint64_t) key * GW + cw] >> cb) & 1u; };
                     for (int strand = 0; strand < 2 && best < stop; ++strand) {
                         if (!(((strand ? mrw : mfw) >> cb) & 1u)) continue;
-                        uint32_t wh = 0, wl = 0, run = 0;
-                        int seen = 0;
-                        for (uint32_t w = 0; w * 32u < len && seen < stop; ++w) {
-                            const uint32_t hi = p[3 * w], lo = p[3 * w + 1], va = p[3 * w + 2];
-                            const uint32_t nb = min(32u, len - w * 32u);
-                            for (uint32_t j = 0; j < nb; ++j) {
-                                wh = (wh >> 1) | (((hi >> j) & 1u) << (k - 1));
-                                wl = (wl >> 1) | (((lo >> j) & 1u) << (k - 1));
-                                run = ((va >> j) & 1u) ? run + 1 : 0;
-                                if (run < (uint32_t) k) continue;
-                                uint32_t ka, kb;
-                                if (strand == 0) ka = __brev(wh) >> sh, kb = __brev(wl) >> sh;
-                                else ka = ~wh & mask, kb = ~wl & mask;
-                                if (bit(TA, psi_a<uint32_t>(ka, k)) && bit(TB, kb) && bit(TC, ka ^ kb) && bit(TD, ka | kb)) {
-                                    ++seen;
-                                    run = 0;                   // hash.clear(), search_reads.h:60
-                                    if (seen >= stop) break;
-                                }
-                            }
-                        }
-                        best = max(best, seen);
+                        best = max(best, slice_strand_count<GW, false>(p, last, T, k, cw, cb, strand, stop));
                     }
                 }
             }

@@ -30,14 +30,6 @@
 
 namespace commet {
 
-__device__ __forceinline__ void wide_drop(uint4 &v, uint32_t j, uint32_t keep)
-{
-    if (j == 0) v.x &= keep;
-    else if (j == 1) v.y &= keep;
-    else if (j == 2) v.z &= keep;
-    else v.w &= keep;
-}
-
 template <int LPR, int NP>
 __global__ __launch_bounds__(256) void hits_wide_kernel(ReadsView rv, const uint32_t *__restrict__ tables, int k, int max_hits, int g, uint32_t nw,
                                                         uint32_t rw, const uint64_t *__restrict__ sel, uint8_t *__restrict__ hits,
@@ -50,8 +42,7 @@ __global__ __launch_bounds__(256) void hits_wide_kernel(ReadsView rv, const uint
     const uint64_t r = ((uint64_t) blockIdx.x * 4 + wave) * RPW + grp;
     bool active = r < rv.n;
     if (active && sel) active = (sel[r >> 6] >> (r & 63)) & 1ull;
-    const uint64_t plane_stride = ((uint64_t) rw) << k;   // words per table
-    const uint32_t *TA = tables, *TB = TA + plane_stride, *TC = TB + plane_stride, *TD = TC + plane_stride;
+    const SlicePlanes T(tables, k, rw);
     uint64_t t0 = 0;
     uint32_t len = 0;
     int before = 0;
@@ -64,7 +55,7 @@ __global__ __launch_bounds__(256) void hits_wide_kernel(ReadsView rv, const uint
     const uint32_t *p = rv.planes + 3 * t0;
     const int sh = 32 - k;
     const uint32_t mask = (1u << k) - 1u;
-    const int last = walk ? (int) len - 1 : -1;            // a group that does not walk has no window
+    const int last = walk ? (int) len - 1 : -1;           // a group that does not walk has no window
     uint4 f0[NP], f1[NP], r0[NP], r1[NP];                 // blocks with a hit per chunk bit: 2-bit counters (f1 f0), (r1 r0)
     bool have[NP];
 #pragma unroll
@@ -73,7 +64,9 @@ __global__ __launch_bounds__(256) void hits_wide_kernel(ReadsView rv, const uint
         have[i] = 4u * pc < nw && (int) (128u * pc) < g;  // the piece holds a chunk of this pass
         f0[i] = f1[i] = r0[i] = r1[i] = make_uint4(0, 0, 0, 0);
     }
-    // (1) row pass over all windows; every lane of the group rolls the same window
+    // (1) row pass over all windows; every lane of the group rolls the same window.  This is search_wide_kernel's wide_row_pass, and the
+    // window test of (2) its wide_window_hit, both written out: through the functions this kernel's registers moved (88 -> 78 VGPRs, a
+    // wave more) and its search time rose by about 1 % (MEASUREMENTS.md); as written here its code is what it was before they existed
     {
         uint4 cur_f[NP], cur_r[NP];
 #pragma unroll
@@ -93,9 +86,9 @@ __global__ __launch_bounds__(256) void hits_wide_kernel(ReadsView rv, const uint
                     const uint32_t ra = ~wh & mask, rb = ~wl & mask;
                     bool selfp;
                     const uint32_t addr = psi_a<uint32_t>(ka, k, selfp);
-                    const uint4 *af = (const uint4 *) (TA + (uint64_t) addr * rw), *ar = (const uint4 *) (TA + (uint64_t) (selfp ? addr : addr ^ 1u) * rw);
-                    const uint4 *bf = (const uint4 *) (TB + (uint64_t) kb * rw), *br = (const uint4 *) (TB + (uint64_t) rb * rw);
-                    const uint4 *cf = (const uint4 *) (TC + (uint64_t) (ka ^ kb) * rw), *cr = (const uint4 *) (TC + (uint64_t) (ra ^ rb) * rw);
+                    const uint4 *af = (const uint4 *) (T.a + (uint64_t) addr * rw), *ar = (const uint4 *) (T.a + (uint64_t) (selfp ? addr : addr ^ 1u) * rw);
+                    const uint4 *bf = (const uint4 *) (T.b + (uint64_t) kb * rw), *br = (const uint4 *) (T.b + (uint64_t) rb * rw);
+                    const uint4 *cf = (const uint4 *) (T.c + (uint64_t) (ka ^ kb) * rw), *cr = (const uint4 *) (T.c + (uint64_t) (ra ^ rb) * rw);
                     uint4 x[NP][6];
 #pragma unroll
                     for (int i = 0; i < NP; ++i) {
@@ -182,8 +175,8 @@ __global__ __launch_bounds__(256) void hits_wide_kernel(ReadsView rv, const uint
                         uint32_t ka, kb;
                         if (strand == 0) ka = __brev(wh) >> sh, kb = __brev(wl) >> sh;
                         else ka = ~wh & mask, kb = ~wl & mask;
-                        const uint32_t va = TA[(uint64_t) psi_a<uint32_t>(ka, k) * rw + cw], vb = TB[(uint64_t) kb * rw + cw];
-                        const uint32_t vc = TC[(uint64_t) (ka ^ kb) * rw + cw], vd = TD[(uint64_t) (ka | kb) * rw + cw];
+                        const uint32_t va = T.a[(uint64_t) psi_a<uint32_t>(ka, k) * rw + cw], vb = T.b[(uint64_t) kb * rw + cw];
+                        const uint32_t vc = T.c[(uint64_t) (ka ^ kb) * rw + cw], vd = T.d[(uint64_t) (ka | kb) * rw + cw];
                         hit = ((va & vb & vc & vd) >> cb) & 1u;
                     }
                 }

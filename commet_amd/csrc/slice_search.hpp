@@ -23,6 +23,16 @@
 //                           replayed one by one with the reference's exact control flow (search_reads.h:45-83) in
 //                           increasing chunk order; the first chunk that finds the read tags it, exactly as the
 //                           reference's chunk loop would.
+//
+// What these kernels, search_wide_kernel (below) and the two profile kernels on the same tables (hits_sliced_kernel,
+// hit_profile_sliced.hpp; hits_wide_kernel, hit_profile_wide.hpp) share stands here once, each piece described where it is defined:
+//   roll_windows, roll_blocks     the serial walk of a read's windows; the same with window positions counted in blocks of k
+//   SlicePlanes, strand_keys      where the four tables start; a window's keys on a strand
+//   slice_window_masks<GW>        narrow tables: the chunks in which a window is a full hit, per strand (paired plane-A load, short circuit)
+//   slice_strand_count<GW, PRUNE> narrow tables: the exact single-bit replay of one chunk and strand, counted up to a stop value
+//   slice_pick, wide_word, wide_drop   a word of a register-held mask by a run-time index
+// wide_row_pass, wide_window_hit and wide_ballot are search_wide_kernel's steps by name; hits_wide_kernel has the same pass and window
+// test written out (see there).
 #pragma once
 
 #include "kernels.hpp"
@@ -36,6 +46,63 @@ struct SliceChunk {
     uint64_t first;   // first read of the chunk's range
     uint64_t count;   // reads in the range (selected or not); 0 = empty chunk
 };
+
+// the bases of a walk that ends with the window at `end` (none if end < 0)
+__device__ __forceinline__ uint32_t bases_to(int end) { return (uint32_t) max(end + 1, 0); }
+
+// The serial roll of a read's windows, for the row passes of search_sliced_kernel, search_wide_kernel and hits_sliced_kernel: the first
+// n bases of the word triples at p, (wh, wl) the last k of them, and f(q, wh, wl, ok) for each base q, ok = the window that ends at q is
+// complete and all ACGT.  Loops of the same form stay written out where the helper cost time in the measurements on record
+// (MEASUREMENTS.md): slice_build_kernel's (8 and 14 %), hits_wide_kernel's row pass (about 1 %), and the replay's in slice_strand_count
+// (about 1 %, the size of the spread between rounds: kept written out on the side of the code that was there), which also ends early and
+// restarts the run of valid bases at a hit
+template <typename F>
+__device__ __forceinline__ void roll_windows(const uint32_t *__restrict__ p, uint32_t n, int k, F &&f)
+{
+    uint32_t wh = 0, wl = 0, run = 0;
+    for (uint32_t w = 0; w * 32u < n; ++w) {
+        const uint32_t hi = p[3 * w], lo = p[3 * w + 1], va = p[3 * w + 2];
+        const uint32_t nb = min(32u, n - w * 32u);
+        for (uint32_t j = 0; j < nb; ++j) {
+            wh = (wh >> 1) | (((hi >> j) & 1u) << (k - 1));
+            wl = (wl >> 1) | (((lo >> j) & 1u) << (k - 1));
+            run = ((va >> j) & 1u) ? run + 1 : 0;
+            f((int) (32u * w + j), wh, wl, run >= (uint32_t) k);
+        }
+    }
+}
+
+// The roll of the block-counting row passes (search_wide_kernel, hits_sliced_kernel): the window end positions
+// k - 1 .. n - 1 are cut into blocks of k; window(wh, wl) for every complete ACGT window, fold() behind every block, the last, partial
+// one included.  A position with an invalid window counts in its block; a position before k - 1 is not a window position yet
+template <typename WIN, typename FOLD>
+__device__ __forceinline__ void roll_blocks(const uint32_t *__restrict__ p, uint32_t n, int k, WIN &&window, FOLD &&fold)
+{
+    int in_block = 0;                                      // window positions since the block began
+    roll_windows(p, n, k, [&](int q, uint32_t wh, uint32_t wl, bool ok) {
+        if (q < k - 1) return;
+        if (ok) window(wh, wl);
+        if (++in_block == k) in_block = 0, fold();
+    });
+    fold();
+}
+
+// The four tables of a table set, plane p at tables + p * (row_words << k): rows of row_words words (GW in the narrow tables)
+struct SlicePlanes {
+    const uint32_t *a, *b, *c, *d;
+    __device__ __forceinline__ SlicePlanes(const uint32_t *tables, int k, uint32_t row_words)
+    {
+        const uint64_t plane_stride = ((uint64_t) row_words) << k;
+        a = tables, b = a + plane_stride, c = b + plane_stride, d = c + plane_stride;
+    }
+};
+
+// a window's keys of planes A (before psi_a) and B on a strand; C is ka ^ kb, D is ka | kb
+__device__ __forceinline__ void strand_keys(int strand, uint32_t wh, uint32_t wl, int k, uint32_t &ka, uint32_t &kb)
+{
+    if (strand == 0) ka = __brev(wh) >> (32 - k), kb = __brev(wl) >> (32 - k);
+    else ka = ~wh & ((1u << k) - 1u), kb = ~wl & ((1u << k) - 1u);
+}
 
 // stage[((c * 4 + plane) << (k - 5)) + word]: chunk c's plane as a plain bit array (plane A at psi_a addresses)
 __global__ __launch_bounds__(1024) void slice_build_kernel(ReadsView rv, const uint64_t *__restrict__ sel,
@@ -56,6 +123,7 @@ __global__ __launch_bounds__(1024) void slice_build_kernel(ReadsView rv, const u
         uint64_t t0;
         uint32_t len;
         read_extent(rv, r, t0, len);
+        // (roll_windows written out: through the helper this kernel measured 8 % and 14 % slower, MEASUREMENTS.md)
         const uint32_t *p = rv.planes + 3 * t0;
         uint32_t wh = 0, wl = 0, run = 0;
         for (uint32_t w = 0; w * 32u < len; ++w) {
@@ -153,6 +221,92 @@ template <int GW> struct SliceWord {
     }
 };
 
+// word cw of a (a select per word keeps the words in registers)
+template <int GW>
+__device__ __forceinline__ uint32_t slice_pick(const SliceWord<GW> &a, int cw)
+{
+    uint32_t m = 0;
+#pragma unroll
+    for (int i = 0; i < GW; ++i)
+        if (i == cw) m = a.x[i];
+    return m;
+}
+
+// The narrow entry test of a window (search_sliced_kernel, hits_sliced_kernel): mf / mr = the chunks of the table set in which the
+// window is a full four-lane hit on the forward / reverse-complement strand.  Plane A's entries of the two strands are neighbours
+// (psi_a; ONE entry if the window is its own reverse complement); planes B, C, D are fetched per strand while a chunk is left.
+// Returns bit 0 / bit 1 = the forward / reverse strand got as far as plane D (a mask of a strand that did not is zero)
+template <int GW>
+__device__ __forceinline__ int slice_window_masks(const SlicePlanes &T, int k, uint32_t wh, uint32_t wl, SliceWord<GW> &mf, SliceWord<GW> &mr)
+{
+    bool selfp;
+    const uint32_t addr = psi_a<uint32_t>(__brev(wh) >> (32 - k), k, selfp);
+    if constexpr (GW <= 2) {
+        // the pair (addr & ~1, addr | 1) is 2 * GW contiguous words: one load for both strands
+        SliceWord<2 * GW> pr;
+        pr.load(T.a + (uint64_t) (addr & ~1u) * GW);
+#pragma unroll
+        for (int i = 0; i < GW; ++i) {
+            mf.x[i] = pr.x[(addr & 1u) * GW + i];
+            mr.x[i] = selfp ? mf.x[i] : pr.x[((addr & 1u) ^ 1u) * GW + i];
+        }
+    } else {
+        mf.load(T.a + (uint64_t) addr * GW);
+        if (selfp) mr = mf;
+        else mr.load(T.a + (uint64_t) (addr ^ 1u) * GW);
+    }
+    auto bcd = [&](SliceWord<GW> &m, int strand) -> bool {   // -> plane D was reached: only then can m hold a chunk
+        SliceWord<GW> x;
+        if (!m.any()) return false;
+        uint32_t a, b;
+        strand_keys(strand, wh, wl, k, a, b);
+        x.load(T.b + (uint64_t) b * GW), m.and_with(x);
+        if (!m.any()) return false;
+        x.load(T.c + (uint64_t) (a ^ b) * GW), m.and_with(x);
+        if (!m.any()) return false;
+        x.load(T.d + (uint64_t) (a | b) * GW), m.and_with(x);
+        return true;
+    };
+    const bool df = bcd(mf, 0), dr = bcd(mr, 1);
+    return (df ? 1 : 0) | (dr ? 2 : 0);
+}
+
+// The narrow replay of one chunk (bit cb of word cw of every entry) on one strand, with the reference's exact control flow
+// (search_reads.h:45-83): the greedy count of non-overlapping full hits, up to `stop`.  PRUNE: the walk also ends where the hits
+// missing to `stop` no longer fit behind the window (exact, see search_kernel), so the count says only whether `stop` was reached
+template <int GW, bool PRUNE>
+__device__ __forceinline__ int slice_strand_count(const uint32_t *__restrict__ p, int last, const SlicePlanes &T, int k, int cw, int cb, int strand, int stop)
+{
+    auto bit = [&](const uint32_t *t, uint32_t key) -> bool { return (t[(uint64_t) key * GW + cw] >> cb) & 1u; };
+    const uint32_t len = (uint32_t) last + 1u;
+    int seen = 0;
+    bool dead = false;
+    // (roll_windows written out, see there)
+    uint32_t wh = 0, wl = 0, run = 0;
+    for (uint32_t w = 0; w * 32u < len && seen < stop && !dead; ++w) {
+        const uint32_t hi = p[3 * w], lo = p[3 * w + 1], va = p[3 * w + 2];
+        const uint32_t nb = min(32u, len - w * 32u);
+        for (uint32_t j = 0; j < nb; ++j) {
+            wh = (wh >> 1) | (((hi >> j) & 1u) << (k - 1));
+            wl = (wl >> 1) | (((lo >> j) & 1u) << (k - 1));
+            run = ((va >> j) & 1u) ? run + 1 : 0;
+            if (PRUNE && (int) (32u * w + j) + (stop - seen - 1) * k > last) {
+                dead = true;
+                break;
+            }
+            if (run < (uint32_t) k) continue;
+            uint32_t ka, kb;
+            strand_keys(strand, wh, wl, k, ka, kb);
+            if (bit(T.a, psi_a<uint32_t>(ka, k)) && bit(T.b, kb) && bit(T.c, ka ^ kb) && bit(T.d, ka | kb)) {
+                ++seen;
+                run = 0;                                   // hash.clear(), search_reads.h:60
+                if (seen >= stop) break;
+            }
+        }
+    }
+    return seen;
+}
+
 template <int GW>
 __global__ __launch_bounds__(256) COMMET_SGPRS void search_sliced_kernel(ReadsView rv, const uint32_t *__restrict__ tables, int k, int t, int g,
                                                             const uint64_t *__restrict__ sel, uint64_t *__restrict__ tags,
@@ -171,7 +325,7 @@ __global__ __launch_bounds__(256) COMMET_SGPRS void search_sliced_kernel(ReadsVi
         if (tags) tagw = tags[word];
     }
     const bool active = (r < rv.n) && ((selw >> lane) & 1ull) && !((tagw >> lane) & 1ull);
-    const uint32_t *TA = tables, *TB = tables + ((1ull << k) * GW), *TC = tables + ((2ull << k) * GW), *TD = tables + ((3ull << k) * GW);
+    const SlicePlanes T(tables, k, GW);
     bool found = false;
     int found_chunk = -1;
     if (active) {
@@ -179,117 +333,40 @@ __global__ __launch_bounds__(256) COMMET_SGPRS void search_sliced_kernel(ReadsVi
         uint32_t len;
         read_extent(rv, r, t0, len);
         const uint32_t *p = rv.planes + 3 * t0;
-        const int sh = 32 - k;
-        const uint32_t mask = (1u << k) - 1u;
         const int last = (int) len - 1;
         const int pe = last - (t - 1) * k;                     // last window that can be a strand's FIRST hit
         const int lim = t >= 2 ? last - (t - 2) * k : last;    // last window that can be its second hit
         SliceWord<GW> once_f, once_r, cand;
         once_f.clear(), once_r.clear(), cand.clear();
         // (1) word-parallel pass over the windows ending at or before lim
-        {
-            uint32_t wh = 0, wl = 0, run = 0;
-            for (uint32_t w = 0; (int) (w * 32u) <= lim; ++w) {
-                const uint32_t hi = p[3 * w], lo = p[3 * w + 1], va = p[3 * w + 2];
-                const uint32_t nb = (uint32_t) min(32, lim - (int) (w * 32u) + 1);
-                for (uint32_t j = 0; j < nb; ++j) {
-                    wh = (wh >> 1) | (((hi >> j) & 1u) << (k - 1));
-                    wl = (wl >> 1) | (((lo >> j) & 1u) << (k - 1));
-                    run = ((va >> j) & 1u) ? run + 1 : 0;
-                    if (run < (uint32_t) k) continue;
-                    const int q = (int) (32u * w + j);
-                    const uint32_t ka = __brev(wh) >> sh, kb = __brev(wl) >> sh;
-                    bool selfp;
-                    const uint32_t addr = psi_a<uint32_t>(ka, k, selfp);
-                    SliceWord<GW> mf, mr, x;
-                    if constexpr (GW <= 2) {
-                        // the pair (addr & ~1, addr | 1) is 2 * GW contiguous words: one load for both strands
-                        SliceWord<2 * GW> pr;
-                        pr.load(TA + (uint64_t) (addr & ~1u) * GW);
+        roll_windows(p, bases_to(lim), k, [&](int q, uint32_t wh, uint32_t wl, bool ok) {
+            if (ok) {
+                SliceWord<GW> mf, mr;
+                slice_window_masks<GW>(T, k, wh, wl, mf, mr);
+                if (t >= 2) {
 #pragma unroll
-                        for (int i = 0; i < GW; ++i) {
-                            mf.x[i] = pr.x[(addr & 1u) * GW + i];
-                            mr.x[i] = selfp ? mf.x[i] : pr.x[((addr & 1u) ^ 1u) * GW + i];
-                        }
-                    } else {
-                        mf.load(TA + (uint64_t) addr * GW);
-                        if (selfp) mr = mf;
-                        else mr.load(TA + (uint64_t) (addr ^ 1u) * GW);
-                    }
-                    if (mf.any()) {
-                        x.load(TB + (uint64_t) kb * GW), mf.and_with(x);
-                        if (mf.any()) {
-                            x.load(TC + (uint64_t) (ka ^ kb) * GW), mf.and_with(x);
-                            if (mf.any()) x.load(TD + (uint64_t) (ka | kb) * GW), mf.and_with(x);
-                        }
-                    }
-                    if (mr.any()) {
-                        const uint32_t ra = ~wh & mask, rb = ~wl & mask;
-                        x.load(TB + (uint64_t) rb * GW), mr.and_with(x);
-                        if (mr.any()) {
-                            x.load(TC + (uint64_t) (ra ^ rb) * GW), mr.and_with(x);
-                            if (mr.any()) x.load(TD + (uint64_t) (ra | rb) * GW), mr.and_with(x);
-                        }
-                    }
-                    if (t >= 2) {
+                    for (int i = 0; i < GW; ++i) cand.x[i] |= (once_f.x[i] & mf.x[i]) | (once_r.x[i] & mr.x[i]);
+                }
+                if (q <= pe) {
 #pragma unroll
-                        for (int i = 0; i < GW; ++i) cand.x[i] |= (once_f.x[i] & mf.x[i]) | (once_r.x[i] & mr.x[i]);
-                    }
-                    if (q <= pe) {
-#pragma unroll
-                        for (int i = 0; i < GW; ++i) once_f.x[i] |= mf.x[i], once_r.x[i] |= mr.x[i];
-                    }
+                    for (int i = 0; i < GW; ++i) once_f.x[i] |= mf.x[i], once_r.x[i] |= mr.x[i];
                 }
             }
-            if (t < 2) {
+        });
+        if (t < 2) {
 #pragma unroll
-                for (int i = 0; i < GW; ++i) cand.x[i] = once_f.x[i] | once_r.x[i];
-            }
+            for (int i = 0; i < GW; ++i) cand.x[i] = once_f.x[i] | once_r.x[i];
         }
         // (2) exact replay of the candidate chunks, in chunk order (search_reads.h:45-83 on chunk c's bits)
 #pragma unroll 1
         for (int cw = 0; cw < GW && !found; ++cw) {
-            uint32_t m = 0;
-#pragma unroll
-            for (int i = 0; i < GW; ++i)
-                if (i == cw) m = cand.x[i];   // (a select per word keeps cand in registers)
+            uint32_t m = slice_pick<GW>(cand, cw);
             while (m && !found) {
                 const int cb = __ffs((int) m) - 1;
                 m &= m - 1u;
                 const int c = cw * 32 + cb;
                 if (c >= g) break;
-                auto bit = [&](const uint32_t *T, uint32_t key) -> bool { return (T[(uint64_t) key * GW + cw] >> cb) & 1u; };
-                for (int strand = 0; strand < 2 && !found; ++strand) {
-                    uint32_t wh = 0, wl = 0, run = 0;
-                    int seen = 0;
-                    bool dead = false;
-                    for (uint32_t w = 0; w * 32u < len && !found && !dead; ++w) {
-                        const uint32_t hi = p[3 * w], lo = p[3 * w + 1], va = p[3 * w + 2];
-                        const uint32_t nb = min(32u, len - w * 32u);
-                        for (uint32_t j = 0; j < nb; ++j) {
-                            wh = (wh >> 1) | (((hi >> j) & 1u) << (k - 1));
-                            wl = (wl >> 1) | (((lo >> j) & 1u) << (k - 1));
-                            run = ((va >> j) & 1u) ? run + 1 : 0;
-                            // exact pruning (see search_kernel): the missing hits no longer fit behind this window
-                            if ((int) (32u * w + j) + (t - seen - 1) * k > last) {
-                                dead = true;
-                                break;
-                            }
-                            if (run < (uint32_t) k) continue;
-                            uint32_t ka, kb;
-                            if (strand == 0) ka = __brev(wh) >> sh, kb = __brev(wl) >> sh;
-                            else ka = ~wh & mask, kb = ~wl & mask;
-                            if (bit(TA, psi_a<uint32_t>(ka, k)) && bit(TB, kb) && bit(TC, ka ^ kb) && bit(TD, ka | kb)) {
-                                ++seen;
-                                run = 0;                       // hash.clear(), search_reads.h:60
-                                if (seen >= t) {
-                                    found = true;
-                                    break;
-                                }
-                            }
-                        }
-                    }
-                }
+                for (int strand = 0; strand < 2 && !found; ++strand) found = slice_strand_count<GW, true>(p, last, T, k, cw, cb, strand, t) >= t;
                 if (found) found_chunk = c;
             }
         }
@@ -353,6 +430,79 @@ __device__ __forceinline__ uint4 wide_at_least(const uint4 &c0, const uint4 &c1,
     return make_uint4(c0.x & c1.x, c0.y & c1.y, c0.z & c1.z, c0.w & c1.w);
 }
 __device__ __forceinline__ uint32_t wide_word(const uint4 &v, uint32_t j) { return j == 0 ? v.x : j == 1 ? v.y : j == 2 ? v.z : v.w; }
+__device__ __forceinline__ void wide_drop(uint4 &v, uint32_t j, uint32_t keep)
+{
+    if (j == 0) v.x &= keep;
+    else if (j == 1) v.y &= keep;
+    else if (j == 2) v.z &= keep;
+    else v.w &= keep;
+}
+// the ballot of a read's group of LPR lanes (by the whole wave)
+template <int LPR>
+__device__ __forceinline__ uint64_t wide_ballot(bool x, int grp)
+{
+    uint64_t m = __ballot(x);
+    if constexpr (LPR < 64) m = (m >> (grp * LPR)) & ((1ull << LPR) - 1ull);
+    return m;
+}
+
+// (1) of search_wide_kernel (hits_wide_kernel keeps the same pass written out, to `last`: see there): the row pass over the windows
+// ending at or before `end`, every lane of the group rolling the same window.  Per window and strand six coalesced row fetches, lane sl the pieces sl + LPR * i it has (have[i]), planes
+// A & B & C; per block of k window positions (roll_blocks) the chunk bits with a hit go into the 2-bit counters (f1 f0), (r1 r0)
+template <int LPR, int NP>
+__device__ __forceinline__ void wide_row_pass(const uint32_t *__restrict__ p, int end, const SlicePlanes &T, int k, uint32_t rw, int sl, const bool (&have)[NP],
+                                              uint4 (&f0)[NP], uint4 (&f1)[NP], uint4 (&r0)[NP], uint4 (&r1)[NP])
+{
+    uint4 cur_f[NP], cur_r[NP];
+#pragma unroll
+    for (int i = 0; i < NP; ++i) cur_f[i] = cur_r[i] = f0[i] = f1[i] = r0[i] = r1[i] = make_uint4(0, 0, 0, 0);
+    roll_blocks(
+        p, bases_to(end), k,
+        [&](uint32_t wh, uint32_t wl) {
+            uint32_t ka, kb, ra, rb;
+            strand_keys(0, wh, wl, k, ka, kb), strand_keys(1, wh, wl, k, ra, rb);
+            bool selfp;
+            const uint32_t addr = psi_a<uint32_t>(ka, k, selfp);
+            const uint4 *af = (const uint4 *) (T.a + (uint64_t) addr * rw), *ar = (const uint4 *) (T.a + (uint64_t) (selfp ? addr : addr ^ 1u) * rw);
+            const uint4 *bf = (const uint4 *) (T.b + (uint64_t) kb * rw), *br = (const uint4 *) (T.b + (uint64_t) rb * rw);
+            const uint4 *cf = (const uint4 *) (T.c + (uint64_t) (ka ^ kb) * rw), *cr = (const uint4 *) (T.c + (uint64_t) (ra ^ rb) * rw);
+            uint4 x[NP][6];
+#pragma unroll
+            for (int i = 0; i < NP; ++i) {
+                if (!have[i]) continue;
+                const int pc = sl + LPR * i;
+                x[i][0] = af[pc], x[i][1] = bf[pc], x[i][2] = cf[pc];
+                x[i][3] = ar[pc], x[i][4] = br[pc], x[i][5] = cr[pc];
+            }
+#pragma unroll
+            for (int i = 0; i < NP; ++i) {
+                if (!have[i]) continue;
+                or_into(cur_f[i], and3(x[i][0], x[i][1], x[i][2]));
+                or_into(cur_r[i], and3(x[i][3], x[i][4], x[i][5]));
+            }
+        },
+        [&]() {
+#pragma unroll
+            for (int i = 0; i < NP; ++i) wide_fold(cur_f[i], f0[i], f1[i]), wide_fold(cur_r[i], r0[i], r1[i]);
+        });
+}
+
+// The per-window test of search_wide_kernel's replay, lane = window: the window that ends at q is complete, all ACGT and a full
+// four-lane hit on the strand in the chunk at bit cb of word cw of the rows.  (hits_wide_kernel has the same test written out, in a loop
+// of its own: it asks only the windows from next_ok on and jumps there, where this kernel asks every window of a stretch of LPR and
+// prunes while it walks the ballot — one loop for both would change what the search kernel requests)
+__device__ __forceinline__ bool wide_window_hit(const uint32_t *__restrict__ p, int q, const SlicePlanes &T, int k, uint32_t rw, int strand, uint32_t cw, uint32_t cb)
+{
+    ItemWords<uint32_t> it;
+    it.load(p, (uint32_t) q >> 5);
+    uint32_t wh, wl;
+    if (!it.window((uint32_t) q & 31u, k, (1u << k) - 1u, wh, wl)) return false;
+    uint32_t ka, kb;
+    strand_keys(strand, wh, wl, k, ka, kb);
+    const uint32_t va = T.a[(uint64_t) psi_a<uint32_t>(ka, k) * rw + cw], vb = T.b[(uint64_t) kb * rw + cw];
+    const uint32_t vc = T.c[(uint64_t) (ka ^ kb) * rw + cw], vd = T.d[(uint64_t) (ka | kb) * rw + cw];
+    return ((va & vb & vc & vd) >> cb) & 1u;
+}
 
 template <int LPR, int NP>
 __global__ __launch_bounds__(256) void search_wide_kernel(ReadsView rv, const uint32_t *__restrict__ tables, int k, int t, int g,
@@ -367,14 +517,11 @@ __global__ __launch_bounds__(256) void search_wide_kernel(ReadsView rv, const ui
     bool active = r < rv.n;
     if (active && sel) active = (sel[r >> 6] >> (r & 63)) & 1ull;
     if (active && tags) active = !((tags[r >> 6] >> (r & 63)) & 1ull);
-    const uint64_t plane_stride = ((uint64_t) rw) << k;   // words per table
-    const uint32_t *TA = tables, *TB = TA + plane_stride, *TC = TB + plane_stride, *TD = TC + plane_stride;
+    const SlicePlanes T(tables, k, rw);
     uint64_t t0 = 0;
     uint32_t len = 0;
     if (active) read_extent(rv, r, t0, len);
     const uint32_t *p = rv.planes + 3 * t0;
-    const int sh = 32 - k;
-    const uint32_t mask = (1u << k) - 1u;
     const int last = (int) len - 1;
     const int J = min(t, 3);
     const int lim = active ? last - (t - J) * k : -1;     // hit J of a strand's scan ends at or before lim
@@ -384,52 +531,10 @@ __global__ __launch_bounds__(256) void search_wide_kernel(ReadsView rv, const ui
     for (int i = 0; i < NP; ++i) have[i] = 4u * (uint32_t) (sl + LPR * i) < nw;
     // (1) row pass over the windows ending at or before lim; every lane of the group rolls the same window
     {
-        uint4 cur_f[NP], cur_r[NP], f0[NP], f1[NP], r0[NP], r1[NP];
-#pragma unroll
-        for (int i = 0; i < NP; ++i) cur_f[i] = cur_r[i] = f0[i] = f1[i] = r0[i] = r1[i] = make_uint4(0, 0, 0, 0);
-        uint32_t wh = 0, wl = 0, run = 0;
-        int in_block = 0;                                  // window positions since the block began
-        for (uint32_t w = 0; (int) (w * 32u) <= lim; ++w) {
-            const uint32_t hi = p[3 * w], lo = p[3 * w + 1], va = p[3 * w + 2];
-            const uint32_t nb = (uint32_t) min(32, lim - (int) (w * 32u) + 1);
-            for (uint32_t j = 0; j < nb; ++j) {
-                wh = (wh >> 1) | (((hi >> j) & 1u) << (k - 1));
-                wl = (wl >> 1) | (((lo >> j) & 1u) << (k - 1));
-                run = ((va >> j) & 1u) ? run + 1 : 0;
-                if ((int) (32u * w + j) < k - 1) continue;              // not a window position yet
-                if (run >= (uint32_t) k) {
-                    const uint32_t ka = __brev(wh) >> sh, kb = __brev(wl) >> sh;
-                    const uint32_t ra = ~wh & mask, rb = ~wl & mask;
-                    bool selfp;
-                    const uint32_t addr = psi_a<uint32_t>(ka, k, selfp);
-                    const uint4 *af = (const uint4 *) (TA + (uint64_t) addr * rw), *ar = (const uint4 *) (TA + (uint64_t) (selfp ? addr : addr ^ 1u) * rw);
-                    const uint4 *bf = (const uint4 *) (TB + (uint64_t) kb * rw), *br = (const uint4 *) (TB + (uint64_t) rb * rw);
-                    const uint4 *cf = (const uint4 *) (TC + (uint64_t) (ka ^ kb) * rw), *cr = (const uint4 *) (TC + (uint64_t) (ra ^ rb) * rw);
-                    uint4 x[NP][6];
-#pragma unroll
-                    for (int i = 0; i < NP; ++i) {
-                        if (!have[i]) continue;
-                        const int pc = sl + LPR * i;
-                        x[i][0] = af[pc], x[i][1] = bf[pc], x[i][2] = cf[pc];
-                        x[i][3] = ar[pc], x[i][4] = br[pc], x[i][5] = cr[pc];
-                    }
-#pragma unroll
-                    for (int i = 0; i < NP; ++i) {
-                        if (!have[i]) continue;
-                        or_into(cur_f[i], and3(x[i][0], x[i][1], x[i][2]));
-                        or_into(cur_r[i], and3(x[i][3], x[i][4], x[i][5]));
-                    }
-                }
-                if (++in_block == k) {                      // the block is complete
-                    in_block = 0;
-#pragma unroll
-                    for (int i = 0; i < NP; ++i) wide_fold(cur_f[i], f0[i], f1[i]), wide_fold(cur_r[i], r0[i], r1[i]);
-                }
-            }
-        }
+        uint4 f0[NP], f1[NP], r0[NP], r1[NP];
+        wide_row_pass<LPR, NP>(p, lim, T, k, rw, sl, have, f0, f1, r0, r1);
 #pragma unroll
         for (int i = 0; i < NP; ++i) {
-            wide_fold(cur_f[i], f0[i], f1[i]), wide_fold(cur_r[i], r0[i], r1[i]);   // the last, partial block
             cand_f[i] = wide_at_least(f0[i], f1[i], J), cand_r[i] = wide_at_least(r0[i], r1[i], J);
             if (!have[i]) cand_f[i] = cand_r[i] = make_uint4(0, 0, 0, 0);
         }
@@ -464,14 +569,10 @@ __global__ __launch_bounds__(256) void search_wide_kernel(ReadsView rv, const ui
             for (int i = 0; i < NP; ++i)
                 if (pc == (uint32_t) (sl + LPR * i)) {
                     mine_f = (wide_word(cand_f[i], wj) >> cb) & 1u, mine_r = (wide_word(cand_r[i], wj) >> cb) & 1u;
-                    if (wj == 0) cand_f[i].x &= keep, cand_r[i].x &= keep;
-                    else if (wj == 1) cand_f[i].y &= keep, cand_r[i].y &= keep;
-                    else if (wj == 2) cand_f[i].z &= keep, cand_r[i].z &= keep;
-                    else cand_f[i].w &= keep, cand_r[i].w &= keep;
+                    wide_drop(cand_f[i], wj, keep), wide_drop(cand_r[i], wj, keep);
                 }
         }
-        uint64_t bf = __ballot(mine_f), br = __ballot(mine_r);
-        if constexpr (LPR < 64) bf = (bf >> (grp * LPR)) & ((1ull << LPR) - 1ull), br = (br >> (grp * LPR)) & ((1ull << LPR) - 1ull);
+        const uint64_t bf = wide_ballot<LPR>(mine_f, grp), br = wide_ballot<LPR>(mine_r, grp);
         bool found = false;
         for (int strand = 0; strand < 2; ++strand) {
             const bool flagged = go && (strand ? br != 0 : bf != 0);   // a strand without J hit blocks cannot find the read
@@ -479,22 +580,8 @@ __global__ __launch_bounds__(256) void search_wide_kernel(ReadsView rv, const ui
             bool dead = false;
             for (int qb = k - 1; __any(flagged && !found && !dead && qb <= last && qb + (t - seen - 1) * k <= last); qb += LPR) {
                 const int q = qb + sl;
-                bool hit = false;
-                if (flagged && !found && !dead && q <= last) {
-                    ItemWords<uint32_t> it;
-                    it.load(p, (uint32_t) q >> 5);
-                    uint32_t wh, wl;
-                    if (it.window((uint32_t) q & 31u, k, mask, wh, wl)) {
-                        uint32_t ka, kb;
-                        if (strand == 0) ka = __brev(wh) >> sh, kb = __brev(wl) >> sh;
-                        else ka = ~wh & mask, kb = ~wl & mask;
-                        const uint32_t va = TA[(uint64_t) psi_a<uint32_t>(ka, k) * rw + cw], vb = TB[(uint64_t) kb * rw + cw];
-                        const uint32_t vc = TC[(uint64_t) (ka ^ kb) * rw + cw], vd = TD[(uint64_t) (ka | kb) * rw + cw];
-                        hit = ((va & vb & vc & vd) >> cb) & 1u;
-                    }
-                }
-                uint64_t m = __ballot(hit);
-                if constexpr (LPR < 64) m = (m >> (grp * LPR)) & ((1ull << LPR) - 1ull);
+                const bool hit = flagged && !found && !dead && q <= last && wide_window_hit(p, q, T, k, rw, strand, cw, cb);
+                uint64_t m = wide_ballot<LPR>(hit, grp);
                 while (m && !found && !dead) {
                     const int qq = qb + (__ffsll((long long) m) - 1);
                     m &= m - 1ull;

@@ -384,8 +384,9 @@ SLICED_FHW = (1, 32, 33, 65, 97, 129)
 SLOT_SWEEPS = [(k, t, 6, FHW, 0) for k in (25, 32, 33, 34) for t in (1, 2, 3)]
 SMALL_SWEEPS = [(20, t, 6, FHW, 0) for t in (1, 2, 3)] + [(16, t, 0, FHW, 8) for t in (1, 2, 3)]                 # the plain kernel below the tiled search's k
 # (k = 12, t = 1: one accidental hit anywhere flips a read, and a filter of 2^12 bits gives one in a thousand reads: three fhw only)
+# (t >= 4: the wide row pass ends before the last window, at last - (t - 3) k; shorter fhw lists keep the reads within 255 first-hit windows)
 SLICED_SWEEPS = [(12, 1, 0, (1, 32, 33), 4), (12, 2, 0, SLICED_FHW, 4), (16, 1, 0, SLICED_FHW, 16), (16, 2, 0, SLICED_FHW, 16),
-                 (21, 3, 40, SLICED_FHW, 0), (24, 2, 40, SLICED_FHW, 0)]
+                 (21, 3, 40, SLICED_FHW, 0), (24, 2, 40, SLICED_FHW, 0), (16, 5, 0, (1, 32, 33), 16), (21, 4, 40, (1, 32, 33, 65), 0)]
 SLOT_LADDERS = [(k, 6) for k in (16, 20, 25, 32, 33, 34)]
 SLICED_LADDERS = [(k, 300) for k in (12, 16, 21, 24)]
 JOB_LADDERS = [(25, 3), (33, 3), (32, 1)]                      # (k, chunks per index set)
