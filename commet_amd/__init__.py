@@ -8,7 +8,7 @@ Only what the path needs lives here:
   build.py   hipcc / g++ build recipes used by __graft_entry__.build()
 """
 from .api import Context, ReadSet, CommetError, device_count, device_cache_trim, device_cache_bytes, device_pooled_bytes, device_alloc_stats, files_packed_bytes, tags_at  # noqa: F401
-from .api import device_alloc_refuse, device_alloc_requests, refusing_device_allocs  # noqa: F401
+from .api import device_alloc_refuse, device_alloc_requests, refusing_device_allocs, hits_to_tags  # noqa: F401
 
 __all__ = ["Context", "ReadSet", "CommetError", "device_count", "device_cache_trim", "device_cache_bytes", "device_pooled_bytes", "device_alloc_stats", "files_packed_bytes", "tags_at",
-           "device_alloc_refuse", "device_alloc_requests", "refusing_device_allocs"]
+           "device_alloc_refuse", "device_alloc_requests", "refusing_device_allocs", "hits_to_tags"]

@@ -143,6 +143,11 @@ def files_packed_bytes(paths):
     return int(r.value), int(b.value), int(p.value)
 
 
+def hits_to_tags(ctx, hits, file_reads=None, t_first=1, n_t=1, want_shared=True):
+    """Context.hits_to_tags: tags_at for every t in t_first .. t_first + n_t - 1 and the per-file counts, on ctx's device"""
+    return ctx.hits_to_tags(hits, file_reads, t_first, n_t, want_shared)
+
+
 class Context:
     """commet_ctx: device, k, t, the 4-lane Bloom filter in HBM."""
 
@@ -294,6 +299,50 @@ class Context:
         self._check(self._lib.commet_index_many_and_profile(self._h, nj, _handles(index_sets), _ptrs(isel), search_rs._h, _ptr(ssel), cap_arr,
                                                             _ptrs(hits), C.byref(info)))
         return hits, _info_dict(info)
+
+    def hits_to_tags(self, hits, file_reads=None, t_first=1, n_t=1, want_shared=True, fill=0):
+        """commet_hits_to_tags: hits_tags_kernel on host bytes.  Returns (tags, shared): tags[ti] = tags_at(hits, t_first + ti), made
+        on the device; shared[ti][f] = the reads of file f (file_reads: the read counts of contiguous files, default one file) with at
+        least that many hits (None when want_shared is false).  fill (tests): the byte the output buffers hold before the call."""
+        h = np.ascontiguousarray(hits, dtype=np.uint8)
+        fr = np.ascontiguousarray([h.size] if file_reads is None else file_reads, dtype=np.uint64)
+        tags = [np.full(bits_nbytes(h.size), fill, dtype=np.uint8) for _ in range(int(n_t))]
+        shared = np.full((int(n_t), fr.size), fill * 0x0101010101010101, dtype=np.uint64) if want_shared else None
+        self._check(self._lib.commet_hits_to_tags(self._h, _ptr(h) if h.size else None, h.size, fr.size, fr.ctypes.data_as(_l.u64p), int(t_first),
+                                                  int(n_t), _ptrs(tags), _ptr(shared)))
+        return tags, shared
+
+    def index_and_thresholds(self, index_rs, search_sets, index_select=None, search_selects=None, max_t=8):
+        """commet_index_and_thresholds: index_and_profile with max_hits = max_t, thresholded on the device.  Returns (tags, shared,
+        info): tags[s][t - 1] = the BooleanVector bytes index_and_search gives for search set s on a context of this k and that t,
+        shared[s][t - 1] = np.uint64 per file of set s, its reads among them — for every t in 1..max_t, from one search."""
+        ns, T = len(search_sets), int(max_t)
+        isel = _as_bits(index_select, index_rs.num_reads, "index_select")
+        ssel = _selections(search_selects, search_sets, "search_select")
+        tags = [[np.zeros(bits_nbytes(rs.num_reads), dtype=np.uint8) for _ in range(T)] for rs in search_sets]
+        shared = [[np.zeros(rs.num_files, dtype=np.uint64) for _ in range(T)] for rs in search_sets]
+        info = _l.JobInfo()
+        self._check(self._lib.commet_index_and_thresholds(self._h, index_rs._h, _ptr(isel), ns, _handles(search_sets), _ptrs(ssel), T,
+                                                          _ptrs([a for row in tags for a in row]), _ptrs([a for row in shared for a in row]),
+                                                          C.byref(info)))
+        return tags, shared, _info_dict(info)
+
+    def index_many_and_thresholds(self, index_sets, search_rs, index_selects=None, search_select=None, t=2):
+        """commet_index_many_and_thresholds: index_many_and_profile with max_hits[j] = t[j] (an int or one entry per job), thresholded
+        on the device: the many-job search with a threshold per job.  Returns (tags, shared, info): tags[j] = job j's BooleanVector
+        bytes at t[j], shared[j] = np.uint64 per file of search_rs."""
+        nj = len(index_sets)
+        ts = [int(t)] * nj if np.isscalar(t) else [int(x) for x in t]
+        if len(ts) != nj:
+            raise CommetError(f"t: need one entry per job ({nj}), got {len(ts)}")
+        isel = _selections(index_selects, index_sets, "index_select")
+        ssel = _as_bits(search_select, search_rs.num_reads, "search_select")
+        tags = [np.zeros(bits_nbytes(search_rs.num_reads), dtype=np.uint8) for _ in range(nj)]
+        shared = [np.zeros(search_rs.num_files, dtype=np.uint64) for _ in range(nj)]
+        info = _l.JobInfo()
+        self._check(self._lib.commet_index_many_and_thresholds(self._h, nj, _handles(index_sets), _ptrs(isel), search_rs._h, _ptr(ssel),
+                                                               (C.c_int * max(nj, 1))(*ts), _ptrs(tags), _ptrs(shared), C.byref(info)))
+        return tags, shared, _info_dict(info)
 
     def poison(self, byte):
         """test hook: every bit array of the context (filter slots, interleaved A planes, bit-sliced planes and tables) filled with `byte`"""

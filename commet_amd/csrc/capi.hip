@@ -16,6 +16,7 @@
 #include "hit_profile_wide.hpp"
 #include "hit_profile_sliced.hpp"
 #include "hit_profile_tiled.hpp"
+#include "hits_tags.hpp"
 #include "read_filter.hpp"
 #include "filter_bits.hpp"
 #include "read_iter.hpp"
@@ -63,6 +64,7 @@
 #include "capi/job.hpp"              // commet_index_reads / _search_reads / _index_and_search
 #include "capi/many.hpp"             // what the two many-job calls share: their record, plans, pass packing, the build of a pass's filters
 #include "capi/multi.hpp"            // commet_index_many_and_search: several jobs on one search set, their filters in one pass
+#include "capi/thresholds.hpp"       // what a profile call leaves of its byte arrays: bytes, or tags and per-file counts (hits_tags_kernel); commet_hits_to_tags
 #include "capi/profile.hpp"          // commet_index_and_profile: per-read hit counts, the tags of every t from one job
 #include "capi/multi_profile.hpp"    // commet_index_many_and_profile: several profile jobs on one search set, their filters in one hits pass
 #include "capi/options.hpp"          // commet_set_option, measurement hooks

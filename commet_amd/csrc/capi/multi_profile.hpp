@@ -25,6 +25,8 @@
 // Auto (multi_job = 0) shares where the search set takes a lane per read: measured against the jobs one by one in MEASUREMENTS.md,
 // "Jobs that share a hits pass".  A search set of long reads stays job by job in auto, as on the search side (multi.hpp).
 // Not built: the tiled probe or the bit-sliced tables for shared passes, passes shared between jobs whose search selections differ.
+// commet_index_many_and_thresholds is the same call (profile_many below) with max_hits[j] = t[j] and another last step: per job the
+// tags at t[j] and the per-file counts come down, not the bytes (HitsLeave, thresholds.hpp) — the many-job search with a threshold per job.
 #pragma once
 
 namespace {
@@ -32,7 +34,10 @@ namespace {
 // one commet_index_many_and_profile call (the record both many-job calls keep: ManyCall, many.hpp)
 struct ProfileManyRun : ManyCall {
     const int *max_hits;
-    uint8_t *const *hits_out;
+    uint8_t *const *hits_out;                   // job j's bytes; or, tags (commet_index_many_and_thresholds): job j's tags at max_hits[j] and its
+    bool tags = false;                          // per-file counts, tags_out[j] and shared_out[j] (HitsLeave, thresholds.hpp)
+    uint8_t *const *tags_out = nullptr;
+    uint64_t *const *shared_out = nullptr;
     int cap = 8;                                // slots of a pass
     std::vector<uint8_t> vis;                   // the reads the passes visit (plan_search), unless all of them
     bool all_visited = false;
@@ -140,28 +145,32 @@ int run_shared_hits_pass(ProfileManyRun &m, const std::vector<int> &in_pass)
     if (m.tm.end_set(0)) return 1;
     m.clk.lap(m.ph_launch);
     HIP_OK(hipMemcpyAsync(&c->h_counters[0], c->d_jobcnt, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-    for (size_t q = 0; q < in_pass.size(); ++q)
-        if (m.hits_out && m.hits_out[in_pass[q]])
-            HIP_OK(hipMemcpyAsync(m.hits_out[in_pass[q]], c->d_hits + (uint64_t) q * m.stride, srs->n_reads, hipMemcpyDeviceToHost, c->stream));
+    HitsLeave leave;
+    for (size_t q = 0; q < in_pass.size(); ++q) {
+        const int j = in_pass[q];
+        const uint8_t *d = c->d_hits + (uint64_t) q * m.stride;
+        if (m.tags) leave.tags_of(d, srs, m.max_hits[j], 1, m.tags_out ? m.tags_out + j : nullptr, m.shared_out ? m.shared_out + j : nullptr);
+        else if (m.hits_out && m.hits_out[j]) leave.bytes_of(d, srs->n_reads, m.hits_out[j]);
+    }
+    if (leave.queue(c)) return 1;
     HIP_OK(hipStreamSynchronize(c->stream));
     c->kclock.collect();
+    leave.finish();
     m.sum.reads_scanned += c->h_counters[0];
     (void) account_pass_times(m);
     m.clk.lap(m.ph_wait);
     return 0;
 }
 
-}  // namespace
-
-extern "C" {
-
-int commet_index_many_and_profile(commet_ctx *c, int n_jobs, const commet_readset *const *index_rs, const uint8_t *const *index_select,
-                                  const commet_readset *search_rs, const uint8_t *search_select, const int *max_hits, uint8_t *const *hits_out,
-                                  commet_job_info *info)
+// the call behind commet_index_many_and_profile (hits_out: the bytes) and commet_index_many_and_thresholds (hits_out == nullptr: job
+// j's tags at max_hits[j] and its per-file counts): everything up to the download is the same
+int profile_many(commet_ctx *c, int n_jobs, const commet_readset *const *index_rs, const uint8_t *const *index_select, const commet_readset *search_rs,
+                 const uint8_t *search_select, const int *max_hits, uint8_t *const *hits_out, bool tags, uint8_t *const *tags_out,
+                 uint64_t *const *shared_out, commet_job_info *info)
 {
     if (validate_many(c, n_jobs, index_rs, search_rs)) return 1;
     for (int j = 0; j < n_jobs; ++j)
-        if (max_hits[j] < 1 || max_hits[j] > 255) return fail("max_hits must be in 1..255 (got %d for job %d)", max_hits[j], j);
+        if (max_hits[j] < 1 || max_hits[j] > 255) return fail("%s must be in 1..255 (got %d for job %d)", tags ? "t" : "max_hits", max_hits[j], j);
     HIP_OK(hipSetDevice(c->device));
     // the sets of this call are neither exported nor offloaded while it runs (the jobs that run alone count their own sets again: in_job is a depth)
     SetUse in_jobs(c, search_rs);
@@ -169,10 +178,14 @@ int commet_index_many_and_profile(commet_ctx *c, int n_jobs, const commet_readse
     if (in_jobs.enter()) return 1;
     ProfileManyRun m(c, n_jobs, index_rs, index_select, search_rs, search_select, max_hits, hits_out);
     m.cap = std::max(1, std::min(8, c->chunk_group));
+    m.tags = tags, m.tags_out = tags_out, m.shared_out = shared_out;
     const OneJob one = [&](int j, commet_job_info *ji) {
         uint8_t *to = hits_out ? hits_out[j] : nullptr;
-        return commet_index_and_profile(c, index_rs[j], index_select ? index_select[j] : nullptr, 1, &search_rs, search_select ? &search_select : nullptr,
-                                        max_hits[j], hits_out ? &to : nullptr, ji);
+        ProfileWant want;
+        if (tags) want.t_first = max_hits[j], want.n_t = 1, want.tags_out = tags_out ? tags_out + j : nullptr, want.shared_out = shared_out ? shared_out + j : nullptr;
+        else want.hits_out = hits_out ? &to : nullptr;
+        return profile_job(c, index_rs[j], index_select ? index_select[j] : nullptr, 1, &search_rs, search_select ? &search_select : nullptr, max_hits[j],
+                           want, ji);
     };
     auto finish = [&](const char *what) {
         m.sum.probes = 0;
@@ -219,6 +232,24 @@ int commet_index_many_and_profile(commet_ctx *c, int n_jobs, const commet_readse
         if (rc == 2) return no_room();
     }
     return finish("");
+}
+
+}  // namespace
+
+extern "C" {
+
+int commet_index_many_and_profile(commet_ctx *c, int n_jobs, const commet_readset *const *index_rs, const uint8_t *const *index_select,
+                                  const commet_readset *search_rs, const uint8_t *search_select, const int *max_hits, uint8_t *const *hits_out,
+                                  commet_job_info *info)
+{
+    return profile_many(c, n_jobs, index_rs, index_select, search_rs, search_select, max_hits, hits_out, false, nullptr, nullptr, info);
+}
+
+int commet_index_many_and_thresholds(commet_ctx *c, int n_jobs, const commet_readset *const *index_rs, const uint8_t *const *index_select,
+                                     const commet_readset *search_rs, const uint8_t *search_select, const int *t, uint8_t *const *tags_out,
+                                     uint64_t *const *shared_out, commet_job_info *info)
+{
+    return profile_many(c, n_jobs, index_rs, index_select, search_rs, search_select, t, nullptr, true, tags_out, shared_out, info);
 }
 
 }  // extern "C"

@@ -156,6 +156,11 @@ int commet_set_option(commet_ctx *c, const char *name, int64_t value)
         c->tq_hit_cap = (int) std::max<int64_t>(0, std::min<int64_t>(value, TQ_HIT_CAP));
         return 0;
     }
+    if (!strcmp(name, "hits_tags_blocks")) {  // TEST HOOK: the most workgroups a hits_tags_kernel launch takes (capi/thresholds.hpp); fewer: more tiles per workgroup
+        if (value < 1 || value > HITS_TAGS_BLOCKS) return fail("hits_tags_blocks must be in 1..%d", HITS_TAGS_BLOCKS);
+        c->hits_tags_blocks = (int) value;
+        return 0;
+    }
     if (!strcmp(name, "part_list")) {
         c->part_list = value != 0;
         return 0;

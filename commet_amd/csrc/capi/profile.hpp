@@ -32,6 +32,8 @@
 // the 1 GiB clamp), in one table set built by run_narrow_passes (job.hpp) as a job's are, and ONE hits_sliced_kernel launch per search
 // set and pass.  No room for the tables: the slot loop.  1 = never; 0 = auto, which is never for now (MEASUREMENTS.md, "Hit profile").
 // Several such jobs on one search set, their chunk filters in one hits pass: commet_index_many_and_profile (capi/multi_profile.hpp).
+// commet_index_and_thresholds is the same job (profile_job below) with another last step: the bytes stay on the device and the tags of
+// every t in 1..max_t and the per-file counts come down instead (HitsLeave, thresholds.hpp).
 #pragma once
 
 namespace {
@@ -246,13 +248,19 @@ int run_profile_sliced(JobRun &j, int max_hits, const std::vector<uint64_t> &at,
     });
 }
 
-}  // namespace
+// What a single profile job leaves of the bytes of its search sets (HitsLeave, thresholds.hpp): the bytes themselves, hits_out[s]
+// (commet_index_and_profile), or, n_t > 0, the tags of the thresholds t_first .. t_first + n_t - 1 and the per-file counts, set s's
+// at tags_out[s * n_t + ti] and shared_out[s * n_t + ti] (the thresholds calls)
+struct ProfileWant {
+    uint8_t *const *hits_out = nullptr;
+    int t_first = 0, n_t = 0;
+    uint8_t *const *tags_out = nullptr;
+    uint64_t *const *shared_out = nullptr;
+};
 
-extern "C" {
-
-int commet_index_and_profile(commet_ctx *c, const commet_readset *index_rs, const uint8_t *index_select, int n_search,
-                             const commet_readset *const *search_rs, const uint8_t *const *search_select, int max_hits, uint8_t *const *hits_out,
-                             commet_job_info *info)
+// the profile job behind commet_index_and_profile and commet_index_and_thresholds: everything up to the download is the same
+int profile_job(commet_ctx *c, const commet_readset *index_rs, const uint8_t *index_select, int n_search, const commet_readset *const *search_rs,
+                const uint8_t *const *search_select, int max_hits, const ProfileWant &want, commet_job_info *info)
 {
     if (n_search < 0) return fail("n_search must not be negative (got %d)", n_search);
     if (max_hits < 1 || max_hits > 255) return fail("max_hits must be in 1..255 (got %d)", max_hits);
@@ -287,15 +295,44 @@ int commet_index_and_profile(commet_ctx *c, const commet_readset *index_rs, cons
     j.clk.lap(j.ph_launch);
     if (!rc && hipMemcpyAsync(&c->h_counters[0], d_walked, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream) != hipSuccess)
         rc = fail("counter copy failed");
-    for (int s = 0; s < n_search && !rc; ++s)
-        if (hits_out && hits_out[s] && search_rs[s]->n_reads &&
-            hipMemcpyAsync(hits_out[s], c->d_hits + at[(size_t) s], search_rs[s]->n_reads, hipMemcpyDeviceToHost, c->stream) != hipSuccess)
-            rc = fail("hit count copy failed");
+    HitsLeave leave;
+    for (int s = 0; s < n_search; ++s) {
+        const uint8_t *d = c->d_hits + at[(size_t) s];
+        if (want.n_t)
+            leave.tags_of(d, search_rs[s], want.t_first, want.n_t, want.tags_out ? want.tags_out + (size_t) s * want.n_t : nullptr,
+                          want.shared_out ? want.shared_out + (size_t) s * want.n_t : nullptr);
+        else if (want.hits_out && want.hits_out[s]) leave.bytes_of(d, search_rs[s]->n_reads, want.hits_out[s]);
+    }
+    if (!rc) rc = leave.queue(c);
     rc = drain_job(j, rc);
     if (rc) return rc;
+    leave.finish();
     fill_job_info(j, rc, nullptr, info, c->h_counters[0], 0);
     if (info) info->total_ms = j.clk.total_ms();
     return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int commet_index_and_profile(commet_ctx *c, const commet_readset *index_rs, const uint8_t *index_select, int n_search,
+                             const commet_readset *const *search_rs, const uint8_t *const *search_select, int max_hits, uint8_t *const *hits_out,
+                             commet_job_info *info)
+{
+    ProfileWant want;
+    want.hits_out = hits_out;
+    return profile_job(c, index_rs, index_select, n_search, search_rs, search_select, max_hits, want, info);
+}
+
+int commet_index_and_thresholds(commet_ctx *c, const commet_readset *index_rs, const uint8_t *index_select, int n_search,
+                                const commet_readset *const *search_rs, const uint8_t *const *search_select, int max_t, uint8_t *const *tags_out,
+                                uint64_t *const *shared_out, commet_job_info *info)
+{
+    if (max_t < 1 || max_t > 255) return fail("max_t must be in 1..255 (got %d)", max_t);
+    ProfileWant want;
+    want.t_first = 1, want.n_t = max_t, want.tags_out = tags_out, want.shared_out = shared_out;
+    return profile_job(c, index_rs, index_select, n_search, search_rs, search_select, max_t, want, info);
 }
 
 }  // extern "C"

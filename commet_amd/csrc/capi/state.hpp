@@ -9,6 +9,8 @@ namespace {
 
 thread_local std::string g_err;
 
+constexpr int HITS_TAGS_BLOCKS = 2048;          // workgroups of a hits_tags_kernel launch at most: eight per CU (capi/thresholds.hpp)
+
 // Every kernel launch of the library notes its entry point here (the host-side handle hipLaunchKernel takes): the
 // test-suite resolves the addresses against the library's symbol table and checks that every instantiation compiled
 // into it was reached by a parity test (commet_launched_kernels, tests/test_gpu_zz_dispatch_coverage.py).
@@ -478,6 +480,8 @@ struct commet_ctx {
     uint64_t mtags_cap = 0;
     uint8_t *d_hits = nullptr;                       // commet_index_and_profile: a hit-count byte per read of every search set of the call, kept between calls
     uint64_t hits_cap = 0;
+    uint64_t *d_twords = nullptr;                    // the thresholds calls (capi/thresholds.hpp): file ends, per-file counts and tag words of a call's byte arrays, kept between calls
+    uint64_t twords_cap = 0;
     int multi_job = 0;                               // option: 0 = commet_index_many_and_search shares passes between jobs where it can, 1 = job by job, 2 = as 0 + search sets of long reads; commet_index_many_and_profile the same (2 also shares hits passes on long-read search sets)
     int sparse_search = 0;                           // option: 0 auto (a pass over less than half of a set's reads), 1 never, 2 whenever a selection applies
     unsigned long long *d_plansum = nullptr;  // per-block k-mer sums of a selection (host planner input)
@@ -565,6 +569,7 @@ struct commet_ctx {
     uint8_t *d_qres = nullptr;        // tiled search (tile_search.hpp): one result byte per query record of the set being scanned
     uint64_t qres_cap = 0;
     int tq_hit_cap = TQ_HIT_CAP;      // option "tq_hit_cap" (tests): full hits a piece of the replay may post before its scans walk their own candidates
+    int hits_tags_blocks = HITS_TAGS_BLOCKS;   // option "hits_tags_blocks" (tests): the most workgroups of a hits_tags_kernel launch
     int ordered_scan = 0;             // option "ordered_scan": 0 = ragged sets of 2^16 reads and more are walked in order of their window counts by the
                                       // gather kernels' first pass, 1 = never, 2 = whenever the set is ragged (tests)
     int mask_split = 0;               // option "mask_split": 0 = a pass over that list runs segment by segment, each with the mask width its reads need, 1 = one launch

@@ -96,7 +96,12 @@ SIGNATURES = {
                                            C.c_int, C.POINTER(C.c_void_p), C.POINTER(JobInfo)]),
     "commet_index_many_and_profile": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p,
                                                 C.POINTER(C.c_int), C.POINTER(C.c_void_p), C.POINTER(JobInfo)]),
-    "commet_set_option": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int64]),
+    "commet_hits_to_tags": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, u64p, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_void_p]),
+    "commet_index_and_thresholds": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                              C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(JobInfo)]),
+    "commet_index_many_and_thresholds": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p,
+                                                   C.POINTER(C.c_int), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(JobInfo)]),
+    "commet_set_option":(C.c_int, [C.c_void_p, C.c_char_p, C.c_int64]),
     "commet_filter_export_reference": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
     "commet_filter_set_bits": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, u64p]),
     "commet_last_kernel_ms": (C.c_int, [C.c_void_p, f64p, f64p]),

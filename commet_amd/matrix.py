@@ -36,6 +36,7 @@ step (`filter_reads`, skipped when bvs are given), `OUT/<file>_in_<set>.bv`,
   python -m commet_amd.matrix sets.txt -k 32 -t 2 -o out/            (1 GPU)
   python -m commet_amd.matrix sets.txt -k 32 -t 2 -o out/ --gpus 8   (8 GPUs: starts its own ranks)
   python -m torch.distributed.run --nproc-per-node 8 -m commet_amd.matrix sets.txt …   (any launcher that sets RANK / WORLD_SIZE / MASTER_*)
+  python -m commet_amd.matrix sets.txt -k 32 --max-t 4 -o out/       (1 GPU: the matrix at every t = 1..4 from one run, out/t<t>/: matrix_sweep.py)
 """
 import argparse
 import os
@@ -150,6 +151,13 @@ class HipEngine:
 
     def index_many_and_search(self, indexes, search, isels, ssel):
         return self.ctx.index_many_and_search(indexes, search, isels, ssel)
+
+    # the threshold sweep (matrix_sweep.py): tags of every t and per-file counts, made on the device
+    def index_and_thresholds(self, index, searches, isel, ssels, max_t):
+        return self.ctx.index_and_thresholds(index, searches, isel, ssels, max_t)
+
+    def index_many_and_thresholds(self, indexes, search, isels, ssel, ts):
+        return self.ctx.index_many_and_thresholds(indexes, search, isels, ssel, ts)
 
     def list_estimate(self, rs):
         return rs.cache_estimate()
@@ -1087,7 +1095,27 @@ def main(argv=None):
                          "come back so that a matrix larger than the device finishes; one rank only")
     ap.add_argument("--gpus", type=int, default=1,
                     help="ranks to start on this node, one per GPU (ignored under a launcher that has set WORLD_SIZE)")
+    ap.add_argument("--max-t", dest="max_t", type=int, default=None,
+                    help="the matrix at every threshold t in 1..MAX_T from one run (commet_amd.matrix_sweep): OUT/t<t>/ holds what -t t "
+                         "writes; one rank, every set resident, -l 0; -t is not used")
     a = ap.parse_args(argv)
+    if a.max_t is not None:
+        from . import matrix_sweep
+        budget = a.set_budget_gb if a.set_budget_gb is not None else os.environ.get("COMMET_MATRIX_SET_BUDGET_GB")
+        why = matrix_sweep.refusal(a.max_t, gpus=a.gpus, set_budget_gb=budget, l=a.l, world=int(os.environ.get("WORLD_SIZE", "1")))
+        if why:
+            ap.error(why)
+        try:
+            res = matrix_sweep.run(a.input_file, a.directory, k=a.k, max_t=a.max_t, n=a.n, e=a.e, m=a.m, bin_dir=a.bin_dir)
+            if os.environ.get("COMMET_MATRIX_REPORT"):
+                import json
+                with open(os.environ["COMMET_MATRIX_REPORT"], "w") as fh:
+                    json.dump(res, fh)
+        except BaseException:
+            traceback.print_exc()
+            sys.stderr.flush()
+            os._exit(1)
+        return 0
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # this process never touches the GPU: it starts the ranks as plain child processes and leaves with their exit code
         return sharding.spawn_ranks(a.gpus, [sys.executable, "-m", "commet_amd.matrix"] + list(sys.argv[1:] if argv is None else argv))

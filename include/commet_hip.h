@@ -368,6 +368,33 @@ int commet_index_many_and_profile(commet_ctx *ctx, int n_jobs, const commet_read
                                   const uint8_t *search_select, const int *max_hits, uint8_t *const *hits_out,
                                   commet_job_info *info);
 
+/* Thresholds: the profile calls above with the step behind the search made on the device too — hits_tags_kernel (hits_tags.hpp)
+ * streams over the final hit-count bytes once and leaves, for every wanted threshold, the BooleanVector of the reads with at least
+ * that many hits and, per file of the searched set (files are contiguous runs of set-wide read numbers, commet_readset_file_reads;
+ * a file may hold no read), how many of its reads have them — the cells of the similarity matrix.  Only bits come down: no host
+ * code thresholds bytes or counts bits.  Tag arrays have n / 8 + 1 bytes like every tag array of this header, padding bits zero.
+ * When the device has no room for the tag words the bytes come down and a plain host loop makes the same tags and counts.
+ *
+ * commet_hits_to_tags: the kernel on HOST bytes (uploaded, thresholded, downloaded): tags_out[ti] = the reads r with
+ * hits[r] >= t_first + ti for ti in 0..n_t - 1 (1 <= t_first, t_first + n_t - 1 <= 255), shared_out[ti * n_files + f] (may be NULL)
+ * = those of them in file f; file_reads[0..n_files) must sum to n_reads.  A fast tags_at for large arrays, and the tests' handle. */
+int commet_hits_to_tags(commet_ctx *ctx, const uint8_t *hits, uint64_t n_reads, int n_files, const uint64_t *file_reads,
+                        int t_first, int n_t, uint8_t *const *tags_out, uint64_t *shared_out);
+/* commet_index_and_profile with max_hits = max_t (1..255), leaving tags and counts instead of bytes: tags_out[s * max_t + (t - 1)]
+ * is bit for bit what commet_index_and_search leaves for search set s on a context of this k and that t; shared_out (may be NULL;
+ * same indexing) points to one count per file of set s.  Any entry of either array may be NULL.  The context's own t is not used. */
+int commet_index_and_thresholds(commet_ctx *ctx, const commet_readset *index_rs, const uint8_t *index_select,
+                                int n_search, const commet_readset *const *search_rs, const uint8_t *const *search_select,
+                                int max_t, uint8_t *const *tags_out, uint64_t *const *shared_out, commet_job_info *info);
+/* commet_index_many_and_profile with max_hits[j] = t[j], leaving job j's tags at t[j] in tags_out[j] and its per-file counts (one
+ * per file of search_rs) in shared_out[j] (the array, and any entry of either, may be NULL): the many-job search with a threshold
+ * per job.  The jobs share hits passes as there; a job that runs alone, and every job when a pass has no room, goes through the
+ * single-job thresholds path. */
+int commet_index_many_and_thresholds(commet_ctx *ctx, int n_jobs, const commet_readset *const *index_rs,
+                                     const uint8_t *const *index_select, const commet_readset *search_rs,
+                                     const uint8_t *search_select, const int *t, uint8_t *const *tags_out,
+                                     uint64_t *const *shared_out, commet_job_info *info);
+
 /* ---- test / measurement hooks --------------------------------------------- */
 /* Tunables / diagnostics, by name.  Unknown names are an error.  None of them changes a result bit, except the test
  * hook max_kmer.
@@ -430,6 +457,8 @@ int commet_index_many_and_profile(commet_ctx *ctx, int n_jobs, const commet_read
  *                        narrowest masks its reads fit (the list starts with the reads of most windows), 1 = one launch at the set's width
  *   tq_hit_cap           TEST HOOK of the tiled search's replay: full hits a piece of 256 reads may post for its owners (default and
  *                        at most 1024; beyond it every scan of the piece walks its own candidates — same bits, slower); 0 forces that path
+ *   hits_tags_blocks     TEST HOOK: the most workgroups a hits_tags_kernel launch takes (1..2048, default 2048: a launch of more tiles
+ *                        of 4096 reads gives every workgroup a contiguous run of them; tests reach that walk at small sizes)
  *   part_no_uni (0/1)    1 = never take the fixed-read-length fast path of hist / scatter1 (nor the item list of ragged sets)
  *   part_list (0/1)      ragged sets (reads of several lengths): 0 = hist / scatter1 walk the chunk's item list (written out once per
  *                        chunk; the words of the coming round's items prefetched as on fixed-length sets), 1 = the round planner

@@ -35,6 +35,10 @@ stream synchronise and the copy back) and then runs once more with option kernel
                     tools/long_read_bench.py's workloads `ragged_1k_10k` and `len5500` (--long-workloads, --scale), one result line
                     each; both legs are ONE commet_index_many_and_profile call, (a) `alone` under multi_job = 1 (the jobs one by one
                     through hits_wave_kernel), (b) `shared` under multi_job = 2 (hits_jobs_wave_kernel); the protocol is --jobs' own
+  --thresholds      with --jobs N: the step behind the search.  Job j has the threshold 1 + j % --max-t; (a) `bytes`, the way there was before:
+                    ONE commet_index_many_and_profile call, then api.tags_at and matrix_io.popcount per job on the host; (b) `tags`: ONE
+                    commet_index_many_and_thresholds call (hits_tags_kernel: only bits come down).  Tags and counts of the two are
+                    compared; per leg the wall time of the whole step, the event-timed device time of the searches and the rest (host)
   python tools/hits_bench.py [--reads 10000000] [--read-len 100] [-k 32] [--max-t 8] [--rounds 2] [--reps 3] [--out FILE]"""
 import argparse
 import json
@@ -156,10 +160,20 @@ def child_many(a):
             bits[:packed.size] = packed
             sels.append(bits)
 
+        ts = [1 + j % a.max_t for j in range(a.n_jobs)]
+
         def call():
             """-> (hits per job, summed info, wall ms); every library call ends in a stream synchronise and the copy back"""
             t0 = time.perf_counter()
-            if a.share:
+            if a.leave == "bytes":                                               # (--thresholds: -> (tags, counts) per job in place of the hits)
+                from commet_amd.matrix_io import popcount
+                hits, info = ctx.index_many_and_profile([irs] * a.n_jobs, qrs, index_selects=sels, max_hits=ts)
+                tags = [commet_amd.tags_at(h, t) for h, t in zip(hits, ts)]
+                hits = (tags, [popcount(tg, qrs.num_reads) for tg in tags])
+            elif a.leave == "tags":
+                tags, shared, info = ctx.index_many_and_thresholds([irs] * a.n_jobs, qrs, index_selects=sels, t=ts)
+                hits = (tags, [int(sh.sum()) for sh in shared])
+            elif a.share:
                 hits, info = ctx.index_many_and_profile([irs] * a.n_jobs, qrs, index_selects=sels, max_hits=a.max_t)
             else:
                 hits, info = [], {}
@@ -181,8 +195,12 @@ def child_many(a):
         out["index_ms"] = [round(c[1]["index_ms"], 3) for c in calls]
         out["search_ms"] = [round(c[1]["search_ms"], 3) for c in calls]
         out["chunks"], out["search_launches"], out["reads_walked"] = int(info["n_chunks"]), int(info["search_launches"]), int(info["reads_scanned"])
-        out["found_per_job"] = [int((h > 0).sum()) for h in hits]
-        np.save(os.path.join(a.work, a.hits_name), np.stack(hits))
+        if a.leave:
+            out["found_per_job"] = hits[1]
+            np.save(os.path.join(a.work, a.hits_name), np.stack(hits[0]))
+        else:
+            out["found_per_job"] = [int((h > 0).sum()) for h in hits]
+            np.save(os.path.join(a.work, a.hits_name), np.stack(hits))
     print("RESULT " + json.dumps(out), flush=True)
 
 
@@ -206,6 +224,35 @@ def many_leg(a):
                      "search_launches": runs[name][0]["search_launches"], "reads_walked": runs[name][0]["reads_walked"], "kernels_ms": runs[name][0]["kernels_ms"]}
     out["shared_over_alone"] = round(out["shared"]["wall_ms"] / out["alone"]["wall_ms"], 4)
     out["found_per_job"] = runs["shared"][0]["found_per_job"]
+    return out
+
+
+def thresholds_leg(a):
+    """--thresholds: bytes + host thresholding against the thresholds call, fresh processes alternated"""
+    legs = [("bytes", ["--n-jobs", str(a.jobs), "--leave", "bytes"]), ("tags", ["--n-jobs", str(a.jobs), "--leave", "tags"])]
+    runs = {name: [] for name, _ in legs}
+    equal = []
+    for r in range(a.rounds):
+        for name, extra in legs:
+            runs[name].append(run_child(a, "many", "c1", a.limit, extra + ["--hits-name", f"thr_{name}.npy"]))
+            print(f"round {r} {name}: wall ms {runs[name][-1]['wall_ms']}", file=sys.stderr, flush=True)
+        equal.append(bool(np.array_equal(np.load(os.path.join(a.work, "thr_bytes.npy")), np.load(os.path.join(a.work, "thr_tags.npy")))
+                          and runs["bytes"][-1]["found_per_job"] == runs["tags"][-1]["found_per_job"]))
+    out = {"outputs_equal": all(equal), "runs": runs}
+    for name, _ in legs:
+        per = [med(c["wall_ms"]) for c in runs[name]]
+        dev = med([med(c["index_ms"]) + med(c["search_ms"]) for c in runs[name]])
+        k = runs[name][0]["kernels_ms"]
+        out[name] = {"wall_ms": round(med(per), 3), "rounds_wall_ms": per, "wall_ms_spread": round((max(per) - min(per)) / med(per), 4),
+                     "search_device_ms": round(dev, 3), "hits_tags_kernel": k.get("hits_tags_kernel"),
+                     "host_ms": round(med(per) - dev - (k.get("hits_tags_kernel") or [0, 0.0])[1], 3), "kernels_ms": k}
+    out["tags_over_bytes"] = round(out["tags"]["wall_ms"] / out["bytes"]["wall_ms"], 4)
+    # the kernel's traffic: every job's n bytes read once, n / 8 bytes of its one tag vector written
+    n, launches, ms = a.reads, *(out["tags"]["hits_tags_kernel"] or [0, 0.0])
+    if ms:
+        out["hits_tags_bytes_per_s"] = launches * (n + n / 8) / (ms * 1e-3)
+        out["hits_tags_share_of_8TBs"] = round(out["hits_tags_bytes_per_s"] / 8e12, 4)
+    out["found_per_job"] = runs["tags"][0]["found_per_job"]
     return out
 
 
@@ -294,6 +341,8 @@ def main():
     ap.add_argument("--jobs", type=int, default=0, help="N jobs on disjoint N-ths of set 0, all searching set 1: one by one against one many-job call")
     ap.add_argument("--n-jobs", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--share", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("--thresholds", action="store_true", help="with --jobs: many-job profile + host thresholding against the thresholds call")
+    ap.add_argument("--leave", default=None, choices=["bytes", "tags"], help=argparse.SUPPRESS)
     ap.add_argument("--long", action="store_true", help="with --jobs: on long-read search sets, multi_job = 1 against multi_job = 2")
     ap.add_argument("--long-workloads", nargs="+", default=["ragged_1k_10k", "len5500"], help="--long: workloads of tools/long_read_bench.py")
     ap.add_argument("--scale", type=float, default=1.0, help="--long: reads per set, as a share of the workload's")
@@ -373,6 +422,16 @@ def main():
         if a.jobs:
             if a.jobs < 2:
                 raise SystemExit("--jobs needs at least two jobs")
+            if a.thresholds:
+                m = thresholds_leg(a)
+                res = {"workload": f"2 x {a.reads} x {a.read_len} bp, k={a.k}, {a.jobs} jobs on disjoint parts of set 0, job j at t = 1 + j % {a.max_t}", "thresholds": m}
+                if a.out:
+                    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+                    open(a.out, "w").write(json.dumps(res) + "\n")
+                print(json.dumps({"workload": res["workload"], **{f: v for f, v in m.items() if f != "runs"}}), flush=True)
+                if not m["outputs_equal"]:
+                    raise SystemExit("the tags or counts of the two legs differ")
+                return
             m = many_leg(a)
             res = {"workload": f"2 x {a.reads} x {a.read_len} bp, k={a.k}, {a.jobs} jobs on disjoint parts of set 0, max_hits={a.max_t}", "many": m}
             if a.out:
