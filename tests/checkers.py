@@ -5,8 +5,7 @@ checker_job: one run of the restated tool (oracle_binding.index_and_search) over
 its .bv files say."""
 import os
 
-import numpy as np
-
+import every_k_sets as eks
 import oracle_binding as ob
 import util
 
@@ -14,28 +13,8 @@ import util
 def key_level_search(idx_reads, queries, k, t):
     """search_reads.h:45-83 over the CPU checker's KEYS (ok_keys_of_read: hash_key.h's add / rv_add per complete window) with the four
     lanes kept as Python sets — for k whose 2^(k-1)-byte filter the checker cannot allocate on a test host (k = 38: 128 GiB)"""
-    lanes = [set(), set(), set(), set()]
-    for r in idx_reads:
-        keys, _ = ob.keys_of_read(r, k)
-        for j in range(4):
-            lanes[j].update(keys[:, j].tolist())
-    out = np.zeros(len(queries), dtype=bool)
-    for i, q in enumerate(queries):
-        for rev in (False, True):
-            keys, pos = ob.keys_of_read(q, k, reverse=rev)
-            seen, next_end = 0, 0
-            for (a, b, c, d), p in zip(keys.tolist(), pos.tolist()):
-                if p < next_end:                       # hash.clear() after a hit: the next complete window ends k bases later
-                    continue
-                if a in lanes[0] and b in lanes[1] and c in lanes[2] and d in lanes[3]:
-                    seen += 1
-                    if seen >= t:
-                        out[i] = True
-                        break
-                    next_end = p + k
-            if out[i]:
-                break
-    return out
+    # the one statement of the rule is every_k_sets.key_level_job: here every index read in ONE filter (no chunk fills, no read dropped)
+    return eks.key_level_job(k, idx_reads, [queries], eks.ONE_CHUNK).tags(t)[0]
 
 
 def checker_job(d, k, t, index_reads, search_sets, max_kmer=0):
