@@ -23,6 +23,7 @@
 #include "host/fasta_source.hpp"
 #include "host/ingest_pack.hpp"
 #include "host/filter_rule.hpp"
+#include "host/devmem.hpp"
 
 #include <hip/hip_runtime.h>
 

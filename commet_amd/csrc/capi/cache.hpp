@@ -39,31 +39,22 @@ uint64_t shrink_query_lists(commet_ctx *c, uint64_t target, bool even_in_job)
     return freed;
 }
 
-// hipMalloc that gives the cached query lists back and tries once more when the device is out of memory
-hipError_t dev_alloc(commet_ctx *c, void **p, size_t bytes, bool job_thread)
+// hipMalloc that gives the cached query lists back and tries once more when the device is out of memory.  job_thread: the lists of the
+// running job's sets go too (shrink_query_lists, even_in_job).  ql_locked: the caller HOLDS ql_mu (build_query_list,
+// ensure_query_results) — the mutex is not taken again, and job_thread is then IGNORED: only the lists of sets outside the running job
+// go, whatever it says (the caller is about to use the job's own)
+hipError_t dev_alloc(commet_ctx *c, void **p, size_t bytes, bool job_thread, bool ql_locked = false)
 {
     hipError_t e = dm_malloc(p, bytes);
     if (e != hipErrorOutOfMemory) return e;
     (void) hipGetLastError();
     uint64_t freed;
     {
-        std::lock_guard<std::mutex> lk(c->ql_mu);
-        freed = shrink_query_lists(c, 0, job_thread);
+        std::unique_lock<std::mutex> lk(c->ql_mu, std::defer_lock);
+        if (!ql_locked) lk.lock();
+        freed = shrink_query_lists(c, 0, job_thread && !ql_locked);
     }
     if (!freed) return e;
-    e = dm_malloc(p, bytes);
-    if (e == hipErrorOutOfMemory) (void) hipGetLastError();
-    return e;
-}
-
-// the same for a caller that HOLDS ql_mu (build_query_list, ensure_query_results: dev_alloc would take the mutex again): the lists of
-// sets outside the running job are given back directly
-hipError_t dev_alloc_locked(commet_ctx *c, void **p, size_t bytes)
-{
-    hipError_t e = dm_malloc(p, bytes);
-    if (e != hipErrorOutOfMemory) return e;
-    (void) hipGetLastError();
-    if (!shrink_query_lists(c, 0, false)) return e;
     e = dm_malloc(p, bytes);
     if (e == hipErrorOutOfMemory) (void) hipGetLastError();
     return e;
@@ -84,7 +75,7 @@ int grow_kept(commet_ctx *c, T *&ptr, uint64_t &cap, uint64_t need, uint64_t all
     ptr = nullptr, cap = 0;
     void *p = nullptr;
     const size_t bytes = (size_t) alloc_elems * sizeof(T);
-    const hipError_t e = ql_locked ? dev_alloc_locked(c, &p, bytes) : dev_alloc(c, &p, bytes, true);
+    const hipError_t e = dev_alloc(c, &p, bytes, true, ql_locked);
     if (e != hipSuccess) {
         (void) hipGetLastError();
         return fail("cannot allocate %zu bytes of device memory: %s", bytes, hipGetErrorString(e));
@@ -144,11 +135,8 @@ uint64_t commet_device_pooled_bytes(int device)
 
 int commet_device_alloc_stats(int device, double *wait_ms, uint64_t *fresh_bytes, uint64_t *calls)
 {
-    uint64_t ns = 0, by = 0, n = 0;
-    for (int d = 0; d < 16; ++d) {
-        if (device >= 0 && d != device) continue;
-        ns += g_devmem.drv_ns[d].load(), by += g_devmem.drv_bytes[d].load(), n += g_devmem.drv_calls[d].load();
-    }
+    uint64_t ns, by, n;
+    g_devmem.driver_stats(device, &ns, &by, &n);
     if (wait_ms) *wait_ms = (double) ns * 1e-6;
     if (fresh_bytes) *fresh_bytes = by;
     if (calls) *calls = n;
@@ -157,16 +145,12 @@ int commet_device_alloc_stats(int device, double *wait_ms, uint64_t *fresh_bytes
 
 void commet_device_alloc_refuse(uint64_t at_least_bytes, uint64_t nth)
 {
-    g_devmem.refuse_at_least = 0, g_devmem.refuse_nth = 0;       // (nothing is refused while the numbers restart)
-    g_devmem.requests = 0, g_devmem.refused = 0, g_devmem.last_refused_bytes = 0;
-    g_devmem.refuse_at_least = at_least_bytes, g_devmem.refuse_nth = nth;
+    g_devmem.refuse(at_least_bytes, nth);
 }
 
 void commet_device_alloc_requests(uint64_t *requests, uint64_t *refused, uint64_t *last_refused_bytes)
 {
-    if (requests) *requests = g_devmem.requests.load();
-    if (refused) *refused = g_devmem.refused.load();
-    if (last_refused_bytes) *last_refused_bytes = g_devmem.last_refused_bytes.load();
+    g_devmem.requests(requests, refused, last_refused_bytes);
 }
 
 int commet_cache_stats(commet_ctx *c, uint64_t *bytes, uint64_t *budget_bytes, uint64_t *evictions)

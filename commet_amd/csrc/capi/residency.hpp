@@ -19,7 +19,7 @@ uint64_t set_device_bytes(uint64_t max_reads, uint64_t max_bases)
     const uint64_t triples = (max_bases >> 5) + max_reads + 1, bw = bitmap_words(max_reads);
     const uint64_t sizes[7] = {triples * 12, (max_reads + 1) * 8, (max_reads + 1) * 4, 8 * 4, bw * 8, bw * 8, bw * 8};
     uint64_t total = 0;
-    for (uint64_t b : sizes) total += g_devmem.enabled() ? dm_size_class((size_t) b) : b;
+    for (uint64_t b : sizes) total += g_devmem.request_bytes((size_t) b);
     return total;
 }
 

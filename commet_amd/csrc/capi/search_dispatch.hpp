@@ -397,6 +397,9 @@ bool tq_geometry_ok(const commet_ctx *c, const commet_readset *rs, int64_t windo
 // (rs->fhw_total: the set's first-hit windows summed over its reads — n x first_hit_windows for reads of one length, less for ragged sets)
 bool tiled_geometry_ok(const commet_ctx *c, const commet_readset *rs) { return tq_geometry_ok(c, rs, first_hit_windows(c, rs), rs->fhw_total); }
 
+// the memory of the set's list was set aside (commet_readset_reserve_cache) and no trim since has given it back: the blocks are still filed
+bool list_set_aside(const commet_readset *rs) { return rs->ql_reserved.load() && rs->ql_reserved_at.load() == g_devmem.trims(); }
+
 bool tiled_ok(const commet_ctx *c, const commet_readset *rs, int g)
 {
     if (c->tiled_mode == 1 || c->count_probes || rs->ql.failed) return false;
@@ -406,8 +409,7 @@ bool tiled_ok(const commet_ctx *c, const commet_readset *rs, int g)
     // against the fused kernels: configs[1] search 9.4 -> 8.6 ms, configs[2] jobs 1.92-1.96 -> 1.84 s.
     const uint64_t est = rs->fhw_total * 8;
     // (a list above the cap when its memory was set aside beforehand, commet_readset_reserve_cache: the allocation is then not on this job's path)
-    const bool set_aside = rs->ql_reserved.load() && rs->ql_reserved_at.load() == g_devmem.trims.load();   // (no trim since: the blocks are still filed)
-    if (rs->n_reads < (1ull << 20) || (est > c->ql_max_list && !set_aside)) return false;
+    if (rs->n_reads < (1ull << 20) || (est > c->ql_max_list && !list_set_aside(rs))) return false;
     // A list of more than 4 GiB (sets of 15 M reads and up) is built for a set's SECOND such scan: a set that is scanned once —
     // every target of a rank that holds few pairs of a large matrix — would pay 12 ms of kernels and an 11 GB allocation for a
     // 7.6 ms gain (one J2 / J3 job of configs[3]: 54.7 against 62.3 ms), a set that is scanned again and again — every set of a
@@ -435,7 +437,7 @@ int build_query_list(commet_ctx *c, const commet_readset *rs, int t, commet_read
     // buffer kept with the context (a hipFree would wait for the index build).
     hipStream_t ls = c->list_stream;
     // (the caller holds ql_mu: on an allocation failure here the other sets' lists are given back directly)
-    auto alloc = [&](void **ptr, size_t bytes) { return dev_alloc_locked(c, ptr, bytes); };
+    auto alloc = [&](void **ptr, size_t bytes) { return dev_alloc(c, ptr, bytes, true, true); };
     hipError_t e = alloc((void **) &ql.d_tile_off, (entries + 1) * sizeof(unsigned long long));
     // (grows a few times in a context's life)
     if (e == hipSuccess && grow_kept(c, c->d_ql_totals, c->ql_totals_cap, (uint64_t) nb + 1, (uint64_t) nb + 1, true)) e = hipErrorOutOfMemory;
@@ -773,12 +775,11 @@ int commet_readset_reserve_cache(commet_ctx *c, const commet_readset *rs)
     uint64_t b[6];
     {
         std::lock_guard<std::mutex> lk(c->ql_mu);
-        const bool still = rs->ql_reserved.load() && rs->ql_reserved_at.load() == g_devmem.trims.load();
-        if (rs->ql.built || still || !g_devmem.enabled() || !query_list_blocks(c, rs, b)) return 0;
+        if (rs->ql.built || list_set_aside(rs) || !g_devmem.enabled() || !query_list_blocks(c, rs, b)) return 0;
     }
     for (int i = 0; i < 6; ++i)
         if (b[i] && dm_reserve((size_t) b[i]) != hipSuccess) return 0;      // no room: the set keeps the cap's rule
-    rs->ql_reserved_at.store(g_devmem.trims.load());
+    rs->ql_reserved_at.store(g_devmem.trims());
     rs->ql_reserved.store(true);
     return 0;
 }

@@ -60,333 +60,58 @@ decltype(auto) with_value(T v, F &&f)
     }
 }
 
-// ---- device memory kept for reuse ----------------------------------------------------------------------------------------
-// On this driver a hipMalloc of GBs costs 15-30 ms per GiB on some boxes (and ~0 on others: tools/exp/alloc_cost*.hip — where a
-// 16 GiB hipMalloc took 483 ms, and 965 ms again after its hipFree, sixteen of 1 GiB took 0.3 ms and a hipMallocAsync of 16 GiB
-// 14 ms), and one that follows the hipFree of tens of GB now and then blocks for 50-150 ms (seen up to 2 s): a context created after another one was closed, a query list built after one was dropped, a
-// workspace that grows — all of them on some job's path (bench.py's configs[2] leg behind the headline: 1.50 s of device time
-// against 1.15 s in a fresh process, the difference being the GPU idling behind such calls; profiles/r05_c2_variance).  So the
-// library never gives a block of 8 MiB or more back while the process lives: dm_free waits for the device, as hipFree does (its
-// callers count on that), and files the block; dm_malloc takes the smallest filed block of the current device that is large enough
-// and at most a quarter larger, else asks hipMalloc — and when hipMalloc is out of memory, everything filed is given back and
-// it is asked once more.  Blocks are never split (an exported set's IPC handle must be that of a whole allocation).
-// COMMET_DEVMEM_POOL=1 (off by default): a new block of 256 MiB or more comes from hipMallocAsync on a stream of the cache's own,
-// drained before the block is handed out — 0.4-0.9 ms per GiB on either kind of box in isolation, but on a box whose hipMalloc
-// is free anyway the 10-set matrix of bench.py took 12.7 s with it against 10.9 s without (device time +4 %: kernels gather more
-// slowly from pool memory; the loader thread's waits 1.5 s against 0.6 s; profiles/r05_pool), and the box of the other kind has
-// not come up again to be measured.  No IPC handle can be had for such a block, so commet_readset_export first moves a set's
-// planes into a hipMalloc block (dm_make_shareable).
-// At most half the device (COMMET_DEVMEM_CACHE_GB) is kept, the largest blocks going first; commet_device_cache_trim gives all of
-// it back.  COMMET_DEVMEM_CACHE=0: plain hipMalloc / hipFree.
-struct DevMemCache {
-    struct Block {
-        int device;
-        size_t bytes;                                              // as allocated
-        bool pooled;                                               // from hipMallocAsync (no IPC handle can be had for it)
-    };
-    std::mutex mu;
-    std::map<void *, Block> live;                                  // blocks handed out
-    std::multimap<size_t, std::pair<void *, bool>> filed[16];      // per device, by size: pointer, pooled
-    size_t filed_bytes[16] = {0};
-    size_t cap[16] = {0};                                          // bytes kept at most per device (COMMET_DEVMEM_CACHE_GB; default: half the device)
-    hipStream_t pool_stream[16] = {nullptr};                       // the stream the stream-ordered allocations are ordered on (always drained before use)
-    int on = -1, pool_on = -1;
-    size_t pool_min = 0;                                           // COMMET_DEVMEM_POOL_MIN_MB (tests: a set of a few MB in pooled blocks); never below 8 MiB
-    // what the DRIVER was asked for, per device (commet_device_alloc_stats): time the calling thread spent inside hipMalloc /
-    // hipMallocAsync, bytes and calls — a box that charges for a process's first use of device memory shows here, not in kernel time
-    std::atomic<uint64_t> drv_ns[16], drv_bytes[16], drv_calls[16];
-    std::atomic<uint64_t> trims{0};                                // times filed blocks went back to the driver (dm_trim): what was set aside before is gone
-    // test hook (commet_device_alloc_refuse; off = 0, 0): dm_malloc refuses a request of refuse_at_least bytes or more, and the
-    // refuse_nth request since arming (once), as the driver does when it is out of memory; what dm_malloc saw since arming
-    std::atomic<uint64_t> refuse_at_least{0}, refuse_nth{0};
-    std::atomic<uint64_t> requests{0}, refused{0}, last_refused_bytes{0};
-    DevMemCache()
+// ---- device memory kept for reuse: the cache of host/devmem.hpp (why, and its rules, there) over the HIP runtime ----------------------
+struct HipDriver {
+    using Err = hipError_t;
+    using Stream = hipStream_t;
+    static constexpr Err ok = hipSuccess, oom = hipErrorOutOfMemory;
+    static Err cleared(Err e)                                        // an error answered is HIP's last error no longer
     {
-        for (int d = 0; d < 16; ++d) drv_ns[d] = 0, drv_bytes[d] = 0, drv_calls[d] = 0;
+        if (e != hipSuccess) (void) hipGetLastError();
+        return e;
     }
-    bool enabled()
+    Err current(int *dev) { return hipGetDevice(dev); }
+    void set_device(int dev) { (void) hipSetDevice(dev); }
+    Err alloc(void **p, size_t bytes) { return cleared(hipMalloc(p, bytes)); }
+    Err free(void *p) { return hipFree(p); }
+    Stream new_stream()
     {
-        if (on < 0) {
-            const char *e = getenv("COMMET_DEVMEM_CACHE");
-            on = !(e && atoi(e) == 0);
-        }
-        return on != 0;
+        Stream st = nullptr;
+        return cleared(hipStreamCreateWithFlags(&st, hipStreamNonBlocking)) == hipSuccess ? st : nullptr;
     }
-    int verb = -1;
-    bool verbose()                                                 // COMMET_DEVMEM_VERBOSE=1: one line on stderr per block asked from or returned to the driver
+    Err pool_alloc(void **p, size_t bytes, Stream st)
     {
-        if (verb < 0) {
-            const char *e = getenv("COMMET_DEVMEM_VERBOSE");
-            verb = e && atoi(e) != 0;
-        }
-        return verb != 0;
+        const Err e = hipMallocAsync(p, bytes, st);
+        return cleared(e == hipSuccess ? hipStreamSynchronize(st) : e);
     }
-    bool pooling()
+    void pool_free(void *p, Stream st) { (void) hipFreeAsync(p, st), (void) hipStreamSynchronize(st); }
+    void pool_trim(int dev)
     {
-        if (pool_on < 0) {
-            const char *e = getenv("COMMET_DEVMEM_POOL");
-            pool_on = e && atoi(e) != 0;
-            const char *m = getenv("COMMET_DEVMEM_POOL_MIN_MB");
-            pool_min = m ? std::max<size_t>((size_t) atoll(m) << 20, (size_t) 8 << 20) : (size_t) 256 << 20;
-        }
-        return pool_on != 0;
-    }
-};
-DevMemCache g_devmem;
-constexpr size_t DEVMEM_MIN_FILED = (size_t) 8 << 20;
-
-// one block from the driver: stream-ordered from 256 MiB on unless an IPC handle will be asked for it
-hipError_t dm_driver_alloc_untimed(void **p, size_t bytes, int dev, bool shareable, bool *pooled);
-hipError_t dm_driver_alloc(void **p, size_t bytes, int dev, bool shareable, bool *pooled)
-{
-    const auto t0 = std::chrono::steady_clock::now();
-    const hipError_t e = dm_driver_alloc_untimed(p, bytes, dev, shareable, pooled);
-    if (dev >= 0 && dev < 16) {
-        g_devmem.drv_ns[dev] += (uint64_t) std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
-        g_devmem.drv_calls[dev] += 1;
-        if (e == hipSuccess) g_devmem.drv_bytes[dev] += bytes;
-    }
-    return e;
-}
-hipError_t dm_driver_alloc_untimed(void **p, size_t bytes, int dev, bool shareable, bool *pooled)
-{
-    *pooled = false;
-    if (!shareable && g_devmem.pooling() && bytes >= g_devmem.pool_min) {
-        hipStream_t st;
-        {
-            std::lock_guard<std::mutex> lk(g_devmem.mu);
-            if (!g_devmem.pool_stream[dev] && hipStreamCreateWithFlags(&g_devmem.pool_stream[dev], hipStreamNonBlocking) != hipSuccess) {
-                (void) hipGetLastError();
-                g_devmem.pool_stream[dev] = nullptr;
-            }
-            st = g_devmem.pool_stream[dev];
-        }
-        if (st) {
-            hipError_t e = hipMallocAsync(p, bytes, st);
-            if (e == hipSuccess) e = hipStreamSynchronize(st);
-            if (e == hipSuccess) {
-                *pooled = true;
-                return e;
-            }
-            if (e != hipErrorOutOfMemory) (void) hipGetLastError();     // (not supported here, ...: the plain call below)
-            else return e;
-        }
-    }
-    return hipMalloc(p, bytes);
-}
-
-void dm_driver_free(void *q, int dev, bool pooled)
-{
-    if (!pooled) {
-        (void) hipFree(q);
-        return;
-    }
-    hipStream_t st = g_devmem.pool_stream[dev];
-    (void) hipFreeAsync(q, st);
-    (void) hipStreamSynchronize(st);
-}
-
-// gives every filed block of `device` (-1: all) back to the driver; returns the bytes released
-size_t dm_trim(int device)
-{
-    g_devmem.trims += 1;
-    std::vector<std::pair<int, std::pair<void *, bool>>> drop;
-    size_t bytes = 0;
-    {
-        std::lock_guard<std::mutex> lk(g_devmem.mu);
-        for (int d = 0; d < 16; ++d) {
-            if (device >= 0 && d != device) continue;
-            for (auto &b : g_devmem.filed[d]) drop.push_back({d, b.second}), bytes += b.first;
-            g_devmem.filed[d].clear();
-            g_devmem.filed_bytes[d] = 0;
-        }
-    }
-    bool any_pooled = false;
-    for (auto &q : drop) dm_driver_free(q.second.first, q.first, q.second.second), any_pooled |= q.second.second;
-    if (any_pooled) {                                              // the pool itself keeps nothing either
         int cur = 0;
+        hipMemPool_t pool;
         const bool have = hipGetDevice(&cur) == hipSuccess;
-        for (int d = 0; d < 16; ++d) {
-            if ((device >= 0 && d != device) || !g_devmem.pool_stream[d]) continue;
-            hipMemPool_t pool;
-            if (hipSetDevice(d) == hipSuccess && hipDeviceGetDefaultMemPool(&pool, d) == hipSuccess) (void) hipMemPoolTrimTo(pool, 0);
-        }
+        if (hipSetDevice(dev) == hipSuccess && hipDeviceGetDefaultMemPool(&pool, dev) == hipSuccess) (void) hipMemPoolTrimTo(pool, 0);
         if (have) (void) hipSetDevice(cur);
         (void) hipGetLastError();
     }
-    return bytes;
-}
-
-size_t dm_filed_bytes(int device)
-{
-    std::lock_guard<std::mutex> lk(g_devmem.mu);
-    return device >= 0 && device < 16 ? g_devmem.filed_bytes[device] : 0;
-}
-
-size_t dm_pooled_bytes(int device)
-{
-    std::lock_guard<std::mutex> lk(g_devmem.mu);
-    size_t n = 0;
-    for (auto &b : g_devmem.live)
-        if (b.second.device == device && b.second.pooled) n += b.second.bytes;
-    return n;
-}
-
-// Size classes: a block of 8 MiB or more is asked for in steps of 1/16 .. 1/32 of its size (a request of 8.5 GB becomes one of 8.6 GB).
-// The objects a context makes — scatter workspaces sized by a chunk's k-mer count, a set's planes, a query list — come out a few
-// hundred bytes apart from one set to the next; filed under their exact sizes, a block that was 100 bytes short served nobody and
-// the next context asked the driver for the same 17 GB again (the first process on a box that charges for fresh device memory pays
-// 30 ms per GiB for that, DESIGN section 4: bench.py's matrix legs, commet_device_alloc_stats).
-inline size_t dm_size_class(size_t bytes)
-{
-    if (bytes < DEVMEM_MIN_FILED) return bytes;
-    const int lg = 63 - __builtin_clzll((unsigned long long) bytes);
-    const size_t granule = (size_t) 1 << (lg - 4);
-    return (bytes + granule - 1) & ~(granule - 1);
-}
-
-// `shareable`: the block may be exported to another process (commet_readset_export), so it comes from hipMalloc
-hipError_t dm_malloc(void **p, size_t bytes, bool shareable = false)
-{
-    *p = nullptr;
-    {   // the refusal hook: the caller's byte count, before anything else; a refusal touches nothing but the hook's own numbers
-        const uint64_t n = g_devmem.requests.fetch_add(1, std::memory_order_relaxed) + 1;
-        const uint64_t at_least = g_devmem.refuse_at_least.load(std::memory_order_relaxed), nth = g_devmem.refuse_nth.load(std::memory_order_relaxed);
-        if ((at_least && bytes >= at_least) || (nth && n == nth)) {
-            g_devmem.refused.fetch_add(1, std::memory_order_relaxed);
-            g_devmem.last_refused_bytes.store(bytes, std::memory_order_relaxed);
-            return hipErrorOutOfMemory;
-        }
-    }
-    if (g_devmem.enabled()) bytes = dm_size_class(bytes);
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return hipMalloc(p, bytes);
-    if (!g_devmem.enabled()) {
-        const auto t0 = std::chrono::steady_clock::now();
-        const hipError_t e = hipMalloc(p, bytes);
-        g_devmem.drv_ns[dev] += (uint64_t) std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
-        g_devmem.drv_calls[dev] += 1;
-        if (e == hipSuccess) g_devmem.drv_bytes[dev] += bytes;
-        return e;
-    }
-    if (bytes >= DEVMEM_MIN_FILED) {
-        std::lock_guard<std::mutex> lk(g_devmem.mu);
-        for (auto it = g_devmem.filed[dev].lower_bound(bytes); it != g_devmem.filed[dev].end() && it->first <= bytes + bytes / 4; ++it) {
-            if (shareable && it->second.second) continue;
-            *p = it->second.first;
-            g_devmem.filed_bytes[dev] -= it->first;
-            g_devmem.live[*p] = {dev, it->first, it->second.second};
-            g_devmem.filed[dev].erase(it);
-            return hipSuccess;
-        }
-    }
-    bool pooled = false;
-    if (g_devmem.verbose()) {
-        std::lock_guard<std::mutex> lk(g_devmem.mu);
-        fprintf(stderr, "[devmem] driver alloc %.1f MiB (filed: %.1f GiB in %zu blocks)\n", bytes / 1048576.0, g_devmem.filed_bytes[dev] / 1073741824.0, g_devmem.filed[dev].size());
-    }
-    hipError_t e = dm_driver_alloc(p, bytes, dev, shareable, &pooled);
-    if (e == hipErrorOutOfMemory && dm_trim(dev)) {
-        (void) hipGetLastError();
-        e = dm_driver_alloc(p, bytes, dev, shareable, &pooled);
-    }
-    if (e == hipSuccess && bytes >= DEVMEM_MIN_FILED) {
-        std::lock_guard<std::mutex> lk(g_devmem.mu);
-        g_devmem.live[*p] = {dev, bytes, pooled};
-    }
-    return e;
-}
-
-// a block of `bytes` asked from the driver NOW and filed at once, for an allocation that will come later on some job's path (a helper
-// thread pays the driver's price instead of the job thread); never taken from the filed blocks themselves
-hipError_t dm_reserve(size_t bytes)
-{
-    if (!g_devmem.enabled() || bytes < DEVMEM_MIN_FILED) return hipSuccess;
-    bytes = dm_size_class(bytes);
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return hipErrorInvalidDevice;
-    void *p = nullptr;
-    bool pooled = false;
-    const hipError_t e = dm_driver_alloc(&p, bytes, dev, false, &pooled);
-    if (e != hipSuccess) {
-        (void) hipGetLastError();
-        return e;
-    }
-    std::lock_guard<std::mutex> lk(g_devmem.mu);
-    g_devmem.filed[dev].emplace(bytes, std::make_pair(p, pooled));
-    g_devmem.filed_bytes[dev] += bytes;
-    return hipSuccess;
-}
-
-hipError_t dm_free(void *p)
-{
-    if (!p) return hipSuccess;
-    if (g_devmem.enabled()) {
-        DevMemCache::Block what{-1, 0, false};
-        {
-            std::lock_guard<std::mutex> lk(g_devmem.mu);
-            auto it = g_devmem.live.find(p);
-            if (it != g_devmem.live.end()) what = it->second, g_devmem.live.erase(it);
-        }
-        if (what.device >= 0) {
-            const int d = what.device;
-            int cur = d;
-            const bool have_cur = hipGetDevice(&cur) == hipSuccess;
-            if (have_cur && cur != d) (void) hipSetDevice(d);      // (the block's device, whatever device the calling thread is on)
-            (void) hipDeviceSynchronize();                         // what hipFree does: no kernel still reads the block when somebody else gets it
-            std::vector<std::pair<void *, bool>> over;             // kept within the cap (other processes may share the device): largest first
-            {
-                std::lock_guard<std::mutex> lk(g_devmem.mu);
-                g_devmem.filed[d].emplace(what.bytes, std::make_pair(p, what.pooled));
-                g_devmem.filed_bytes[d] += what.bytes;
-                if (!g_devmem.cap[d]) {
-                    size_t fr = 0, tot = 0;
-                    const char *e = getenv("COMMET_DEVMEM_CACHE_GB");
-                    if (e) g_devmem.cap[d] = (size_t) (std::max(0.0, atof(e)) * (double) (1ull << 30)) + 1;
-                    else g_devmem.cap[d] = hipMemGetInfo(&fr, &tot) == hipSuccess ? tot / 2 : (size_t) 64 << 30;
-                }
-                while (g_devmem.filed_bytes[d] > g_devmem.cap[d] && !g_devmem.filed[d].empty()) {
-                    auto last = std::prev(g_devmem.filed[d].end());
-                    over.push_back(last->second);
-                    g_devmem.filed_bytes[d] -= last->first;
-                    g_devmem.filed[d].erase(last);
-                }
-            }
-            if (!over.empty() && g_devmem.verbose()) fprintf(stderr, "[devmem] over the cap of %.1f GiB: %zu block(s) back to the driver\n", g_devmem.cap[d] / 1073741824.0, over.size());
-            for (auto &q : over) dm_driver_free(q.first, d, q.second);
-            if (have_cur && cur != d) (void) hipSetDevice(cur);
-            return hipSuccess;
-        }
-    }
-    return hipFree(p);
-}
-
-// the block at *p made exportable: one that came from the stream-ordered pool is copied into a hipMalloc block of its own (the
-// device drained first; the caller sees to it that no other host thread uses the block meanwhile) and filed
-hipError_t dm_make_shareable(void **p)
-{
-    if (!*p) return hipSuccess;
-    DevMemCache::Block what{-1, 0, false};
+    Err sync() { return hipDeviceSynchronize(); }
+    size_t total_bytes()
     {
-        std::lock_guard<std::mutex> lk(g_devmem.mu);
-        auto it = g_devmem.live.find(*p);
-        if (it != g_devmem.live.end()) what = it->second;
+        size_t fr = 0, tot = 0;
+        return hipMemGetInfo(&fr, &tot) == hipSuccess ? tot : (size_t) 128 << 30;   // (not known: as a device of 128 GiB)
     }
-    if (what.device < 0 || !what.pooled) return hipSuccess;
-    void *q = nullptr;
-    hipError_t e = dm_malloc(&q, what.bytes, true);
-    if (e != hipSuccess) return e;
-    e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = hipMemcpy(q, *p, what.bytes, hipMemcpyDeviceToDevice);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) {
-        (void) dm_free(q);
-        return e;
-    }
-    (void) dm_free(*p);
-    *p = q;
-    return hipSuccess;
-}
+    Err copy(void *dst, const void *src, size_t bytes) { return hipMemcpy(dst, src, bytes, hipMemcpyDeviceToDevice); }
+};
+HipDriver g_hip_driver;
+DevMemCache<HipDriver> g_devmem(g_hip_driver);
+
+hipError_t dm_malloc(void **p, size_t bytes, bool shareable = false) { return g_devmem.malloc(p, bytes, shareable); }
+hipError_t dm_free(void *p) { return g_devmem.free(p); }
+hipError_t dm_reserve(size_t bytes) { return g_devmem.reserve(bytes); }
+hipError_t dm_make_shareable(void **p) { return g_devmem.make_shareable(p); }
+size_t dm_trim(int device) { return g_devmem.trim(device); }
+size_t dm_filed_bytes(int device) { return g_devmem.filed_bytes(device); }
+size_t dm_pooled_bytes(int device) { return g_devmem.pooled_bytes(device); }
 
 int fail(const char *fmt, ...)
 {
@@ -691,7 +416,7 @@ struct commet_readset {
     mutable LenSeg len_seg[5];
     mutable int n_len_seg = 0;
     mutable uint32_t ql_wanted = 0;                 // scans that would have taken the tiled search had the set's (large) list existed (tiled_ok)
-    mutable std::atomic<uint64_t> ql_reserved_at{0};  // g_devmem.trims when the memory was set aside: a trim since then has given it back
+    mutable std::atomic<uint64_t> ql_reserved_at{0};  // g_devmem.trims() when the memory was set aside: a trim since then has given it back
     mutable std::atomic<bool> ql_reserved{false};   // the memory of the set's list waits in the library's device cache (commet_readset_reserve_cache): a list above the cap may be built
     mutable int in_job = 0;                         // calls that are using the set now (a depth: commet_index_many_and_search nests commet_index_and_search); written under
                                                     // ql_mu (SetUse below).  While it is not 0 the set's list stays, and the set is neither exported nor offloaded

@@ -1,5 +1,5 @@
 """Every no-room fallback of the library, run: device allocations refused on request (commet_device_alloc_refuse, the hook at the top
-of dm_malloc, capi/state.hpp) on small shapes, every result against the CPU checker on the same reads.
+of dm_malloc: DevMemCache::malloc, host/devmem.hpp) on small shapes, every result against the CPU checker on the same reads.
 
 "Out of device memory costs speed, never correctness" is promised at more than a dozen sites (the slot ladder 8 -> 4 -> 1 of
 run_slot_groups, ensure_slots' "only the g needed now", wide rows -> narrow tables -> slot loop, rerun_alone_no_room of
