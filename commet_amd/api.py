@@ -344,6 +344,22 @@ class Context:
                                                                (C.c_int * max(nj, 1))(*ts), _ptrs(tags), _ptrs(shared), C.byref(info)))
         return tags, shared, _info_dict(info)
 
+    def index_and_search_relative(self, index_rs, search_sets, index_select=None, search_selects=None, percent=50, min_hits=1):
+        """commet_index_and_search_relative: the chunk loop with a threshold per read, t_r = max(min_hits, ceil(percent / 100 x W_r)),
+        W_r = len // k the most non-overlapping k-mers the read can hold (relative.thresholds is the rule in numpy).  A read is found
+        when one chunk filter holds t_r of its non-overlapping k-mers on one strand; a read with t_r > W_r never is.  Returns (tags,
+        shared, info): tags[s] = the BooleanVector bytes of search set s, shared[s] = np.uint64 per file of set s, both made on the
+        device.  The context's own t is not used.  Where every read gets the same t_r the result is index_and_search's at that t."""
+        ns = len(search_sets)
+        isel = _as_bits(index_select, index_rs.num_reads, "index_select")
+        ssel = _selections(search_selects, search_sets, "search_select")
+        tags = [np.zeros(bits_nbytes(rs.num_reads), dtype=np.uint8) for rs in search_sets]
+        shared = [np.zeros(rs.num_files, dtype=np.uint64) for rs in search_sets]
+        info = _l.JobInfo()
+        self._check(self._lib.commet_index_and_search_relative(self._h, index_rs._h, _ptr(isel), ns, _handles(search_sets), _ptrs(ssel),
+                                                               int(percent), int(min_hits), _ptrs(tags), _ptrs(shared), C.byref(info)))
+        return tags, shared, _info_dict(info)
+
     def poison(self, byte):
         """test hook: every bit array of the context (filter slots, interleaved A planes, bit-sliced planes and tables) filled with `byte`"""
         self.set_option("poison", byte)
@@ -464,6 +480,13 @@ class ReadSet:
         self._check(self._lib.commet_readset_filter(self._ctx._h, self._h, int(min_len), -1 if max_n is None else int(max_n),
                                                     float(min_shannon), -1 if max_reads is None else int(max_reads), _ptr(bits), st))
         return bits, [{f: int(getattr(st[i], f)) for f, _ in _l.FilterStats._fields_} for i in range(nf)]
+
+    def relative_thresholds(self, percent, min_hits=1):
+        """commet_readset_relative_thresholds: np.uint16 per read, the threshold index_and_search_relative gives it under no selection
+        (relative.thresholds is the same rule in numpy); 0 where the read cannot hold that many non-overlapping k-mers"""
+        out = np.zeros(self.num_reads, dtype=np.uint16)
+        self._check(self._lib.commet_readset_relative_thresholds(self._ctx._h, self._h, int(percent), int(min_hits), _ptr(out)))
+        return out
 
     def file_reads(self):
         return [int(self._lib.commet_readset_file_reads(self._h, i)) for i in range(self.num_files)]

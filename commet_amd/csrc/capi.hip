@@ -12,6 +12,7 @@
 #include "long_search.hpp"
 #include "hit_profile.hpp"
 #include "hit_profile_group.hpp"
+#include "relative_search.hpp"
 #include "hit_profile_jobs.hpp"
 #include "hit_profile_wide.hpp"
 #include "hit_profile_sliced.hpp"
@@ -67,6 +68,7 @@
 #include "capi/multi.hpp"            // commet_index_many_and_search: several jobs on one search set, their filters in one pass
 #include "capi/thresholds.hpp"       // what a profile call leaves of its byte arrays: bytes, or tags and per-file counts (hits_tags_kernel); commet_hits_to_tags
 #include "capi/profile.hpp"          // commet_index_and_profile: per-read hit counts, the tags of every t from one job
+#include "capi/relative.hpp"         // commet_index_and_search_relative: a threshold per read, a share of the k-mers it can hold
 #include "capi/multi_profile.hpp"    // commet_index_many_and_profile: several profile jobs on one search set, their filters in one hits pass
 #include "capi/options.hpp"          // commet_set_option, measurement hooks
 #include "capi/microbench.hpp"       // commet_membench / _ldsbench

@@ -121,6 +121,7 @@ void commet_destroy(commet_ctx *c)
     (void) dm_free(c->d_mtags);
     (void) dm_free(c->d_hits);
     (void) dm_free(c->d_twords);
+    (void) dm_free(c->d_thr);
     c->sel_ids.release(), c->sel_ids2.release(), c->act_ids.release();
     c->part[0].release();
     c->part[1].release();

@@ -147,8 +147,17 @@ int try_hits_tiled(commet_ctx *c, const commet_readset *rs, int g, bool sparse, 
     return launch_hits_tiled(c, rs, l, g, max_hits, d_sel, d_hits, d_walked) ? 2 : 0;
 }
 
+// the list of a pass of search set s that walks few of the set's reads (sparse_pass; no tags: a read that needs no walk is skipped by
+// the kernel itself), for hits_pass below and rel_pass (relative.hpp).  Empty: the pass is not sparse, or no room (the bitmap form)
+ActiveList hits_pass_list(JobRun &j, int s, bool sparse)
+{
+    ActiveList al{nullptr, nullptr};
+    if (sparse && build_active_list(j.c, j.search_rs[s], j.sel_of(s), nullptr, j.visited[s], &al)) al = ActiveList{nullptr, nullptr};
+    return al;
+}
+
 // search set s against the g chunk filters in slots 0 .. g - 1: the tiled profile where it applies; else the gather kernels, a pass
-// over few of the set's reads walking their list (sparse_pass; no tags: a saturated read is skipped by the kernel itself)
+// over few of the set's reads walking their list
 int hits_pass(JobRun &j, int s, int g, int gs, int max_hits, uint8_t *d_hits, unsigned long long *d_walked)
 {
     commet_ctx *c = j.c;
@@ -162,9 +171,7 @@ int hits_pass(JobRun &j, int s, int g, int gs, int max_hits, uint8_t *d_hits, un
         if (rs->n_reads) ++j.n_search_launches;
         return 0;
     }
-    ActiveList al{nullptr, nullptr};
-    if (sparse && build_active_list(c, rs, sel_s, nullptr, j.visited[s], &al))
-        al = ActiveList{nullptr, nullptr};         // (no room: the bitmap form)
+    const ActiveList al = hits_pass_list(j, s, sparse);
     if (launch_hits(c, rs, g, gs, max_hits, sel_s, d_hits, d_walked, al, j.visited[s])) return 1;
     if (rs->n_reads) ++j.n_search_launches;
     return 0;
@@ -258,43 +265,78 @@ struct ProfileWant {
     uint64_t *const *shared_out = nullptr;
 };
 
+// The frame of a job that keeps a byte per read of its search sets in c->d_hits — the profile job below, and the relative search
+// (relative.hpp), whose bytes are found flags: open() checks, plans and zeroes; the caller runs its passes over the slot groups;
+// close() queues what the call leaves, drains and accounts.  Each set's bytes start on a 256-byte line, at[s]
+struct BytesJob {
+    commet_ctx *c;
+    JobRun j;
+    SetUse in_job;                                 // offload / export cannot take a set mid-call
+    std::vector<uint64_t> at;
+    uint64_t n_bytes = 0;
+    unsigned long long *d_walked = nullptr;        // the count of walked reads
+    BytesJob(commet_ctx *c_, const commet_readset *index_rs, int n_search, const commet_readset *const *search_rs)
+        : c(c_), j(c_, index_rs, n_search, search_rs), in_job(c_, index_rs), at((size_t) n_search + 1, 0)
+    {
+    }
+    uint8_t *bytes_of(int s) const { return c->d_hits + at[(size_t) s]; }
+    // the slot loop's group cap, a rule of its own (no group8_ok condition: the hits kernels keep no masks)
+    int group_cap() const { return (c->k >= 2 && j.n_chunks() >= 2) ? std::max(1, std::min(8, c->chunk_group)) : 1; }
+
+    int open(const uint8_t *index_select, const uint8_t *const *search_select, bool want_times)
+    {
+        const int n_search = j.n_search;
+        if (validate_job(c, j.index_rs, n_search, j.search_rs)) return 1;
+        HIP_OK(hipSetDevice(c->device));
+        for (int s = 0; s < n_search; ++s) in_job.add(j.search_rs[s]);
+        if (in_job.enter()) return 1;
+        if (plan_job(j, index_select, search_select)) return 1;
+        for (int s = 0; s < n_search; ++s) at[(size_t) s + 1] = at[(size_t) s] + ((j.search_rs[s]->n_reads + 255) & ~255ull);
+        n_bytes = std::max<uint64_t>(at[(size_t) n_search], 256);
+        if (grow_kept(c, c->d_hits, c->hits_cap, n_bytes, n_bytes) || grow_kept(c, c->d_jobcnt, c->jobcnt_cap, 1, 64)) return 1;
+        d_walked = c->d_jobcnt;
+        HIP_OK(hipMemsetAsync(c->d_hits, 0, n_bytes, c->stream));
+        HIP_OK(hipMemsetAsync(d_walked, 0, sizeof(unsigned long long), c->stream));
+        j.tm.timed = want_times && j.n_chunks() * (uint64_t) (n_search + 4) <= 16384;
+        return 0;
+    }
+
+    int close(int rc, HitsLeave &leave, commet_job_info *info)
+    {
+        c->cur_slot = 0;
+        j.clk.lap(j.ph_launch);
+        if (!rc && hipMemcpyAsync(&c->h_counters[0], d_walked, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream) != hipSuccess)
+            rc = fail("counter copy failed");
+        if (!rc) rc = leave.queue(c);
+        rc = drain_job(j, rc);
+        if (rc) return rc;
+        leave.finish();
+        fill_job_info(j, rc, nullptr, info, c->h_counters[0], 0);
+        if (info) info->total_ms = j.clk.total_ms();
+        return 0;
+    }
+};
+
 // the profile job behind commet_index_and_profile and commet_index_and_thresholds: everything up to the download is the same
 int profile_job(commet_ctx *c, const commet_readset *index_rs, const uint8_t *index_select, int n_search, const commet_readset *const *search_rs,
                 const uint8_t *const *search_select, int max_hits, const ProfileWant &want, commet_job_info *info)
 {
     if (n_search < 0) return fail("n_search must not be negative (got %d)", n_search);
     if (max_hits < 1 || max_hits > 255) return fail("max_hits must be in 1..255 (got %d)", max_hits);
-    JobRun j(c, index_rs, n_search, search_rs);
-    if (validate_job(c, index_rs, n_search, search_rs)) return 1;
-    HIP_OK(hipSetDevice(c->device));
-    SetUse in_job(c, index_rs);                    // offload / export cannot take a set mid-call
-    for (int s = 0; s < n_search; ++s) in_job.add(search_rs[s]);
-    if (in_job.enter()) return 1;
-    if (plan_job(j, index_select, search_select)) return 1;
-    // a byte per read and search set (each set's bytes start on a 256-byte line), and the count of walked reads
-    std::vector<uint64_t> at((size_t) n_search + 1, 0);
-    for (int s = 0; s < n_search; ++s) at[(size_t) s + 1] = at[(size_t) s] + ((search_rs[s]->n_reads + 255) & ~255ull);
-    const uint64_t n_bytes = std::max<uint64_t>(at[(size_t) n_search], 256);
-    if (grow_kept(c, c->d_hits, c->hits_cap, n_bytes, n_bytes) || grow_kept(c, c->d_jobcnt, c->jobcnt_cap, 1, 64)) return 1;
-    unsigned long long *d_walked = c->d_jobcnt;
-    HIP_OK(hipMemsetAsync(c->d_hits, 0, n_bytes, c->stream));
-    HIP_OK(hipMemsetAsync(d_walked, 0, sizeof(unsigned long long), c->stream));
+    BytesJob b(c, index_rs, n_search, search_rs);
+    if (b.open(index_select, search_select, info != nullptr)) return 1;
+    JobRun &j = b.j;
+    const std::vector<uint64_t> &at = b.at;
+    unsigned long long *d_walked = b.d_walked;
     const uint64_t n_chunks = j.n_chunks();
-    j.tm.timed = info != nullptr && n_chunks * (uint64_t) (n_search + 4) <= 16384;
     int rc = 0;
     bool wide = false;                             // the call went through bit-sliced tables, wide or narrow
     if (profile_wide_ok(c, n_chunks, n_search, search_rs)) rc = run_profile_wide(j, max_hits, at, d_walked, info != nullptr, &wide);
     else if (profile_slice_ok(c, n_chunks)) rc = run_profile_sliced(j, max_hits, at, d_walked, info != nullptr, &wide);
-    // the job's slot loop with a cap rule of its own (no group8_ok condition: the hits kernels keep no masks)
-    const int group_cap = (c->k >= 2 && n_chunks >= 2) ? std::max(1, std::min(8, c->chunk_group)) : 1;
     if (!rc && !wide)
-        rc = run_slot_groups(j, group_cap, [&](JobRun &jr, int s, uint64_t, int g, int gs) {
-            return hits_pass(jr, s, g, gs, max_hits, c->d_hits + at[(size_t) s], d_walked);
+        rc = run_slot_groups(j, b.group_cap(), [&](JobRun &jr, int s, uint64_t, int g, int gs) {
+            return hits_pass(jr, s, g, gs, max_hits, b.bytes_of(s), d_walked);
         });
-    c->cur_slot = 0;
-    j.clk.lap(j.ph_launch);
-    if (!rc && hipMemcpyAsync(&c->h_counters[0], d_walked, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream) != hipSuccess)
-        rc = fail("counter copy failed");
     HitsLeave leave;
     for (int s = 0; s < n_search; ++s) {
         const uint8_t *d = c->d_hits + at[(size_t) s];
@@ -303,13 +345,7 @@ int profile_job(commet_ctx *c, const commet_readset *index_rs, const uint8_t *in
                           want.shared_out ? want.shared_out + (size_t) s * want.n_t : nullptr);
         else if (want.hits_out && want.hits_out[s]) leave.bytes_of(d, search_rs[s]->n_reads, want.hits_out[s]);
     }
-    if (!rc) rc = leave.queue(c);
-    rc = drain_job(j, rc);
-    if (rc) return rc;
-    leave.finish();
-    fill_job_info(j, rc, nullptr, info, c->h_counters[0], 0);
-    if (info) info->total_ms = j.clk.total_ms();
-    return 0;
+    return b.close(rc, leave, info);
 }
 
 }  // namespace

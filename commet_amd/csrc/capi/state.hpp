@@ -207,6 +207,8 @@ struct commet_ctx {
     uint64_t hits_cap = 0;
     uint64_t *d_twords = nullptr;                    // the thresholds calls (capi/thresholds.hpp): file ends, per-file counts and tag words of a call's byte arrays, kept between calls
     uint64_t twords_cap = 0;
+    uint16_t *d_thr = nullptr;                       // the relative search (capi/relative.hpp): a threshold per read of every search set of the call, in d_hits' layout, kept between calls
+    uint64_t thr_cap = 0;
     int multi_job = 0;                               // option: 0 = commet_index_many_and_search shares passes between jobs where it can, 1 = job by job, 2 = as 0 + search sets of long reads; commet_index_many_and_profile the same (2 also shares hits passes on long-read search sets)
     int sparse_search = 0;                           // option: 0 auto (a pass over less than half of a set's reads), 1 never, 2 whenever a selection applies
     unsigned long long *d_plansum = nullptr;  // per-block k-mer sums of a selection (host planner input)

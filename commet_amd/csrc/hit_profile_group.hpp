@@ -61,19 +61,28 @@ __device__ __forceinline__ uint32_t slot_byte(uint64_t packed, int i)
 // ---------------------------------------------------------------------------
 // a lane per read: the walk of hits_kernel, NF filters' states side by side.  JOBS = false: the filters of one job fold into the
 // read's byte of `hits` (max_hits, al; js and lines are not looked at).  JOBS = true: the slots belong to the jobs of js, a byte
-// array of `lines` lines of 256 bytes per job (js, lines; max_hits and al are not looked at).
+// array of `lines` lines of 256 bytes per job (js, lines; max_hits and al are not looked at).  REL (one job; relative_search.hpp):
+// the cap is the read's own, thr[r] <= 255, max_hits is not looked at, and `hits` holds found flags: a read with no cap or a flag is
+// not walked, and its flag is set iff a count reaches the cap.
 // ---------------------------------------------------------------------------
-template <typename W, int NF, bool JOBS>
+template <typename W, int NF, bool JOBS, bool REL = false>
 __device__ __forceinline__ void hits_lanes(const ReadsView &rv, const FilterGroupView &fg, int k, int max_hits, JobSlots js,
                                            const uint64_t *__restrict__ sel, uint8_t *__restrict__ hits, uint32_t lines,
-                                           unsigned long long *__restrict__ walked, ActiveList al)
+                                           unsigned long long *__restrict__ walked, ActiveList al, const uint16_t *__restrict__ thr = nullptr)
 {
     static_assert(NF == 2 || NF == 4 || NF == 8, "passes of 2, 4 or 8 filter slots");
+    static_assert(!(JOBS && REL), "a cap per read is one job's");
     const SearchLane me = search_lane(rv, al, sel, nullptr);
     const uint64_t r = me.r;
     int before = 0;
+    int cap = max_hits;                             // (one job) where the walk of the read stops
     bool walk = me.active;
-    if constexpr (!JOBS) {
+    if constexpr (REL) {
+        if (walk) {
+            cap = (int) thr[r];
+            walk = cap != 0 && hits[r] == 0;
+        }
+    } else if constexpr (!JOBS) {
         if (walk) {
             before = (int) hits[r];
             walk = before < max_hits;
@@ -103,7 +112,7 @@ __device__ __forceinline__ void hits_lanes(const ReadsView &rv, const FilterGrou
         // wants a window (or the read ends) — a job that reaches its cap does not end the walk for the others
         const auto more = [&] {
             if constexpr (JOBS) return min_free != INT_MAX;
-            else return best < max_hits;
+            else return best < cap;
         };
         for (uint32_t w = 0; w * 32u < len && more(); ++w) {
             const uint32_t hi = p[3 * w], lo = p[3 * w + 1], va = p[3 * w + 2];
@@ -182,6 +191,8 @@ __device__ __forceinline__ void hits_lanes(const ReadsView &rv, const FilterGrou
                 if (h) hits[(uint64_t) job * lines * 256ull + r] = (uint8_t) h;
                 ++job;
             }
+        } else if constexpr (REL) {
+            if (best >= cap) hits[r] = 1;
         } else {
             const int h = min(max_hits, best);
             if (h > before) hits[r] = (uint8_t) h;
@@ -206,7 +217,8 @@ __global__ __launch_bounds__(LONG_WG) void hits_group_wave_kernel(ReadsView rv, 
                                                                   const uint64_t *__restrict__ sel, uint8_t *__restrict__ hits,
                                                                   unsigned long long *__restrict__ walked, ActiveList al)
 {
-    constexpr bool JOBS = false;
+    constexpr bool JOBS = false, REL = false;
+    constexpr const uint16_t *thr = nullptr;
     constexpr JobSlots js{0, 0};
     constexpr uint32_t lines = 0;
 #include "hit_profile_wave_body.hpp"

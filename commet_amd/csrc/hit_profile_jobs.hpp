@@ -43,7 +43,8 @@ __global__ __launch_bounds__(LONG_WG) void hits_jobs_wave_kernel(ReadsView rv, F
                                                                  const uint64_t *__restrict__ sel, uint8_t *__restrict__ hits, uint32_t lines,
                                                                  unsigned long long *__restrict__ walked)
 {
-    constexpr bool JOBS = true;
+    constexpr bool JOBS = true, REL = false;
+    constexpr const uint16_t *thr = nullptr;
     constexpr int max_hits = 0;
     const ActiveList al{nullptr, nullptr};
 #include "hit_profile_wave_body.hpp"

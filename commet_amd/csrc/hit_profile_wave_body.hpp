@@ -3,8 +3,10 @@
 // __device__ function, the six hits_group_wave_kernel number their scalar registers differently, 98 -> 100 and 100 -> 102 SGPRs in
 // code of the same size, and their lines in tools/kernel_resources.py are to stay as measured; hits_lanes, the lane-per-read body, is
 // a function because there nothing moves.)
-// Expects W, NF, JOBS and rv, fg, k, max_hits, js, sel, hits, lines, walked, al.  JOBS = false: max_hits and al are the kernel's, js
-// and lines are not looked at.  JOBS = true: js and lines are the kernel's, max_hits is not looked at, al is empty.
+// Expects W, NF, JOBS, REL and rv, fg, k, max_hits, js, sel, hits, lines, walked, al, thr.  JOBS = false: max_hits and al are the
+// kernel's, js and lines are not looked at.  JOBS = true: js and lines are the kernel's, max_hits is not looked at, al is empty.
+// REL (one job; rel_group_wave_kernel, relative_search.hpp): the cap is the read's own, thr[r], max_hits is not looked at, and `hits`
+// holds found flags: a read with no cap or a flag is not walked, and its flag is set iff a count reaches the cap.
 //
 // A wave per read: the blocks of hits_wave_kernel (64 consecutive windows per block, staged words, shuffles, persistent grid; (JOBS)
 // `sel` skips the unvisited reads, there is no list).  Per block ONE interleaved plane-A load per lane serves every slot and both
@@ -36,7 +38,11 @@
         if (al.ids) r = (uint64_t) al.ids[item];
         else if (sel && !((sel[r >> 6] >> (r & 63ull)) & 1ull)) continue;
         int before = 0;
-        if constexpr (!JOBS) {
+        int read_cap = max_hits;                           // (one job) where the walk of the read stops
+        if constexpr (REL) {
+            read_cap = __builtin_amdgcn_readfirstlane((int) thr[r]);
+            if (read_cap == 0 || hits[r] != 0) continue;
+        } else if constexpr (!JOBS) {
             before = (int) hits[r];
             if (before >= max_hits) continue;
         }
@@ -52,7 +58,7 @@
         int best = 0;                                      // (one job) the highest of the 2 g counts
         const auto more = [&] {                            // the block loop's end: see the last paragraph above
             if constexpr (JOBS) return min_next != INT_MAX;
-            else return best < max_hits;
+            else return best < read_cap;
         };
         for (int base = 0; base < n_win && more(); base += 64) {
             const int s = base + lane, q = s + k - 1;
@@ -82,7 +88,7 @@
 #pragma unroll
                 for (int j = 1; j < NF; ++j) x = (i == j) ? xa[j] : x;
                 const PlanesBCD bcd = planes_bcd(fg, i);
-                int cap = max_hits;
+                int cap = read_cap;
                 if constexpr (JOBS) cap = __builtin_amdgcn_readlane((int) lane_cap, i);
 #pragma unroll
                 for (int strand = 0; strand < 2; ++strand) {
@@ -134,6 +140,8 @@
                 if (lane == 0 && h) hits[(uint64_t) job * lines * 256ull + r] = (uint8_t) h;
                 ++job;
             }
+        } else if constexpr (REL) {
+            if (lane == 0 && best >= read_cap) hits[r] = 1;
         } else {
             const int h = min(max_hits, best);
             if (lane == 0 && h > before) hits[r] = (uint8_t) h;

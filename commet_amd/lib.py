@@ -101,6 +101,9 @@ SIGNATURES = {
                                               C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(JobInfo)]),
     "commet_index_many_and_thresholds": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p,
                                                    C.POINTER(C.c_int), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(JobInfo)]),
+    "commet_readset_relative_thresholds": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "commet_index_and_search_relative": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                                   C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(JobInfo)]),
     "commet_set_option":(C.c_int, [C.c_void_p, C.c_char_p, C.c_int64]),
     "commet_filter_export_reference": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
     "commet_filter_set_bits": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, u64p]),

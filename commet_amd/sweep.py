@@ -107,10 +107,11 @@ def parser():
     return p
 
 
-def _write_files(api, out, t, loaded_set, h, suffix, rows):
-    """the vectors of one set at threshold t, file by file, as save_bv of the tool writes them: <file>_in_<suffix>.bv"""
+def _write_files(api, out, t, loaded_set, h, suffix, rows, per_t=True):
+    """the vectors of one set at threshold t, file by file, as save_bv of the tool writes them: <file>_in_<suffix>.bv, under out/t<t>
+    (per_t false, commet_amd.relative: under out itself)"""
     tag, entries, _, counts, _ = loaded_set
-    d = os.path.join(out, "t%d" % t)
+    d = os.path.join(out, "t%d" % t) if per_t else out
     os.makedirs(d, exist_ok=True)
     pos = 0
     for (f, _), n in zip(entries, counts):

@@ -395,6 +395,40 @@ int commet_index_many_and_thresholds(commet_ctx *ctx, int n_jobs, const commet_r
                                      const uint8_t *search_select, const int *t, uint8_t *const *tags_out,
                                      uint64_t *const *shared_out, commet_job_info *info);
 
+/* The search with a threshold PER READ, a share of what the read can hold (mixed-length sets: merged pairs, long reads).
+ * The rule, for a read of len bases (every character counts, ACGT or not) on a context of k-mer size k:
+ *     W_r = len / k                                       integer division: the most non-overlapping k-mers the read can hold
+ *     t_r = max(min_hits, (percent * W_r + 99) / 100)     integer arithmetic; percent in 1..100; min_hits < 1 behaves as 1
+ * Read r is found in one chunk filter iff max(F, R) >= t_r, F and R the greedy non-overlapping full hits of its forward and
+ * reverse-complement scan, as for commet_index_and_profile.  Tags are ORed over the chunks of the index set, as in every job; counts
+ * are never summed over chunks: a read whose k-mers are spread over two chunk filters is judged in each alone, as the reference
+ * judges it.  A read with t_r > W_r can never be found and is not walked.  The plan (chunks, the dropped look-ahead read, selections,
+ * file rules) is commet_index_and_profile's and does not depend on the rule.  Hence, where the rule gives every read the same t_r = t,
+ * tags and counts are bit for bit commet_index_and_search's on a context of that t; and on any set, the bit of read r equals
+ * (its byte of commet_index_and_profile at max_hits = T) >= t_r wherever t_r <= T <= 255.
+ * t_r is held in 16 bits: a set whose longest read gives W_r > 65535 is refused with a message (k = 1 on reads above 65 kb and
+ * its like).
+ *
+ * commet_readset_relative_thresholds: thr_out[r] = t_r of every read of rs under no selection, 0 where t_r > W_r
+ * (rel_thresholds_kernel, relative_search.hpp): a planner's number, and the tests' handle on that kernel. */
+int commet_readset_relative_thresholds(commet_ctx *ctx, const commet_readset *rs, int percent, int min_hits,
+                                       uint16_t *thr_out /* n_reads */);
+/* The job: the chunks of index_rs (restricted to index_select) in groups of up to "chunk_group" filters (1 when k < 2 or the job has
+ * one chunk), every search set ONE pass per group by rel_kernel / rel_group_kernel (a lane per read) or, for sets that take
+ * "long_search" as a profile does, rel_wave_kernel / rel_group_wave_kernel (a wave per read): the walks of the hit profile with the
+ * read's own stop — a read found by an earlier pass, one with t_r > W_r and one not selected are not walked; the walk of a read ends
+ * at its t_r-th hit in any filter on any strand.  A set whose largest t_r exceeds 255 takes the wave forms too, unless "long_search"
+ * is 1 (or k < 2): then a filter per pass through rel_kernel.  Passes over few of a set's reads walk their list ("sparse_search").
+ * tags_out[s] (n / 8 + 1 bytes, padding bits zero) = the BooleanVector of search set s, shared_out[s] = one count per file of set s,
+ * both made on the device (hits_tags_kernel); the arrays' entries may be NULL.  The context's own t is not used.
+ * info (may be NULL) as in a job: search_launches = the passes, reads_scanned = the reads the passes walked, probes = 0.
+ * When the device has no room for the thresholds or the found flags the call fails with a message; the context stays usable.
+ * Open: the tiled probe, the wide rows, the narrow tables and passes shared between jobs for this call. */
+int commet_index_and_search_relative(commet_ctx *ctx, const commet_readset *index_rs, const uint8_t *index_select,
+                                     int n_search, const commet_readset *const *search_rs, const uint8_t *const *search_select,
+                                     int percent, int min_hits, uint8_t *const *tags_out, uint64_t *const *shared_out,
+                                     commet_job_info *info);
+
 /* ---- test / measurement hooks --------------------------------------------- */
 /* Tunables / diagnostics, by name.  Unknown names are an error.  None of them changes a result bit, except the test
  * hook max_kmer.
